@@ -61,6 +61,10 @@ def parse_args():
                          "per-step id all-gather, the device barriers and the MAX all-reduce of the timing (and with --gather cabi "
                          "a one-rank RCCL communicator inside the library): the multi-GPU code path on a one-GPU box")
     ap.add_argument("--dump-ids", default=None, help="write the gathered ids of the last timed step to this .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy as float32 (the new token ids "
+                         "[n_gpus * batch, new_tokens] of every rank, gathered; exact in float32): inputs and weights are seeded, "
+                         "so two builds can be compared output for output")
     ap.add_argument("--no-pool-hold", action="store_true",
                     help="pool policy A/B: step whatever rows are active even while another call is prefilling (vc_pool_set_hold(0))")
     ap.add_argument("--no-qkv-fused", action="store_true",
@@ -77,7 +81,10 @@ def parse_args():
     ap.add_argument("--pmc-traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc pass "
                          "(default: the committed FETCH_SIZE pass of this kernel under profiles/)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args) -> int:
@@ -560,6 +567,11 @@ def main():
     ids_checked = len(bad_steps) == 0 and all(np.asarray(o).shape == (world * B, N_new) for o in outs)
     if args.dump_ids and rank == 0:
         np.save(args.dump_ids, outs[-1])
+    if args.dump_outputs and rank == 0:
+        last = np.asarray(outs[-1])
+        assert last.max() < 2 ** 24   # token ids are exact in float32
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "new_token_ids.npy"), last.astype(np.float32))
     # ---- transparency legs, outside the timed region -----------------------------------------------------------------
     # (a) the other residency of the inputs (PCIe-inclusive when `value` is resident, and vice versa)
     k_side = max(n_sess, min(args.steps, 2 * n_sess))

@@ -287,6 +287,80 @@ def tokenizer_orders():
     print("[tokenizer]", {k: [t for t in v if t < 0] for k, v in out.items()})
 
 
+def reference_glue():
+    """The reference's prompt glue on the inputs of tests/test_oracle_golden.py (tokenizer helpers on fixed and on seeded random
+    prompts, get_model_name_from_path, expand2square) and tests/test_cost_eval_emu.py (the conversation templates), inputs and
+    outputs together -> tests/golden/reference_glue.json (`python oracle/gen_golden.py --glue`)."""
+    ref_shim.load_reference()
+    from PIL import Image
+    from vcoder_llava import mm_utils
+    from vcoder_llava.vcoder_conversation import conv_templates
+
+    class Fake:
+        bos_token_id = 1
+
+        def __call__(self, text):
+            class R:
+                pass
+            r = R()
+            r.input_ids = [1] + [3 + (ord(c) % 50) for c in text]
+            return r
+
+    class NoBos(Fake):
+        def __call__(self, text):
+            r = Fake.__call__(self, text)
+            r.input_ids = r.input_ids[1:]
+            return r
+
+    tokenizers = {"Fake": Fake(), "NoBos": NoBos()}
+
+    def outcome(fn):
+        try:
+            out = fn()
+            return ["ok", [int(t) for t in (out.tolist() if hasattr(out, "tolist") else list(out))]]
+        except Exception as e:  # noqa: BLE001
+            return [type(e).__name__, None]
+
+    fixed = []
+    for tk in ("Fake", "NoBos"):
+        for prompt in ("A chat. USER: <depth>\n<seg>\n<image>\nWhat is there? ASSISTANT:", "USER: <seg>\n<image>\nhi",
+                       "USER: <image>\ncount", "<seg>\n<image>\nfirst USER: <seg>\n<image>\nsecond"):
+            name = "tokenizer_depth_seg_token" if "<seg>" in prompt else "tokenizer_image_token"
+            fixed.append({"tokenizer": tk, "prompt": prompt, "fn": name,
+                          "ids": [int(t) for t in getattr(mm_utils, name)(prompt, tokenizers[tk])]})
+    rng = np.random.RandomState(5)
+    words = ["USER:", "what", "is", "there?", "ASSISTANT:", "a", "", "\n", "count the objects"]
+    tags = ["<image>", "<seg>", "<depth>", "<image>\n", "<seg>\n", "<depth>\n"]
+    rand = []
+    for _ in range(400):
+        parts = [str(rng.choice(tags)) if rng.rand() < 0.35 else str(rng.choice(words)) for _ in range(int(rng.randint(1, 9)))]
+        prompt = (" " if rng.rand() < 0.7 else "").join(parts)
+        tk = "Fake" if rng.rand() < 0.6 else "NoBos"
+        rt = "pt" if rng.rand() < 0.2 else None
+        rand.append({"prompt": prompt, "tokenizer": tk, "return_tensors": rt,
+                     "outcomes": {name: outcome(lambda: getattr(mm_utils, name)(prompt, tokenizers[tk], return_tensors=rt))
+                                  for name in ("tokenizer_image_token", "tokenizer_seg_token", "tokenizer_depth_seg_token")}})
+    names = {path: mm_utils.get_model_name_from_path(path)
+             for path in ("a/b/llava-v1.5-7b", "x/vcoder_ds_llava-v1.5-13b/", "/m/checkpoint-100", "org/model/checkpoint-5/", "single")}
+    squares = []
+    for (w, h) in ((7, 7), (9, 4), (3, 10), (1, 6)):
+        img = rng.randint(0, 255, size=(h, w, 3)).astype(np.uint8)
+        sq = mm_utils.expand2square(Image.fromarray(img), (10, 20, 30))
+        squares.append({"image": img.tolist(), "background": [10, 20, 30], "square": np.asarray(sq).tolist()})
+    conv = {}
+    q = "<depth>\n<seg>\n<image>\nWhat is in the image?"
+    for mode in ("llava_v1", "vicuna_v1"):
+        c = conv_templates[mode].copy()
+        c.append_message(c.roles[0], q)
+        c.append_message(c.roles[1], None)
+        conv[mode] = c.get_prompt()
+    with open(os.path.join(GOLD, "reference_glue.json"), "w") as f:
+        json.dump({"tokenizer_fixed": fixed, "tokenizer_random": rand, "model_name_from_path": names,
+                   "expand2square": squares, "conv_question": q, "conv_prompt": conv}, f, separators=(",", ":"))
+    print("[glue]", len(fixed), "fixed prompts,", len(rand), "random prompts,",
+          sum(o[0] == "ok" for r in rand for o in r["outcomes"].values()), "of them tokenized")
+
+
 def main_round2():
     """Fixtures added in round 2 (list-form images, the tower boundary, BOS-less tokenizer orders); the round-1 fixtures
     are left untouched (`python oracle/gen_golden.py --round2`)."""
@@ -554,7 +628,10 @@ if __name__ == "__main__":
         main_round2()
     elif "--round3" in sys.argv:
         main_round3()
+    elif "--glue" in sys.argv:
+        reference_glue()
     else:
         main()
         main_round2()
         main_round3()
+        reference_glue()

@@ -1,6 +1,7 @@
 """Batched COST harness on the emulator: bucketing-by-question batches give exactly the per-sample
 (batch-1, what the reference does) answers; chunking and the answers-file format follow the reference's loader; the
-prompt string equals the reference's conversation template when the reference tree is present."""
+prompt string equals the reference's conversation template (tests/golden/reference_glue.json)."""
+import json
 import os
 
 import numpy as np
@@ -8,7 +9,6 @@ import pytest
 from PIL import Image
 
 import kernel_cases as kc
-import ref_shim
 from vcoder_amd import config as vcfg, synth
 from vcoder_amd.eval import cost_eval as ce
 from vcoder_amd.model import language_model as lm
@@ -71,18 +71,15 @@ def test_batched_equals_per_sample_and_file_format(model, folders, tmp_path):
     assert lines[2].startswith("<<ANSWER>>: ") and set(lines[3]) == {"-"}
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="needs /root/reference (build container only)")
 def test_prompt_equals_reference_template():
-    ref_shim.load_reference()
-    from vcoder_llava.vcoder_conversation import conv_templates
-
+    """build_prompt == the reference's conversation templates (vcoder_conversation.conv_templates) as recorded in
+    tests/golden/reference_glue.json by oracle/gen_golden.py --glue."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_glue.json")) as f:
+        glue = json.load(f)
+    q = "<depth>\n<seg>\n<image>\nWhat is in the image?"
+    assert glue["conv_question"] == q and sorted(glue["conv_prompt"]) == ["llava_v1", "vicuna_v1"]
     for mode in ("llava_v1", "vicuna_v1"):
-        conv = conv_templates[mode].copy()
-        q = "<depth>\n<seg>\n<image>\nWhat is in the image?"
-        conv.append_message(conv.roles[0], q)
-        conv.append_message(conv.roles[1], None)
-        assert ce.build_prompt(q, mode) == conv.get_prompt()
+        assert ce.build_prompt(q, mode) == glue["conv_prompt"][mode]
 
 
 def test_answers_equal_reference_loaders(tmp_path):

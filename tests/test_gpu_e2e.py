@@ -843,11 +843,12 @@ def test_bench_two_ranks_self_launched(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     dump = str(tmp_path / "ids.npy")
+    outputs = str(tmp_path / "outputs")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(VC_BENCH_FORCE_DEVICE="0", VC_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--batch",
-                        "2", "--new-tokens", "6", "--inflight", "2", "--dump-ids", dump], env=env, capture_output=True,
-                       text=True, timeout=600)
+                        "2", "--new-tokens", "6", "--inflight", "2", "--dump-ids", dump, "--dump-outputs", outputs], env=env,
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)
@@ -855,8 +856,13 @@ def test_bench_two_ranks_self_launched(tmp_path):
     assert res["value"] > 0 and "roofline" in res and "composite_roofline" in res and "pcie_inclusive" in res
     # a world > 1 line never times the CPU baseline: it carries the cached N = 1 measurement of the box or says that there is none
     assert "cpu_baseline" in res and ("measured_at" in res["cpu_baseline"] or res["cpu_baseline"]["value"] is None)
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
     got = np.load(dump)
     assert got.shape == (4, 6)
+    # --dump-outputs: what the timed path returned in its last step, gathered over the ranks, as float32
+    assert os.listdir(outputs) == ["new_token_ids.npy"]
+    out = np.load(os.path.join(outputs, "new_token_ids.npy"))
+    assert out.dtype == np.float32 and np.array_equal(out, got)
     cfg = vcfg.vicuna_7b("vcoder_ds")
     eng = HipEngine(cfg)
     eng.load_synthetic(42)

@@ -1,6 +1,5 @@
-"""Pins the oracle (oracle/cpu_ref.py) against the committed outputs of the REAL reference (tests/golden/*.npz,
-produced by oracle/gen_golden.py from /root/reference) and — when the reference tree is present — against the live
-reference itself."""
+"""Pins the oracle (oracle/cpu_ref.py) and the prompt glue against the committed outputs of the REAL reference
+(tests/golden/*.npz and reference_glue.json, produced by oracle/gen_golden.py from the reference tree)."""
 import json
 import os
 
@@ -9,7 +8,6 @@ import pytest
 import torch
 
 import cpu_ref
-import ref_shim
 from vcoder_amd import config as vcfg, mm_utils, synth
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -183,90 +181,89 @@ def test_oracle_tower_boundary():
     assert np.abs(feats - g["features"]).max() < 1e-5
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="needs /root/reference (build container only)")
+class _FakeTokenizer:
+    bos_token_id = 1
+
+    def __call__(self, text):
+        class R:
+            pass
+        r = R()
+        r.input_ids = [1] + [3 + (ord(c) % 50) for c in text]
+        return r
+
+
+class _NoBosTokenizer(_FakeTokenizer):
+    def __call__(self, text):
+        r = _FakeTokenizer.__call__(self, text)
+        r.input_ids = r.input_ids[1:]
+        return r
+
+
+_TOKENIZERS = {"Fake": _FakeTokenizer(), "NoBos": _NoBosTokenizer()}
+
+
+def _reference_glue():
+    """what the reference's prompt glue returned on the inputs below (tests/golden/reference_glue.json, oracle/gen_golden.py --glue)"""
+    with open(os.path.join(GOLD, "reference_glue.json")) as f:
+        return json.load(f)
+
+
 def test_reference_tokenizers_live():
-    ref_shim.load_reference()
-    from vcoder_llava import mm_utils as ref_mm
-
-    class Fake:
-        bos_token_id = 1
-
-        def __call__(self, text):
-            class R:
-                pass
-            r = R()
-            r.input_ids = [1] + [3 + (ord(c) % 50) for c in text]
-            return r
-
-    class NoBos(Fake):
-        def __call__(self, text):
-            r = Fake.__call__(self, text)
-            r.input_ids = r.input_ids[1:]
-            return r
-
-    for tk in (Fake(), NoBos()):
-        for prompt in ("A chat. USER: <depth>\n<seg>\n<image>\nWhat is there? ASSISTANT:", "USER: <seg>\n<image>\nhi",
-                       "USER: <image>\ncount", "<seg>\n<image>\nfirst USER: <seg>\n<image>\nsecond"):
-            fn_r = ref_mm.tokenizer_depth_seg_token if "<seg>" in prompt else ref_mm.tokenizer_image_token
-            fn_o = mm_utils.tokenizer_depth_seg_token if "<seg>" in prompt else mm_utils.tokenizer_image_token
-            assert list(fn_r(prompt, tk)) == list(fn_o(prompt, tk)), (type(tk).__name__, prompt)
+    """The tokenizer helpers == the reference's on fixed prompts, with and without a BOS-prepending tokenizer."""
+    want = _reference_glue()["tokenizer_fixed"]
+    cases = [(tk, prompt) for tk in ("Fake", "NoBos")
+             for prompt in ("A chat. USER: <depth>\n<seg>\n<image>\nWhat is there? ASSISTANT:", "USER: <seg>\n<image>\nhi",
+                            "USER: <image>\ncount", "<seg>\n<image>\nfirst USER: <seg>\n<image>\nsecond")]
+    assert [(w["tokenizer"], w["prompt"]) for w in want] == cases
+    for w in want:
+        fn_o = mm_utils.tokenizer_depth_seg_token if "<seg>" in w["prompt"] else mm_utils.tokenizer_image_token
+        assert w["fn"] == fn_o.__name__
+        assert [int(t) for t in fn_o(w["prompt"], _TOKENIZERS[w["tokenizer"]])] == w["ids"], (w["tokenizer"], w["prompt"])
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not ref_shim.reference_available(), reason="needs /root/reference (build container only)")
 def test_reference_prompt_glue_random_live():
-    """f1 (prompt -> ids glue) against the live reference on random prompts: the three tokenizer helpers on random mixes of words,
+    """f1 (prompt -> ids glue) against the reference on random prompts: the three tokenizer helpers on random mixes of words,
     <image> / <seg> / <depth> tags (any count, any order, with and without the newline), both tokenizer kinds, list and 'pt'
-    returns — same ids or the same exception class; get_model_name_from_path and expand2square on random inputs."""
-    ref_shim.load_reference()
+    returns — same ids or the same exception class; get_model_name_from_path and expand2square on random inputs.  The
+    reference's answers to these inputs are tests/golden/reference_glue.json."""
     from PIL import Image
-    from vcoder_llava import mm_utils as ref_mm
 
-    class Fake:
-        bos_token_id = 1
-
-        def __call__(self, text):
-            class R:
-                pass
-            r = R()
-            r.input_ids = [1] + [3 + (ord(c) % 50) for c in text]
-            return r
-
-    class NoBos(Fake):
-        def __call__(self, text):
-            r = Fake.__call__(self, text)
-            r.input_ids = r.input_ids[1:]
-            return r
+    glue = _reference_glue()
 
     def outcome(fn):
         try:
             out = fn()
-            return "ok", (out.tolist() if hasattr(out, "tolist") else list(out))
+            return ["ok", [int(t) for t in (out.tolist() if hasattr(out, "tolist") else list(out))]]
         except Exception as e:  # noqa: BLE001
-            return type(e).__name__, None
+            return [type(e).__name__, None]
 
     rng = np.random.RandomState(5)
     words = ["USER:", "what", "is", "there?", "ASSISTANT:", "a", "", "\n", "count the objects"]
     tags = ["<image>", "<seg>", "<depth>", "<image>\n", "<seg>\n", "<depth>\n"]
     n_ok = 0
-    for c in range(400):
+    assert len(glue["tokenizer_random"]) == 400
+    for want in glue["tokenizer_random"]:
         parts = [str(rng.choice(tags)) if rng.rand() < 0.35 else str(rng.choice(words)) for _ in range(int(rng.randint(1, 9)))]
         prompt = (" " if rng.rand() < 0.7 else "").join(parts)
-        tk = Fake() if rng.rand() < 0.6 else NoBos()
+        tk = "Fake" if rng.rand() < 0.6 else "NoBos"
         rt = "pt" if rng.rand() < 0.2 else None
+        assert (want["prompt"], want["tokenizer"], want["return_tensors"]) == (prompt, tk, rt)
         for name in ("tokenizer_image_token", "tokenizer_seg_token", "tokenizer_depth_seg_token"):
-            a = outcome(lambda: getattr(ref_mm, name)(prompt, tk, return_tensors=rt))
-            b = outcome(lambda: getattr(mm_utils, name)(prompt, tk, return_tensors=rt))
-            assert a == b, (name, type(tk).__name__, repr(prompt), a, b)
+            a = want["outcomes"][name]
+            b = outcome(lambda: getattr(mm_utils, name)(prompt, _TOKENIZERS[tk], return_tensors=rt))
+            assert a == b, (name, tk, repr(prompt), a, b)
             n_ok += a[0] == "ok"
     assert n_ok > 600
+    names = glue["model_name_from_path"]
+    assert len(names) == 5
     for path in ("a/b/llava-v1.5-7b", "x/vcoder_ds_llava-v1.5-13b/", "/m/checkpoint-100", "org/model/checkpoint-5/", "single"):
-        assert ref_mm.get_model_name_from_path(path) == mm_utils.get_model_name_from_path(path), path
-    for (w, h) in ((7, 7), (9, 4), (3, 10), (1, 6)):
-        img = Image.fromarray(rng.randint(0, 255, size=(h, w, 3)).astype(np.uint8))
-        a, b = ref_mm.expand2square(img, (10, 20, 30)), mm_utils.expand2square(img, (10, 20, 30))
-        assert a.size == b.size and np.array_equal(np.asarray(a), np.asarray(b)), (w, h)
+        assert names[path] == mm_utils.get_model_name_from_path(path), path
+    for (w, h), want in zip(((7, 7), (9, 4), (3, 10), (1, 6)), glue["expand2square"]):
+        img = rng.randint(0, 255, size=(h, w, 3)).astype(np.uint8)
+        assert np.array_equal(img, np.asarray(want["image"], dtype=np.uint8))
+        a = np.asarray(want["square"], dtype=np.uint8)
+        b = np.asarray(mm_utils.expand2square(Image.fromarray(img), tuple(want["background"])))
+        assert a.shape == b.shape and np.array_equal(a, b), (w, h)
 
 
 def test_sampling_oracle_equals_hf_warpers():
