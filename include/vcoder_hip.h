@@ -204,6 +204,17 @@ int vc_plan_spliced_len(vc_model* m, const int64_t* ids, int B, int T, const flo
  * next_tok [B] host (greedy argmax, lowest index on ties) or NULL. */
 int vc_decode_step(vc_model* m, const int32_t* tok, float* logits, int32_t* next_tok);
 
+/* multi-token continuation of a cached sequence (HF LlamaModel over past_key_values with n > 1 new ids, no images): tok [B, n]
+ * host, B = the batch of the last vc_prefill, at positions P .. P+n-1 (P = the loop's position), causal inside the chunk, every
+ * cached key visible except those the prefill's attention_mask hides (while vc_decode_step would hide them).  logits_all
+ * [B, n, V] host or NULL; logits_last [B, V] (row n-1 of each sequence) host or NULL.  Honours vc_request_hidden_states
+ * ([(layers + 1), B, n, hidden]) and vc_request_attentions ([layers, B, heads, n, P+n]).  Afterwards the loop stands at P + n:
+ * vc_decode_step continues there (tok = NULL: from the greedy choice of the last logits), vc_reorder_cache applies, a cache
+ * that runs past its reserve grows.  Precision mode "bf16": the extend path (attention over the cache with n queries per
+ * head, GEMV linears up to 128 rows, GEMMs above); "strict" / "split": n cached steps, bit-identical to n vc_decode_step
+ * calls.  A refused call (bad ids, shape, state) changes nothing. */
+int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logits_all, float* logits_last);
+
 /* beam search support: the KV rows of the current vc_prefill / vc_decode_step loop are permuted, row r <- old row src_rows[r] —
  * `past_key_values` reordered by beam_idx after a beam step ([HF] generation/utils.py beam_search; the reference's eval loaders
  * forward num_beams: eval/model_seg_loader.py:129-139) */

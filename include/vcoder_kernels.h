@@ -88,6 +88,13 @@ void vck_attention_decode_fused(const uint16_t* qkv, uint16_t* k, uint16_t* v, u
 void vck_attention_decode_rows(const uint16_t* qkv, uint16_t* k, uint16_t* v, uint16_t* out, int B, int H, int hd,
                                int kv_stride, const int* pos_rows, int pos_stride, const int* active_rows,
                                const float* rope_cos, const float* rope_sin, float scale, void* stream);
+/* extend attention (a multi-token continuation of a cached sequence): n roped queries per (b, h) (q [B,H,q_stride,hd]) at
+ * positions P .. P+n-1 over keys [0, P+n) of the key-major decode cache (k, v [B,H,kv_stride,hd]: bf16, or e4m3 bytes when
+ * kv8), causal inside the chunk; key_mask [B][mask_stride] bytes (0 = hidden; key 0 must be visible) or NULL.  hd 128.
+ * out bf16 [B*n, H*hd], row b*n + t. */
+void vck_attention_extend(const uint16_t* q, const void* k, const void* v, uint16_t* out, int B, int H, int n, int P, int hd,
+                          int q_stride, int kv_stride, int kv8, float scale, const uint8_t* key_mask, int mask_stride,
+                          void* stream);
 /* embedding gather + feature splice (vcoder_ds_llava_arch.py:173-276,305) */
 void vck_splice(const int* row_src, int nrows, const uint16_t* embed, const uint16_t* feats, float* x, int D, void* stream);
 void vck_embed_tokens(const int* tok, const uint16_t* embed, float* x, int B, int D, void* stream);

@@ -536,6 +536,74 @@ def bench_gemv_fp8():
                   flush=True)
 
 
+def bench_extend_linears():
+    """vc_extend's routing question: one 7b decoder layer's linears (qkv, o, gate-up, down) over M token rows as
+    ceil(M / 32) passes of the weight-streaming decode GEMV (folded-RMSNorm operands, as decode_linears runs them) against
+    one prefill GEMM per matrix (with the split-K workspace, as the engine calls it)."""
+    shapes = [(12288, 4096, 0, 0, "qkv"), (4096, 4096, 2, 4, "o"), (22016, 4096, 3, 5, "gate-up"), (4096, 11008, 2, 4, "down")]
+    npart = (4096 // 16 + 15) // 16 * 16
+    ws = torch.zeros(16 << 20, device=dev)
+    Ws = {N * K: [bf16(N * K, scale=0.02) for _ in range(4)] for (N, K, _, _, _) in shapes}
+    for M in (32, 48, 64, 96, 128, 160, 192, 256):
+        t_gemv = t_gemm = 0.0
+        for (N, K, epi_v, epi_g, name) in shapes:
+            W = Ws[N * K]
+            X = bf16(M, K)
+            outv = torch.zeros((M, N), dtype=torch.float32 if epi_v == 2 else torch.bfloat16, device=dev)
+            ldo = N // 2 if epi_v == 3 else N
+            ssq = torch.rand(M, npart, device=dev)
+            gw = torch.rand(N, device=dev) + 0.5
+            xg = torch.zeros((M, N), dtype=torch.bfloat16, device=dev)
+            scratch = torch.zeros(8 * (N // 16 + 1) * 2 * 256, device=dev)
+            counters = torch.zeros((N // 16 + 1) * 2, dtype=torch.int32, device=dev)
+            it = [0]
+
+            def passes():
+                it[0] += 1
+                w = W[it[0] % 4]
+                for m0 in range(0, M, 32):
+                    mr = min(32, M - m0)
+                    if epi_v == 2:
+                        lib.vck_gemv_ex(P(X[m0:]), P(w), None, P(outv[m0:]), None, P(ssq[m0:]), P(gw), P(xg[m0:]), npart,
+                                        C.c_float(1e-5), P(scratch), P(counters), 0, mr, N, K, ldo, epi_v, None)
+                    else:
+                        lib.vck_gemv_ex(P(X[m0:]), P(w), None, P(outv[m0:]), P(ssq[m0:]), None, None, None, npart, C.c_float(1e-5),
+                                        None, None, 0, mr, N, K, ldo, epi_v, None)
+            uv = timeit(passes, iters=20)
+            outg = torch.zeros((M, N), dtype=torch.float32 if epi_g == 4 else torch.bfloat16, device=dev)
+            ldg = N // 2 if epi_g == 5 else N
+
+            def gemm():
+                it[0] += 1
+                lib.vck_gemm_ws(P(X), P(W[it[0] % 4]), None, P(outg), M, N, K, K, K, ldg, epi_g, P(ws), C.c_size_t(64 << 20), None)
+            ug = timeit(gemm, iters=20)
+            t_gemv += uv
+            t_gemm += ug
+            print(f"extend_linears M{M:3d} {name:8s}: GEMV x{(M + 31) // 32} {uv:7.1f} us | GEMM {ug:7.1f} us", flush=True)
+        print(f"extend_linears M{M:3d} layer: GEMV passes {t_gemv:7.1f} us | GEMM {t_gemm:7.1f} us -> "
+              f"{'GEMV' if t_gemv < t_gemm else 'GEMM'}", flush=True)
+
+
+def bench_extend_attn():
+    """attention_extend_kernel at 7b (32 heads, hd 128) over a VCoder-DS prompt (P = 1216): time and the K / V bytes it must
+    read (every cached key once per (b, h): 2 (P + n) hd bytes-per-element) over the 8 TB/s HBM peak"""
+    H, hd, Pp = 32, 128, 1216
+    for kv8 in (0, 1):
+        es = 1 if kv8 else 2
+        for B in (1, 8):
+            for n in (1, 8, 32, 64, 128, 512):
+                S = (Pp + n + 63) // 64 * 64
+                q = bf16(B, H, n, hd)
+                k = torch.randint(0, 120, (B, H, S, hd * es), dtype=torch.uint8, device=dev) if kv8 else bf16(B, H, S, hd)
+                v = torch.randint(0, 120, (B, H, S, hd * es), dtype=torch.uint8, device=dev) if kv8 else bf16(B, H, S, hd)
+                out = torch.zeros((B * n, H * hd), dtype=torch.bfloat16, device=dev)
+                us = timeit(lambda: lib.vck_attention_extend(P(q), P(k), P(v), P(out), B, H, n, Pp, hd, n, S, kv8,
+                                                             C.c_float(1 / math.sqrt(hd)), None, 0, None), iters=20)
+                byts = 2.0 * B * H * (Pp + n) * hd * es
+                print(f"extend_attn kv8={kv8} B{B} n{n:3d} P{Pp}: {us:8.1f} us  {byts / us / 1e3:7.1f} GB/s = "
+                      f"{byts / us / 1e3 / 8000:.2f} of 8 TB/s", flush=True)
+
+
 def bench_attn():
     for (B, H, T, hd, causal, name) in [(8, 32, 1216, 128, 1, "llm prefill"), (24, 16, 577, 64, 0, "vit")]:
         Ts = (T + 63) // 64 * 64
@@ -573,6 +641,7 @@ if __name__ == "__main__":
     table = {"gemm_qkv": bench_gemm_qkv, "gemm32": bench_gemm32, "gemm": bench_gemm, "gemv": bench_gemv, "attn": bench_attn, "dattn": bench_dattn, "gemv_fp8": bench_gemv_fp8,
              "gemv13": bench_gemv13, "gemv_pair": bench_gemv_pair, "gemv_rows": bench_gemv_rows, "dattn_rows": bench_dattn_rows,
              "gemm_f8": bench_gemm_f8, "gemv_rows8": bench_gemv_rows8, "gemv_wide": bench_gemv_wide, "gemm_chunk": bench_gemm_chunk,
-             "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks}
+             "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,
+             "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn}
     for w in what:
         table[w]()

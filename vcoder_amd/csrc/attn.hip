@@ -15,6 +15,9 @@
 // contraction order over keys is permuted identically on both operands).
 #include <stdlib.h>
 
+#include <stdexcept>
+#include <type_traits>
+
 #include "vc_device.h"
 #include "kernels.h"
 
@@ -600,6 +603,202 @@ void launch_attention(const AttnArgs& a, hipStream_t s) {
         else if (variant == 2) launch_attention_v<64, 8, 2>(a, s);
         else launch_attention_v<64, 8, 1>(a, s);
     }
+}
+
+// =============================================================================================
+// extend attention: n new queries of one (b,h) at positions P + t over the P + n keys of the DECODE cache (key-major K and V,
+// bf16 or e4m3).  Workgroup = 64 queries as 4 waves x 16; key tiles of 64; MFMA 16x16x32 and the fp32 online softmax of
+// attention_kernel (S^T = K Q^T, O^T = V^T P^T, the same fragment layouts and LDS swizzles).
+//
+// V arrives key-major, but O^T = V^T P^T wants V^T tiles.  The flash kernel's prefill gets them from a V^T scratch written by
+// qkv_split; here the cache IS the operand, so the transpose happens in the register-staged LDS write: each thread loads 4 dims
+// of the eight keys that make up one 16-byte chunk of the V^T key order (keys 4c..4c+3 and 16+4c..16+4c+3 of a 32-key block,
+// vt_chunk_key0) and writes, per dim, that whole chunk — the transpose costs 4 ds_write_b128 per thread and tile, and no two
+// threads share a 16-byte chunk.  Chosen over ds_read_b64_tr_b16 because (i) the e4m3 cache must pass through registers anyway to be
+// widened, so one staging path serves both cache formats; (ii) the read side stays the flash kernel's conflict-free
+// ds_read_b128 of a key-ordered V^T tile; (iii) the staging registers double as the prefetch of the next tile (its loads are
+// in flight during the MFMAs of the current one), the form the guide rates best for attention forward.
+// Keys past P + n (the cache's unwritten tail) are staged as zeros: a masked score is 0 after exp, but 0 x NaN is not.
+// =============================================================================================
+template <int HD, bool KV8>
+__global__ __launch_bounds__(256) void attention_extend_kernel(AttnExtendArgs p) {
+    static_assert(HD == 128, "the extend kernel's staging map covers hd 128");
+    constexpr int WAVES = 4, QB = WAVES * 16;   // 64 queries per workgroup
+    constexpr int KS = HD / 32, DT = HD / 16, KCH = HD / 8;
+    constexpr int KB_ = 64 * HD * 2;            // K tile [64 keys][HD] bf16, then V^T tile [HD][64 keys]
+    constexpr int KLD = 64 * KCH / 256;         // K chunks per thread and tile (4)
+    using Raw = typename std::conditional<KV8, u32x2, u32x4>::type;   // 8 elements as they sit in the cache
+    using Raw4 = typename std::conditional<KV8, uint32_t, u32x2>::type;   // 4 elements
+    VC_DYNAMIC_SMEM(char, lds);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, j = lane & 15;
+    const int q0 = blockIdx.x * QB, h = blockIdx.y, b = blockIdx.z;
+    const int n = p.n, P = p.P, Tk = P + n;
+    const size_t bh = (size_t)b * p.H + h;
+    constexpr int ESZ = KV8 ? 1 : 2;
+    const char* kbase = reinterpret_cast<const char*>(p.k) + bh * p.kv_stride * (size_t)(HD * ESZ);
+    const char* vbase = reinterpret_cast<const char*>(p.v) + bh * p.kv_stride * (size_t)(HD * ESZ);
+    const bf16_t* qbase = p.q + bh * p.q_stride * HD;
+    const uint8_t* km = p.key_mask != nullptr ? p.key_mask + (size_t)b * p.mask_stride : nullptr;
+
+    u32x4 qf[KS];
+    {
+        const int qrow = min(q0 + wave * 16 + j, n - 1);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = ld16(qbase + (size_t)qrow * HD + ks * 32 + g * 8);
+    }
+    f32x4 o[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+    const float c2 = p.scale * 1.4426950408889634f;
+    const int kv_end = min(Tk, P + q0 + QB);
+    const int nkt = (kv_end + 63) / 64;
+
+    // staging map.  K: chunk c = i * 256 + tid -> key row c / KCH, 16-byte slot c % KCH (16 threads read one 256-byte row).
+    // V: thread = (V^T chunk vch = tid / 32 of the tile: block vch / 4, c = vch % 4; dims 4 vd .. 4 vd + 3, vd = tid % 32)
+    static_assert(HD / 4 == 32, "V staging: 32 threads per key row");
+    const int vch = tid / 32, vd = tid % 32;
+    const int vkey0 = (vch / 4) * 32 + (vch % 4) * 4;   // key of V^T position 8 vch + e: vkey0 + (e & 3) + 16 (e >> 2)
+    Raw kr[KLD];
+    Raw4 vr[8];
+    auto load_tile = [&](int kt) {
+        const int k0 = kt * 64;
+#pragma unroll
+        for (int i = 0; i < KLD; ++i) {
+            const int c = i * 256 + tid, row = c / KCH, slot = c % KCH;
+            if (k0 + row < Tk) kr[i] = *reinterpret_cast<const Raw*>(kbase + ((size_t)(k0 + row) * HD + slot * 8) * ESZ);
+            else kr[i] = Raw{};
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int key = k0 + vkey0 + (e & 3) + 16 * (e >> 2);
+            if (key < Tk) vr[e] = *reinterpret_cast<const Raw4*>(vbase + ((size_t)key * HD + vd * 4) * ESZ);
+            else vr[e] = Raw4{};
+        }
+    };
+    auto widen = [](const Raw& x) -> u32x4 {
+        if constexpr (KV8) {
+            const u32x2 lo = fp8x4_to_bf16x4(x[0]), hi = fp8x4_to_bf16x4(x[1]);
+            return u32x4{lo[0], lo[1], hi[0], hi[1]};
+        } else {
+            return x;
+        }
+    };
+    auto store_tile = [&]() {
+#pragma unroll
+        for (int i = 0; i < KLD; ++i) {
+            const int c = i * 256 + tid, row = c / KCH, slot = c % KCH;
+            st16(lds + swz_k<HD>(row, slot), widen(kr[i]));
+        }
+        // V^T: chunk vch of row d holds the eight keys' elements of dim d in position order
+        u32x2 w[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if constexpr (KV8) w[e] = fp8x4_to_bf16x4(vr[e]);
+            else w[e] = vr[e];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t sh = (i & 1) * 16;
+            uint32_t x[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = (w[e][i >> 1] >> sh) & 0xFFFFu;
+            st16(lds + KB_ + swz_v(vd * 4 + i, vch),
+                 u32x4{x[0] | (x[1] << 16), x[2] | (x[3] << 16), x[4] | (x[5] << 16), x[6] | (x[7] << 16)});
+        }
+    };
+
+    const int w_first = q0 + wave * 16;   // smallest query of this wave
+    if (nkt > 0) load_tile(0);
+    for (int kt = 0; kt < nkt; ++kt) {
+        __syncthreads();   // every wave is done reading the previous tile
+        store_tile();
+        __syncthreads();
+        if (kt + 1 < nkt) load_tile(kt + 1);   // in flight under this tile's MFMAs
+        const int k0 = kt * 64;
+        if (w_first >= n || k0 > P + w_first + 15) continue;   // no query of the wave, or every key in their future
+        f32x4 sacc[4];
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub) sacc[sub] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) sacc[sub] = mfma16(ld16(lds + swz_k<HD>(sub * 16 + j, ks * 4 + g)), qf[ks], sacc[sub]);
+        const int query = w_first + j;
+        if (k0 + 63 > P + w_first || k0 + 64 > Tk || km != nullptr) {   // a tile with a hidden key (wave-uniform)
+#pragma unroll
+            for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int key = k0 + sub * 16 + g * 4 + r;
+                    if (key >= Tk || key > P + query || (km != nullptr && km[key] == 0)) sacc[sub][r] = -INFINITY;
+                }
+        }
+        float mx = vmax3(sacc[0][0], sacc[0][1], sacc[0][2]);
+        mx = vmax3(mx, sacc[0][3], sacc[1][0]);
+        mx = vmax3(mx, sacc[1][1], sacc[1][2]);
+        mx = vmax3(mx, sacc[1][3], sacc[2][0]);
+        mx = vmax3(mx, sacc[2][1], sacc[2][2]);
+        mx = vmax3(mx, sacc[2][3], sacc[3][0]);
+        mx = vmax3(mx, sacc[3][1], sacc[3][2]);
+        mx = vmax2(mx, sacc[3][3]);
+        mx = rows_max(mx);
+        // deferred maximum as in attention_kernel (the reference point moves only when a score exceeds it by e^8); key 0 is
+        // visible to every query (causal from P >= 0; the engine checks the key mask), so the point is finite from tile 0 on
+        constexpr float DEFER = 11.5f;
+        const bool grew = wave_any((mx - m_run) * c2 > DEFER);
+        const float m_new = grew ? vmax2(m_run, mx) : m_run;
+        const float alpha = grew ? fast_exp2((m_run - m_new) * c2) : 1.0f;
+        m_run = m_new;
+        const float mc = m_new * c2;
+        float rs = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < 4; ++sub)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float e = fast_exp2(fmaf(sacc[sub][r], c2, -mc));   // hidden: 0
+                sacc[sub][r] = e;
+                rs += e;
+            }
+        if (grew) {
+            l_run = l_run * alpha;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) o[dt] = o[dt] * alpha;
+        }
+        l_run += rs;
+        u32x4 pb[2];
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh)
+            pb[kh] = u32x4{pack_bf2(sacc[2 * kh][0], sacc[2 * kh][1]), pack_bf2(sacc[2 * kh][2], sacc[2 * kh][3]),
+                           pack_bf2(sacc[2 * kh + 1][0], sacc[2 * kh + 1][1]), pack_bf2(sacc[2 * kh + 1][2], sacc[2 * kh + 1][3])};
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int kh = 0; kh < 2; ++kh) o[dt] = mfma16(ld16(lds + KB_ + swz_v(dt * 16 + j, kh * 4 + g)), pb[kh], o[dt]);
+    }
+    float l = l_run;
+    l += shfl_xor(l, 16);
+    l += shfl_xor(l, 32);
+    const int query = q0 + wave * 16 + j;
+    if (query < n) {
+        const float inv = 1.0f / l;
+        bf16_t* dst = p.out + ((size_t)b * n + query) * ((size_t)p.H * HD) + h * HD + g * 4;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) {
+            const f32x4 v = o[dt] * inv;
+            st8(dst + dt * 16, u32x2{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])});
+        }
+    }
+}
+
+void launch_attention_extend(const AttnExtendArgs& a, hipStream_t s) {
+    if (a.hd != 128) throw std::runtime_error("attention_extend: head dim 128 only");
+    if (a.n < 1 || a.P < 0 || a.P + a.n > a.kv_stride) throw std::runtime_error("attention_extend: positions exceed the cache");
+    const dim3 grid((a.n + 63) / 64, a.H, a.B), block(256);
+    constexpr size_t shmem = 2 * 64 * 128 * 2;   // K tile + V^T tile
+    if (a.kv8) VC_LAUNCH((attention_extend_kernel<128, true>), grid, block, shmem, s, a);
+    else VC_LAUNCH((attention_extend_kernel<128, false>), grid, block, shmem, s, a);
 }
 
 // =============================================================================================

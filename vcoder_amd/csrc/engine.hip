@@ -198,6 +198,7 @@ struct vc_model {
     // decode state of this session's own loop (vc_prefill / vc_decode_step, strict mode, generate with the pool off)
     Buf x_dec, xg_dec, qkv_dec, attn_dec, h_dec, logits, next_tok, out_ids, rows, dsum, ssq;
     Buf sk_scratch, sk_counters;  // split-K partials / arrival counters of the decode GEMV (few-tile matrices)
+    Buf ext_tok;                  // token ids of a vc_extend call [B, n]
     Buf gemm_ws;                  // fp32 workspace of the GEMM's split-K remainder round (64 MiB)
     int out_stride = 0;           // out_ids ints per row
     int last_S = 0;               // spliced prompt length of the last prefill / generate

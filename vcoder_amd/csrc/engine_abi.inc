@@ -187,7 +187,8 @@ VC_API void vc_model_destroy(vc_model* m) {
                    &m->out_ids, &m->dsum, &m->ssq, &m->sk_scratch, &m->sk_counters, &m->gemm_ws, &m->s_cols, &m->s_patches, &m->s_vx, &m->s_vxn, &m->s_vqkv,
                    &m->s_vq, &m->s_vk, &m->s_vv, &m->s_vattn, &m->s_vh, &m->s_sel, &m->s_mid, &m->s_feats, &m->s_xn, &m->s_qkv,
                    &m->s_q, &m->s_attn, &m->s_h, &m->s_kc, &m->s_vc, &m->s_xl, &m->pp_src, &m->pp_sq, &m->pp_tmp, &m->pp_out,
-                   &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre})
+                   &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre,
+                   &m->ext_tok})
         b->release();
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
@@ -718,10 +719,8 @@ VC_API int vc_reorder_cache(vc_model* m, const int32_t* src_rows, int B) {
     GUARD_END(m->ctx)
 }
 
-VC_API int vc_decode_step(vc_model* m, const int32_t* tok, float* logits, int32_t* next_tok) {
-    if (!m) return VC_ERR_INVALID;
-    GUARD_BEGIN
-    USE_DEVICE(m->ctx);
+// one cached step of the session's loop (vc_decode_step; vc_extend in precision modes "strict" / "split")
+void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* next_tok) {
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_decode_step before vc_prefill");
     if (m->cur_pos + 1 > m->capS) grow_kv(m, m->cur_pos + 1);
     const int B = m->curB;
@@ -753,6 +752,102 @@ VC_API int vc_decode_step(vc_model* m, const int32_t* tok, float* logits, int32_
     if (logits) HIPCHK(hipMemcpyAsync(logits, m->logits.p, (size_t)B * m->c.vocab * 4, hipMemcpyDeviceToHost, m->st));
     if (next_tok) HIPCHK(hipMemcpyAsync(next_tok, m->next_tok.p, B * 4, hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
+}
+
+VC_API int vc_decode_step(vc_model* m, const int32_t* tok, float* logits, int32_t* next_tok) {
+    if (!m) return VC_ERR_INVALID;
+    GUARD_BEGIN
+    USE_DEVICE(m->ctx);
+    decode_step_impl(m, tok, logits, next_tok);
     GUARD_END(m->ctx)
 }
 
+/* Multi-token continuation of the session's cached rows: tok [B, n] at positions P .. P+n-1 (P = the loop's position).  See
+ * include/vcoder_hip.h. */
+VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logits_all, float* logits_last) {
+    if (!m) return VC_ERR_INVALID;
+    float* const hidden_req = m->hidden_out;
+    float* const attn_req = m->attn_out;
+    const size_t hidden_cap = m->hidden_cap, attn_cap = m->attn_cap;
+    struct Requests {   // one-shot, also when the call fails
+        vc_model* m;
+        ~Requests() {
+            m->hidden_out = nullptr;
+            m->attn_out = nullptr;
+            m->hidden_cap = m->attn_cap = 0;
+        }
+    } requests{m};
+    GUARD_BEGIN
+    USE_DEVICE(m->ctx);
+    const vc_model_cfg& c = m->c;
+    // every check before anything is enqueued: a refused call leaves the cache and the loop's state as they were
+    REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_extend before vc_prefill");
+    REQUIRE(tok && n >= 1, VC_ERR_INVALID, "vc_extend needs n >= 1 tokens per row");
+    REQUIRE(B == m->curB, VC_ERR_INVALID, "vc_extend: %d rows given, the session's loop has %d", B, m->curB);
+    for (size_t i = 0; i < (size_t)B * n; ++i)
+        REQUIRE(tok[i] >= 0 && tok[i] < c.vocab, VC_ERR_INDEX, "index out of range in self (token id %d)", tok[i]);
+    const int P = m->cur_pos, V = c.vocab, L = c.layers;
+    REQUIRE(P + n <= c.max_positions / 64 * 64, VC_ERR_STATE, "KV cache full: position %d exceeds max_position_embeddings=%d",
+            P + n, c.max_positions);
+    REQUIRE(!attn_req || P + n <= 4096, VC_ERR_INVALID, "output_attentions: at most 4096 positions");
+    REQUIRE(!hidden_req || hidden_cap >= (size_t)(L + 1) * B * n * c.hidden, VC_ERR_INVALID, "hidden-state buffer too small");
+    REQUIRE(!attn_req || attn_cap >= (size_t)L * B * c.heads * n * (P + n), VC_ERR_INVALID, "attention buffer too small");
+    if (m->precision != 0) {
+        // "strict" / "split": n cached steps of the session's loop (the same launches as n vc_decode_step calls); the per-step
+        // diagnostics are gathered into the [.., B, n, ..] layouts of the call
+        const size_t D = c.hidden, H = c.heads;
+        std::vector<int32_t> col(B);
+        std::vector<float> step_lg((size_t)B * V), hs, at;
+        if (attn_req) std::fill(attn_req, attn_req + (size_t)L * B * H * n * (P + n), 0.f);
+        for (int t = 0; t < n; ++t) {
+            for (int b = 0; b < B; ++b) col[b] = tok[(size_t)b * n + t];
+            if (hidden_req) {
+                hs.assign((L + 1) * B * D, 0.f);
+                m->hidden_out = hs.data();
+                m->hidden_cap = hs.size();
+            }
+            if (attn_req) {
+                at.assign((size_t)L * B * H * (P + t + 1), 0.f);
+                m->attn_out = at.data();
+                m->attn_cap = at.size();
+            }
+            decode_step_impl(m, col.data(), step_lg.data(), nullptr);
+            if (logits_all)
+                for (int b = 0; b < B; ++b) memcpy(logits_all + ((size_t)b * n + t) * V, step_lg.data() + (size_t)b * V, (size_t)V * 4);
+            if (hidden_req)
+                for (size_t e = 0; e < (size_t)(L + 1) * B; ++e)
+                    memcpy(hidden_req + (e * n + t) * D, hs.data() + e * D, D * 4);
+            if (attn_req)
+                for (size_t e = 0; e < (size_t)L * B * H; ++e)
+                    memcpy(attn_req + (e * n + t) * (P + n), at.data() + e * (P + t + 1), (size_t)(P + t + 1) * 4);
+        }
+        if (logits_last) memcpy(logits_last, step_lg.data(), step_lg.size() * 4);
+        return VC_OK;
+    }
+    if (P + n > m->capS) grow_kv(m, P + n);
+    m->hidden_out = hidden_req;
+    m->hidden_cap = hidden_cap;
+    m->attn_out = attn_req;
+    m->attn_cap = attn_cap;
+    m->ext_tok.ensure((size_t)B * n * 4);
+    HIPCHK(hipMemcpyAsync(m->ext_tok.p, tok, (size_t)B * n * 4, hipMemcpyHostToDevice, m->st));
+    const bool all_rows = logits_all != nullptr || B * n <= EXTEND_GEMV_ROWS;
+    run_extend(m, m->ext_tok.as<int>(), B, n, logits_all != nullptr);
+    if (all_rows)   // each sequence's last row -> the loop's logits rows (what a decode step leaves there)
+        HIPCHK(hipMemcpy2DAsync(m->logits.p, (size_t)V * 4, m->logits_all.as<float>() + (size_t)(n - 1) * V, (size_t)n * V * 4,
+                                (size_t)V * 4, B, hipMemcpyDeviceToDevice, m->st));
+    // the rows now stand at P + n; the greedy choice of their last logits feeds vc_decode_step(tok = NULL), as after a prefill
+    std::vector<int> rec((size_t)B * RS_STRIDE);
+    HIPCHK(hipMemcpyAsync(rec.data(), m->rows.p, rec.size() * 4, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipStreamSynchronize(m->st));
+    for (int b = 0; b < B; ++b) rec[(size_t)b * RS_STRIDE + RS_POS] += n;
+    HIPCHK(hipMemcpyAsync(m->rows.p, rec.data(), rec.size() * 4, hipMemcpyHostToDevice, m->st));
+    const LoopView v = session_view(m);
+    launch_select_embed(select_args(m, v, v.logits, B, 0), m->st);
+    m->cur_pos = P + n;
+    if (logits_all)
+        HIPCHK(hipMemcpyAsync(logits_all, m->logits_all.p, (size_t)B * n * V * 4, hipMemcpyDeviceToHost, m->st));
+    if (logits_last) HIPCHK(hipMemcpyAsync(logits_last, m->logits.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipStreamSynchronize(m->st));   // `rec` is host memory
+    GUARD_END(m->ctx)
+}

@@ -518,6 +518,124 @@ void enqueue_decode_step_strict(vc_model* m, int B) {
     launch_select_embed(select_args(m, v, v.logits, B, 3), v.st);
 }
 
+// ---- multi-token continuation of the session's cached rows (vc_extend), precision mode 0 ----------------------------------
+// M = B n new rows (row b n + t = token t of sequence b at position P + t).  Per layer: QKV projection -> RoPE at P + t and the
+// K / V rows written into the cache at P + t (qkv_split_kernel over pointers advanced by P rows: its RoPE table and cache
+// rows are indexed by t) -> attention_extend over the cache -> o / gate-up / down.  The linears run on the decode GEMVs (one
+// weight pass per 32 rows, folded RMSNorm) up to EXTEND_GEMV_ROWS rows, above that on the prefill GEMMs (W8A8 for the fp8
+// format).  Leaves the residual rows in `x_out` (m->x) and logits of every row in m->logits_all when all_rows, else of each
+// sequence's last row in m->logits.
+// Crossover measured on MI355X (tools/kbench.py extend_linears, one 7b layer's qkv / o / gate-up / down, bf16): ceil(M / 32)
+// GEMV passes against one GEMM per matrix = 90 / 174 / 264 / 351 / 436 us against 343 / 350 / 354 / 358 / 351 us at
+// M = 32 / 64 / 96 / 128 / 160 (profiles/extend_wall_times.md): the GEMV passes win up to 128 rows.
+constexpr int EXTEND_GEMV_ROWS = 128;
+void run_extend(vc_model* m, const int* tok_dev, int B, int n, bool all_rows) {
+    const vc_model_cfg& c = m->c;
+    const int D = c.hidden, F = c.ffn, H = c.heads, M = B * n, P = m->cur_pos, hd = m->hd;
+    const KvTarget kv = session_kv(m);
+    const bool kv8 = kv.es == 1, f8 = m->weight_format == 2;
+    const bool use_gemv = M <= EXTEND_GEMV_ROWS;
+    const int nr = (int)rup(n, 64);
+    // workspaces: the prefill's buffers, which no captured decode graph refers to
+    m->x.ensure((size_t)M * D * 4);
+    m->xn.ensure((size_t)M * (D + XN_PAD) * 2);
+    m->qkv.ensure((size_t)M * 3 * D * 2);
+    m->q.ensure((size_t)M * D * 2);
+    m->attn.ensure((size_t)M * D * 2);
+    m->h.ensure((size_t)M * F * 2);
+    m->p_ssq.ensure((size_t)M * m->npart * 4);
+    m->vt_pre.ensure((size_t)B * H * hd * nr * 2);   // V^T rows qkv_split writes for a flash kernel (unused here)
+    if (kv8) m->k_pre.ensure((size_t)B * H * nr * hd * 2);
+    if (f8 && !use_gemv) {
+        m->a8.ensure((size_t)M * std::max(D, F));
+        m->a8_scale.ensure((size_t)M * 4);
+    }
+    if (all_rows || use_gemv) m->logits_all.ensure((size_t)M * c.vocab * 4);
+    float* x = m->x.as<float>();
+    auto attention = [&](int l, const bf16_t* qkv_rows) {
+        // RoPE at P + t, K / V rows into the cache at P + t (bf16, or e4m3 with the bf16 K rows in a scratch)
+        const size_t off = (size_t)P * hd;
+        QkvSplitArgs qa{qkv_rows, m->q.as<bf16_t>(), kv8 ? m->k_pre.as<bf16_t>() : kcache(m, kv, l) + off, m->vt_pre.as<bf16_t>(),
+                        B, n, H, hd, n, kv8 ? nr : kv.capS, nullptr, m->rope_cos + off / 2, m->rope_sin + off / 2,
+                        kv8 ? nullptr : vcache(m, kv, l) + off, nr,
+                        kv8 ? reinterpret_cast<uint8_t*>(kcache(m, kv, l)) + off : nullptr,
+                        kv8 ? reinterpret_cast<uint8_t*>(vcache(m, kv, l)) + off : nullptr, kv.capS};
+        launch_qkv_split(qa, m->st);
+        AttnExtendArgs ea{m->q.as<bf16_t>(), kcache(m, kv, l), vcache(m, kv, l), m->attn.as<bf16_t>(), B, H, n, P, hd, n, kv.capS,
+                          kv8 ? 1 : 0, 1.0f / sqrtf((float)hd), nullptr, 0};
+        if (m->kmask_in_decode) {
+            ea.key_mask = m->kmask.as<uint8_t>();
+            ea.mask_stride = c.max_positions;
+        }
+        launch_attention_extend(ea, m->st);
+        if (m->attn_out) {
+            AttnProbsArgs pa{};
+            pa.q_hi = m->q.as<bf16_t>();
+            if (kv8) pa.k8 = reinterpret_cast<const uint8_t*>(kcache(m, kv, l));
+            else pa.k_hi = kcache(m, kv, l);
+            pa.q_stride = n;
+            pa.kv_stride = kv.capS;
+            emit_attentions(m, l, B, n, pa, P + n, P);
+        }
+    };
+    if (use_gemv) {
+        // the decode step's GEMVs over M rows (gemv() runs one weight pass per 32 rows)
+        LoopView v{};
+        v.st = m->st;
+        v.x_dec = x;
+        v.xg_dec = m->xn.as<bf16_t>();
+        v.qkv_dec = m->qkv.as<bf16_t>();
+        v.attn_dec = m->attn.as<bf16_t>();
+        v.h_dec = m->h.as<bf16_t>();
+        v.logits = m->logits_all.as<float>();
+        v.ssq = m->p_ssq.as<float>();
+        v.sk_scratch = m->sk_scratch.as<float>();
+        v.sk_counters = m->sk_counters.as<unsigned>();
+        launch_embed_tokens_ssq(tok_dev, m->embed, x, v.ssq, m->llm[0].in_norm, v.xg_dec, M, D, m->npart, m->st);
+        emit_hidden(m, 0, B, n, x);
+        decode_linears(m, v, M, [&](int l) { attention(l, v.qkv_dec); }, [&](int l) { emit_hidden(m, l + 1, B, n, x); });
+        return;
+    }
+    launch_embed_tokens(tok_dev, m->embed, x, M, D, m->st);
+    emit_hidden(m, 0, B, n, x);
+    for (int l = 0; l < c.layers; ++l) {
+        const LlmLayer& L = m->llm[l];
+        if (f8) {
+            launch_rmsnorm_q8(x, L.in_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
+            gemm_f8(m, nullptr, L.qkv_q, L.qkv_s, m->qkv.p, M, 3 * D, D, 3 * D, EPI_BF16);
+        } else {
+            launch_rmsnorm(x, L.in_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD);
+            gemm(m, m->xn.as<bf16_t>(), L.qkv_w, nullptr, m->qkv.p, M, 3 * D, D, 3 * D, EPI_BF16, D + XN_PAD);
+        }
+        attention(l, m->qkv.as<bf16_t>());
+        if (f8) {
+            gemm_f8(m, m->attn.as<bf16_t>(), L.o_q, L.o_s, x, M, D, D, D, EPI_RESID_F32);
+            launch_rmsnorm_q8(x, L.post_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
+            gemm_f8(m, nullptr, L.gu_q, L.gu_s, m->h.p, M, 2 * F, D, F, EPI_SWIGLU);
+            gemm_f8(m, m->h.as<bf16_t>(), L.down_q, L.down_s, x, M, D, F, D, EPI_RESID_F32);
+        } else {
+            gemm(m, m->attn.as<bf16_t>(), L.o_w, nullptr, x, M, D, D, D, EPI_RESID_F32);
+            launch_rmsnorm(x, L.post_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD);
+            gemm(m, m->xn.as<bf16_t>(), L.gu_w, nullptr, m->h.p, M, 2 * F, D, F, EPI_SWIGLU, D + XN_PAD);
+            gemm(m, m->h.as<bf16_t>(), L.down_w, nullptr, x, M, D, F, D, EPI_RESID_F32);
+        }
+        emit_hidden(m, l + 1, B, n, x);
+    }
+    if (all_rows) {
+        launch_rmsnorm(x, m->final_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st);
+        gemm(m, m->xn.as<bf16_t>(), m->lm_head, nullptr, m->logits_all.p, M, c.vocab, D, c.vocab, EPI_F32);
+    } else {   // the last row of every sequence through the lm_head GEMV, as a prefill does
+        std::vector<int> idx(B);
+        for (int b = 0; b < B; ++b) idx[b] = b * n + n - 1;
+        HIPCHK(hipMemcpyAsync(m->last_idx.p, idx.data(), B * 4, hipMemcpyHostToDevice, m->st));
+        launch_rmsnorm_rows(x, m->last_idx.as<int>(), m->final_norm, m->xl.as<bf16_t>(), B, D, c.rms_eps, m->st);
+        LoopView lv{};
+        lv.st = m->st;
+        gemv(m, lv, m->xl.as<bf16_t>(), m->lm_head_p, nullptr, m->logits.p, B, c.vocab, D, c.vocab, GEMV_F32);
+        HIPCHK(hipStreamSynchronize(m->st));   // `idx` is host memory
+    }
+}
+
 hipGraphExec_t capture_step(vc_model* m, const LoopView& v, int nrows) {
     hipGraph_t g = nullptr;
     hipGraphExec_t exec = nullptr;

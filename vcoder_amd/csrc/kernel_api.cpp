@@ -157,6 +157,14 @@ VCK_EXPORT void vck_attention(const uint16_t* q, const uint16_t* k, const uint16
     AttnArgs a{q, k, vt, out, B, H, T, hd, q_stride, kv_stride, causal, scale};
     launch_attention(a, S(stream));
 }
+/* extend attention: n queries per (b, h) at positions P .. P+n-1 over the P+n keys of a key-major decode cache (bf16, or e4m3
+ * when kv8); key_mask [B][mask_stride] bytes (0 = hidden) or NULL */
+VCK_EXPORT void vck_attention_extend(const uint16_t* q, const void* k, const void* v, uint16_t* out, int B, int H, int n, int P,
+                                     int hd, int q_stride, int kv_stride, int kv8, float scale, const uint8_t* key_mask,
+                                     int mask_stride, void* stream) {
+    AttnExtendArgs a{q, k, v, out, B, H, n, P, hd, q_stride, kv_stride, kv8, scale, key_mask, mask_stride};
+    launch_attention_extend(a, S(stream));
+}
 VCK_EXPORT void vck_splice(const int* row_src, int nrows, const uint16_t* embed, const uint16_t* feats, float* x, int D,
                            void* stream) {
     launch_splice(row_src, nrows, embed, feats, x, D, S(stream));

@@ -245,6 +245,23 @@ struct AttnArgs {
 };
 void launch_attention(const AttnArgs& a, hipStream_t s);
 
+// extend attention (a multi-token continuation of a cached sequence): n new queries of each (b, h) at positions P .. P+n-1
+// over the keys [0, P+n) of the decode cache — key-major K and V rows ([B,H,kv_stride,hd], bf16, or e4m3 when kv8), causal
+// inside the chunk, every cached key visible except those key_mask hides.  out bf16 [B*n, H*hd] (row b*n + t)
+struct AttnExtendArgs {
+    const bf16_t* q;       // [B,H,q_stride,hd], roped at P + t
+    const void* k;
+    const void* v;
+    bf16_t* out;
+    int B, H, n, P, hd;
+    int q_stride, kv_stride;
+    int kv8;               // 1: the caches hold e4m3 bytes (the fp8 weight format), widened to bf16 while staging
+    float scale;
+    const uint8_t* key_mask;   // key_mask[b * mask_stride + key] == 0 hides the key; nullptr = none
+    int mask_stride;
+};
+void launch_attention_extend(const AttnExtendArgs& a, hipStream_t s);
+
 // precision mode "split": fp32 fused-QKV rows -> RoPE (fp32) -> fp32 K / V cache rows + bf16 hi / lo planes of Q, K, V^T
 struct QkvSplit32Args {
     const float* qkv;        // [B*T, 3*H*hd] fp32

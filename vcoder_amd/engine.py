@@ -441,6 +441,37 @@ class HipEngine:
         self.last_hidden_states, self.last_attentions = hid, att
         return lg, nxt
 
+    def extend(self, tokens, all_logits: bool = True, hidden_states: bool = False, attentions: bool = False):
+        """Multi-token continuation of the current loop: tokens [B, n] at positions P .. P+n-1 (P = the position the next
+        decode_step would take), causal inside the chunk over every cached key.  -> (logits_last [B, V], logits_all [B, n, V] or
+        None).  hidden_states / attentions: [(L + 1), B, n, D] / [L, B, H, n, P + n] in last_hidden_states / last_attentions.
+        decode_step continues at P + n."""
+        B = self._cur_batch
+        tk = np.ascontiguousarray(tokens.detach().cpu().numpy() if _is_torch(tokens) else np.asarray(tokens), dtype=np.int32)
+        if tk.ndim != 2 or tk.shape[0] != B or tk.shape[1] < 1:
+            raise ValueError(f"expected tokens [{B}, n]")
+        n, V, P = int(tk.shape[1]), self.cfg.vocab_size, self._step_pos
+        self.last_hidden_states = self.last_attentions = None
+        last = np.empty((B, V), dtype=np.float32)
+        full = np.empty((B, n, V), dtype=np.float32) if all_logits else None
+        hid = att = None
+        try:
+            if hidden_states:
+                hid = np.empty((self.cfg.num_hidden_layers + 1, B, n, self.cfg.hidden_size), dtype=np.float32)
+                self._check(self.lib.vc_request_hidden_states(self._model, hid.ctypes.data_as(C.c_void_p), C.c_size_t(hid.size)))
+            if attentions:
+                att = np.empty((self.cfg.num_hidden_layers, B, self.cfg.num_attention_heads, n, P + n), dtype=np.float32)
+                self._check(self.lib.vc_request_attentions(self._model, att.ctypes.data_as(C.c_void_p), C.c_size_t(att.size)))
+            self._check(self.lib.vc_extend(self._model, tk.ctypes.data_as(C.c_void_p), B, n,
+                                           full.ctypes.data_as(C.c_void_p) if all_logits else None, last.ctypes.data_as(C.c_void_p)))
+        except BaseException:
+            self.lib.vc_request_attentions(self._model, None, C.c_size_t(0))
+            self.lib.vc_request_hidden_states(self._model, None, C.c_size_t(0))
+            raise
+        self._step_pos += n
+        self.last_hidden_states, self.last_attentions = hid, att
+        return last, full
+
     _step_pos = 0   # position of the token the next decode_step processes (prefill: S)
 
     _cur_batch = 0

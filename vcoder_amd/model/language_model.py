@@ -243,9 +243,41 @@ class _HipCausalLMBase:
             past_key_values.length += 1
             logits = torch.from_numpy(lg).unsqueeze(1)
             pkv = past_key_values
+        elif past_key_values is not None:
+            # multi-token continuation of the cache: with images=None, prepare_inputs_labels_for_multimodal returns early
+            # (vcoder_ds_llava_arch.py:129-133) and LlamaModel runs the n new ids at positions past .. past+n-1, causal inside
+            # the chunk, over every cached key.  Every check comes before the engine is touched: a refused call leaves the
+            # cache, its mask and the live handles as they were.
+            if images is not None:
+                raise NotImplementedError("continuing a cached sequence with several new ids AND images is not supported: the "
+                                          "image features would have to be spliced into the continuation")
+            if not isinstance(past_key_values, KVCacheHandle) or past_key_values.generation != self._generation:
+                raise RuntimeError("past_key_values does not belong to the engine's current KV cache")
+            tok = ids.detach().cpu().numpy() if hasattr(ids, "detach") else np.asarray(ids)
+            n = tok.shape[1]
+            if B != past_key_values.batch:
+                raise ValueError(f"input_ids has {B} rows, past_key_values {past_key_values.batch}")
+            if ((tok < 0) | (tok >= self.config.vocab_size)).any():
+                raise IndexError("index out of range in self")
+            if past_key_values.length + n > self.config.max_position_embeddings // 64 * 64:   # vc_extend's own limit
+                raise RuntimeError(f"KV cache full: position {past_key_values.length + n} exceeds max_position_embeddings="
+                                   f"{self.config.max_position_embeddings}")
+            if attention_mask is not None:
+                am = attention_mask.detach().cpu().numpy() if hasattr(attention_mask, "detach") else np.asarray(attention_mask)
+                if am.ndim != 2 or am.shape[0] != B or am.shape[1] < n:
+                    raise ValueError(f"attention_mask must be [{B}, past + {n}], got {tuple(am.shape)}")
+                # the rule of the 1-token path: the prefill's hidden keys stay hidden, the new positions are visible
+                if not bool(np.all(am[:, -n:] != 0)):
+                    raise NotImplementedError("an attention_mask that hides some of the NEW positions of a cached continuation "
+                                              "is outside the VCoder hot path")
+            else:
+                self.engine.clear_attention_mask()
+            _, full = self.engine.extend(tok, all_logits=True, hidden_states=bool(output_hidden_states),
+                                         attentions=bool(output_attentions))
+            past_key_values.length += n
+            logits = torch.from_numpy(full)
+            pkv = past_key_values
         else:
-            if past_key_values is not None:
-                raise NotImplementedError("multi-token continuation of a cached sequence is not on the reference's path")
             # images None: prepare_inputs_labels_for_multimodal returns early (vcoder_ds_llava_arch.py:129-133) and the
             # call is a plain Llama forward over the text ids
             if images is None and attention_mask is not None and not _all_ones(attention_mask):
