@@ -175,9 +175,9 @@ void vck_gemm_qkv(const void* A, const float* a_scale, const void* W, const floa
                   int lda, uint16_t* q, uint16_t* k, uint16_t* v, uint16_t* vt, uint8_t* k8, uint8_t* v8, int q_stride, int kv_stride,
                   int vt_stride, int kv8_stride, const float* rope_cos, const float* rope_sin, int f8, float* ws, size_t ws_bytes,
                   void* stream);
-/* overrides VC_GEMM_VARIANT inside one process (< 0: back to the environment's value): 1 = default (8-phase 256 x 256 for large
- * problems on v_mfma_f32_16x16x32_bf16), 6 = the same schedule on v_mfma_f32_32x32x16_bf16, 7 = that form for every size */
-void vck_set_gemm_variant(int v);
+/* test hook, inside one process: on != 0 sends the bf16 GEMMs of every size to the 8-phase 256 x 256 kernel (default 0: only
+ * M >= 1024 and N >= 512; the e4m3 and fused-QKV GEMMs always take it) */
+void vck_set_gemm_force_8phase(int on);
 /* NT = ceil(tiles / 256) tiles per workgroup for bf16 matrices of more than 512 tiles, one deep-ringed workgroup per CU (NT in
  * 3, 4, 6, 7): -1 / 1 = the classes that measured faster (default), 0 = off, 2 = every class.  Results are bit-identical
  * whichever is set. */

@@ -12,8 +12,14 @@ def be():
     return kc.EmuBackend()
 
 
-@pytest.mark.parametrize("M,N,K,epi,bias", [(128, 128, 64, 3, True), (200, 136, 128, 0, True), (70, 264, 192, 1, True),
-                                            (64, 128, 64, 2, True), (100, 128, 128, 4, False), (100, 256, 64, 5, False)])
+GEMM_CASES = [(128, 128, 64, 3, True), (200, 136, 128, 0, True), (70, 264, 192, 1, True), (64, 128, 64, 2, True),
+              (100, 128, 128, 4, False), (100, 256, 64, 5, False)]
+GEMM_F8_CASES = [(100, 144, 128, 0), (300, 272, 256, 4), (70, 528, 384, 5), (16, 16, 128, 0)]
+QKV_CASES = [(2, 96, 2, 128, False, 0, False, False), (2, 70, 2, 192, True, 0, False, False), (3, 133, 4, 128, False, 0, False, True),
+             (1, 64, 2, 256, False, 0, True, True)]
+
+
+@pytest.mark.parametrize("M,N,K,epi,bias", GEMM_CASES)
 def test_gemm(be, M, N, K, epi, bias):
     kc.check_gemm(be, M, N, K, epi, bias)
 
@@ -37,7 +43,7 @@ def test_gemv_fp8(be, M, N, K, epi, norm):
     kc.check_gemv_fp8(be, M, N, K, epi, norm)
 
 
-@pytest.mark.parametrize("M,N,K,epi", [(100, 144, 128, 0), (300, 272, 256, 4), (70, 528, 384, 5), (16, 16, 128, 0)])
+@pytest.mark.parametrize("M,N,K,epi", GEMM_F8_CASES)
 def test_gemm_f8(be, M, N, K, epi):
     kc.check_gemm_f8(be, M, N, K, epi)
 
@@ -169,8 +175,7 @@ def test_strict_fp32_kernels(be):
     kc.check_qkv_rope_f32(be, 1, 1, 2, 64, 11)
 
 
-@pytest.mark.parametrize("B,T,H,K,bias,ws,f8,kv8", [(2, 96, 2, 128, False, 0, False, False), (2, 70, 2, 192, True, 0, False, False),
-                                                     (3, 133, 4, 128, False, 0, False, True), (1, 64, 2, 256, False, 0, True, True)])
+@pytest.mark.parametrize("B,T,H,K,bias,ws,f8,kv8", QKV_CASES)
 def test_gemm_qkv_fused_epilogue(be, B, T, H, K, bias, ws, f8, kv8):
     kc.check_gemm_qkv_fused(be, B, T, H, K, bias=bias, ws_mb=ws, f8=f8, kv8=kv8)
 
@@ -181,45 +186,22 @@ def test_gemm_qkv_fused_epilogue_splitk_round(be):
     kc.check_gemm_qkv_fused(be, 2, 630, 22, 192, ws_mb=64)
 
 
-def test_alternate_kernel_variants():
-    """The non-default template variants stay correct: the same cases in subprocesses with the tuning knobs flipped (the
-    library reads them once per process); the sweeps run side by side."""
-    import os
-    import subprocess
-    import sys
-
-    plain_gemm = "test_gemm and not f8 and not splitk"
-    sweeps = [
-        # register-staged GEMM, 4 x 32 attention
-        (dict(VC_GEMM_VARIANT="0", VC_ATTN_VARIANT="1"), plain_gemm + " or test_attention"),
-        # 8 x 32 attention
-        (dict(VC_ATTN_VARIANT="2"), "test_attention"),
-        # tile-order knobs of the GEMM (8-phase kernel forced onto every small, ragged, 1-3 k-tile case; split-K rounds
-        # of the bf16 and the e4m3 form)
-        (dict(VC_GEMM_VARIANT="5"), "test_gemm"),
-        # 2: the one-barrier 256x256 kernel; 4: 256x256 as 4 waves x (128 x 128)
-        (dict(VC_GEMM_VARIANT="2"), plain_gemm),
-        (dict(VC_GEMM_VARIANT="4"), plain_gemm),
-        # 7: the 8-phase kernel on v_mfma_f32_32x32x16_bf16 for every size (round 6): ragged tiles, all epilogues, split-K rounds,
-        # and the split mode's K-wrapped / lo-plane forms
-        # (the fused-QKV check compares two launches bit for bit, and its reference GEMM would run on the other MFMA shape, whose
-        # 16-wide k-steps round differently: excluded here)
-        (dict(VC_GEMM_VARIANT="7"), "(" + plain_gemm + " or (test_gemm and splitk and not f8) or test_gemm_split or lo_plane) and not qkv_fused"),
-    ]
-    procs = []
-    for knobs, sel in sweeps:
-        env = dict(os.environ, **knobs)
-        procs.append((knobs, subprocess.Popen([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-k",
-                                               f"({sel}) and not alternate"], env=env, stdout=subprocess.PIPE,
-                                              stderr=subprocess.STDOUT, text=True)))
-    for (knobs, pr), (_, sel) in zip(procs, sweeps):
-        out, _ = pr.communicate()
-        if pr.returncode != 0:
-            # seven pytest processes side by side oversubscribe a small host; a sweep that failed there is repeated alone
-            # and must pass on its own — the kernels are deterministic, so a real defect fails both times
-            r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-k",
-                                f"({sel}) and not alternate"], env=dict(os.environ, **knobs), capture_output=True, text=True)
-            assert r.returncode == 0, f"{knobs}: first run:\n{out[-1500:]}\nrepeated alone:\n{r.stdout[-1500:]}"
+def test_alternate_kernel_variants(be):
+    """Every GEMM case above again with the bf16 8-phase kernel forced onto every size (vck_set_gemm_force_8phase): small, ragged
+    and 1-3 k-tile problems, the split-K rounds of the bf16 and the e4m3 form, the fused QKV epilogue against that GEMM."""
+    be.lib.vck_set_gemm_force_8phase(1)
+    try:
+        for case in GEMM_CASES:
+            test_gemm(be, *case)
+        test_gemm_splitk_remainder_round(be)
+        for case in GEMM_F8_CASES:
+            test_gemm_f8(be, *case)
+        test_gemm_f8_splitk_remainder_round(be)
+        for case in QKV_CASES:
+            test_gemm_qkv_fused_epilogue(be, *case)
+        test_gemm_qkv_fused_epilogue_splitk_round(be)
+    finally:
+        be.lib.vck_set_gemm_force_8phase(0)
 
 
 @pytest.mark.parametrize("M,N,K,epi,norm,G,ks", [

@@ -50,34 +50,6 @@ def bench_gemm():
         print(f"gemm+ws {name:9s}                         : {us:9.1f} us  {2 * M * N * K / us / 1e6:7.1f} TFLOP/s", flush=True)
 
 
-def bench_gemm32():
-    """Round 6 go / no-go: the 8-phase 256 x 256 schedule on v_mfma_f32_16x16x32_bf16 (variant 1) against the same schedule on
-    v_mfma_f32_32x32x16_bf16 (variant 6), random and constant operands, with the split-K workspace (the engine's form)."""
-    ws = torch.zeros(16 << 20, device=dev)
-    for (M, N, K, epi, name) in [(9728, 12288, 4096, 0, "llm qkv"), (9728, 4096, 4096, 4, "llm o"),
-                                 (9728, 22016, 4096, 5, "llm gate-up"), (9728, 4096, 11008, 4, "llm down"),
-                                 (19456, 15360, 5120, 0, "13b qkv"), (19456, 27648, 5120, 5, "13b gate-up"),
-                                 (13848, 3072, 1024, 0, "vit qkv"), (13848, 4096, 1024, 1, "vit fc1"),
-                                 (13848, 1024, 4096, 4, "vit fc2"), (13824, 4096, 4096, 0, "adapter 2")]:
-        for fill in ("random", "const"):
-            if fill == "random":
-                A, W = bf16(M, K), bf16(N, K, scale=0.02)
-            else:
-                A, W = torch.full((M, K), 0.5, device=dev, dtype=torch.bfloat16), torch.full((N, K), 0.01, device=dev, dtype=torch.bfloat16)
-            out = torch.zeros((M, N), dtype=torch.float32 if epi in (3, 4) else torch.bfloat16, device=dev)
-            ldo = N // 2 if epi == 5 else N
-            res = []
-            for v in (1, 6, 1, 6):
-                lib.vck_set_gemm_variant(v)
-                us = timeit(lambda: lib.vck_gemm_ws(P(A), P(W), None, P(out), M, N, K, K, K, ldo, epi, P(ws), C.c_size_t(64 << 20), None),
-                            iters=10)
-                res.append(us)
-            lib.vck_set_gemm_variant(-1)
-            f = lambda us: 2 * M * N * K / us / 1e6
-            print(f"gemm32 {name:12s} {fill:6s} M{M} N{N} K{K} epi{epi}: 16x16x32 {res[0]:8.1f} / {res[2]:8.1f} us ({f(min(res[0], res[2])):6.1f} TF/s)   "
-                  f"32x32x16 {res[1]:8.1f} / {res[3]:8.1f} us ({f(min(res[1], res[3])):6.1f} TF/s)   ratio {min(res[1], res[3]) / min(res[0], res[2]):.3f}", flush=True)
-
-
 def bench_gemm_qkv():
     """Round 6: the QKV projection of a prefill layer as GEMM (EPI_BF16) + qkv_split against the GEMM with RoPE + head split + KV write
     in its epilogue (vck_gemm_qkv), with / without the split-K workspace."""
@@ -612,8 +584,7 @@ def bench_attn():
         us = timeit(lambda: lib.vck_attention(P(q), P(k), P(vt), P(out), B, H, T, hd, Ts, Ts, causal,
                                               C.c_float(1 / math.sqrt(hd)), None), iters=10)
         fl = 4.0 * B * H * T * T * hd * (0.5 if causal else 1.0)
-        print(f"attention {name:12s} variant={os.environ.get('VC_ATTN_VARIANT', '0')}: {us:8.1f} us  "
-              f"{fl / us / 1e6:7.1f} TFLOP/s", flush=True)
+        print(f"attention {name:12s}: {us:8.1f} us  {fl / us / 1e6:7.1f} TFLOP/s", flush=True)
 
 
 def bench_dattn():
@@ -638,7 +609,7 @@ def bench_dattn():
 
 if __name__ == "__main__":
     what = sys.argv[1:] or ["gemm", "gemv", "attn", "dattn"]
-    table = {"gemm_qkv": bench_gemm_qkv, "gemm32": bench_gemm32, "gemm": bench_gemm, "gemv": bench_gemv, "attn": bench_attn, "dattn": bench_dattn, "gemv_fp8": bench_gemv_fp8,
+    table = {"gemm_qkv": bench_gemm_qkv, "gemm": bench_gemm, "gemv": bench_gemv, "attn": bench_attn, "dattn": bench_dattn, "gemv_fp8": bench_gemv_fp8,
              "gemv13": bench_gemv13, "gemv_pair": bench_gemv_pair, "gemv_rows": bench_gemv_rows, "dattn_rows": bench_dattn_rows,
              "gemm_f8": bench_gemm_f8, "gemv_rows8": bench_gemv_rows8, "gemv_wide": bench_gemv_wide, "gemm_chunk": bench_gemm_chunk,
              "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,

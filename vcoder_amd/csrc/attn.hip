@@ -13,7 +13,6 @@
 // O^T = V^T P^T; with S^T in the MFMA C layout each lane already owns the P values of ONE query, so
 // row max / row sum need only 2 cross-lane steps and P feeds the second MFMA from registers (the
 // contraction order over keys is permuted identically on both operands).
-#include <stdlib.h>
 
 #include <stdexcept>
 #include <type_traits>
@@ -550,18 +549,18 @@ static dim3 attention_grid(AttnArgs& a, int QB) {
     return a.sched ? dim3(a.nqb * a.H * a.B) : dim3(a.nqb, a.H, a.B);
 }
 
-template <int HD, int WAVES, int QS>
+// 8 waves x 16 queries keeps the hd-128 kernel at 128 VGPRs (two workgroups per CU)
+template <int HD>
 static void launch_attention_v(const AttnArgs& a0, hipStream_t s) {
-    const int QB = WAVES * QS * 16;
     AttnArgs a = a0;
-    const dim3 grid = attention_grid(a, QB), block(WAVES * 64);
+    const dim3 grid = attention_grid(a, 128), block(512);
 #ifdef VC_EMU
     constexpr size_t shmem = 2 * (64 * HD * 2 + HD * 128);   // the two stages the product build holds in static LDS
 #else
     constexpr size_t shmem = 0;
 #endif
-    if (a.causal) VC_LAUNCH((attention_kernel<HD, true, WAVES, QS>), grid, block, shmem, s, a);
-    else VC_LAUNCH((attention_kernel<HD, false, WAVES, QS>), grid, block, shmem, s, a);
+    if (a.causal) VC_LAUNCH((attention_kernel<HD, true, 8, 1>), grid, block, shmem, s, a);
+    else VC_LAUNCH((attention_kernel<HD, false, 8, 1>), grid, block, shmem, s, a);
 }
 
 template <int HD>
@@ -589,20 +588,8 @@ void launch_attention(const AttnArgs& a, hipStream_t s) {
         else launch_attention_split<64>(a, s);
         return;
     }
-    // 8 waves x 16 queries keeps the hd-128 kernel at 128 VGPRs (the 4x32 form needs ~250 -> 1 wave/SIMD); measured on
-    // MI355X: prefill (hd 128, T 1216, causal) 288 us vs 378 us; ViT (hd 64, T 577) 97 us vs 117 us.
-    static const int variant = getenv("VC_ATTN_VARIANT") ? atoi(getenv("VC_ATTN_VARIANT")) : 0;
-    // variant 2: 8 waves x 32 queries (256 queries per workgroup): every K / V^T fragment read from LDS feeds two MFMAs —
-    // the 8 x 16 form reads 32 KiB of fragments per wave and 64-key tile for 32 MFMAs, i.e. it is bound by LDS bandwidth
-    if (a.hd == 128) {
-        if (variant == 1) launch_attention_v<128, 4, 2>(a, s);
-        else if (variant == 2) launch_attention_v<128, 8, 2>(a, s);
-        else launch_attention_v<128, 8, 1>(a, s);
-    } else {
-        if (variant == 1) launch_attention_v<64, 4, 2>(a, s);
-        else if (variant == 2) launch_attention_v<64, 8, 2>(a, s);
-        else launch_attention_v<64, 8, 1>(a, s);
-    }
+    if (a.hd == 128) launch_attention_v<128>(a, s);
+    else launch_attention_v<64>(a, s);
 }
 
 // =============================================================================================

@@ -8,13 +8,11 @@
 //
 // Design (CDNA4): 128x128 output tile per 256-thread workgroup (4 waves, 2x2, 64x64 each = 4x4 MFMA
 // 16x16x32 fragments, 64 fp32 accumulators per lane), BK=64, two LDS stages (64 KiB -> 2 workgroups/CU),
-// XOR-swizzled LDS rows so the ds_read_b128 fragment reads are bank-conflict free.  Two staging forms:
-// LDS-DMA (global_load_lds_dwordx4, default) and register staging (global_load_dwordx4 issued before the
-// MFMAs of the current tile, ds_write_b128 after).
+// XOR-swizzled LDS rows so the ds_read_b128 fragment reads are bank-conflict free, operands staged by LDS-DMA
+// (global_load_lds_dwordx4).  Large problems take the 256x256 8-phase kernel below instead.
 // The WEIGHT tile is the MFMA A operand and the ACTIVATION tile the B operand, so each lane ends up with
 // 4 consecutive output features of one token: epilogues (bias, GELU, residual add, SwiGLU) are lane-local
 // and stores are 8/16 bytes per lane.
-#include <stdlib.h>
 
 #include "vc_device.h"
 #include <algorithm>
@@ -173,104 +171,11 @@ VC_DEV void qkv_v_store(const QkvEpiArgs& e, int head, int b, int t, int d0, u32
 // column of key kk (0..31) of a 32-key block inside the V^T scratch row (attn.hip vt_chunk_key0: chunk c holds keys 4c..4c+3, 16+4c..16+4c+3)
 VC_DEV int vt_pos32(int kk) { return ((kk & 15) >> 2) * 8 + (kk & 3) + 4 * (kk >> 4); }
 
-template <int EPI>
-__global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmArgs p) {
-    VC_DYNAMIC_SMEM(char, smem);  // [2 stages][W tile | A tile]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wn = wave >> 1, wm = wave & 1;
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
-    int tm, tn;
-    tile_coords(blockIdx.x, tiles_m * tiles_n, tiles_m, tiles_n, tm, tn);
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    // per-thread global source rows for the 4 staged chunks of each operand
-    const char* a_src[4];
-    const char* w_src[4];
-    int lds_off[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = tid + i * 256, row = c >> 3, chunk = c & 7;
-        const int am = min(m0 + row, p.M - 1), wr = min(n0 + row, p.N - 1);
-        a_src[i] = reinterpret_cast<const char*>(p.A + (size_t)am * p.lda) + chunk * 16;
-        w_src[i] = reinterpret_cast<const char*>(p.W + (size_t)wr * p.ldw) + chunk * 16;
-        lds_off[i] = swz(row, chunk);
-    }
-    u32x4 ra[4], rw[4];
-    auto load_tile = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            rw[i] = ld16(w_src[i] + w_koff(kt, p));
-            ra[i] = ld16(a_src[i] + a_koff(kt, p));
-        }
-    };
-    auto store_tile = [&](int stage) {
-        char* ws = smem + stage * (2 * TILE_BYTES);
-        char* as = ws + TILE_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            st16(ws + lds_off[i], rw[i]);
-            st16(as + lds_off[i], ra[i]);
-        }
-    };
-
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = p.K / BK;
-    load_tile(0);
-    store_tile(0);
-    __syncthreads();
-    const int frow = lane & 15, fchunk = lane >> 4;
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        if (more) load_tile(kt + 1);
-        const char* ws = smem + (kt & 1) * (2 * TILE_BYTES);
-        const char* as = ws + TILE_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            u32x4 fw[4], fa[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                fw[i] = ld16(ws + swz(wn * 64 + i * 16 + frow, ks * 4 + fchunk));
-                fa[i] = ld16(as + swz(wm * 64 + i * 16 + frow, ks * 4 + fchunk));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(fw[i], fa[j], acc[i][j]);
-        }
-        if (more) store_tile((kt + 1) & 1);
-        __syncthreads();
-    }
-
-    // ---- epilogue: lane holds out[m][n..n+3], m = .. + (lane&15), n = .. + (lane>>4)*4
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = n0 + wn * 64 + i * 16 + (lane >> 4) * 4;
-        if (n >= p.N) continue;
-        f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (p.bias) bv = ld16f(p.bias + n);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int m = m0 + wm * 64 + j * 16 + (lane & 15);
-            if (m >= p.M) continue;
-            store_out<EPI>(p, m, n, (p.row_scale ? acc[i][j] * p.row_scale[m] : acc[i][j]) + bv);
-        }
-    }
-}
-
-// ---- variant with LDS-DMA staging: same tile / swizzle / MFMA schedule, but the next k-tile is copied global->LDS
-// by global_load_lds_dwordx4 (no staging VGPRs, no ds_write_b128 — the ds_write pass was the larger half of this
-// kernel's LDS time) while the MFMAs of the current tile run; the compiler's vmcnt(0) before the tile's closing
-// barrier retires it.  One wave-instruction fills 8 swizzled rows (1 KiB): lane p writes slot p%8 of row p/8, so it
-// FETCHES chunk (p%8)^(row&7) of that row.
+// ---- LDS-DMA staging: the next k-tile is copied global->LDS by global_load_lds_dwordx4 (no staging VGPRs, no ds_write_b128)
+// while the MFMAs of the current tile run; the compiler's vmcnt(0) before the tile's closing barrier retires it.  One
+// wave-instruction fills 8 swizzled rows (1 KiB): lane p writes slot p%8 of row p/8, so it FETCHES chunk (p%8)^(row&7) of that row.
 // Geometry: WN x WM waves, each owning FI x FJ MFMA tiles (16 features x 16 tokens) -> workgroup tile
-// BNt = WN*FI*16 features x BMt = WM*FJ*16 tokens.  <2,2,4,4> = 128x128 / 4 waves / 64 KiB LDS (2 workgroups per CU);
-// <2,4,8,4> = 256x256 / 8 waves / 128 KiB LDS (1 workgroup per CU): twice the MFMAs per fragment read and a k-tile
-// compute phase (64 MFMAs per wave) long enough to cover the LDS-DMA's HBM latency with a one-tile prefetch distance.
+// BNt = WN*FI*16 features x BMt = WM*FJ*16 tokens.  <2,2,4,4> = 128x128 / 4 waves / 64 KiB LDS (2 workgroups per CU).
 template <int EPI, int WN, int WM, int FI, int FJ>
 __global__ __launch_bounds__(WN * WM * 64) void gemm_bf16_dma_kernel(GemmArgs p) {
     constexpr int BNt = WN * FI * 16, BMt = WM * FJ * 16, NW = WN * WM;
@@ -376,20 +281,9 @@ __global__ __launch_bounds__(WN * WM * 64) void gemm_bf16_dma_kernel(GemmArgs p)
 // instruction sums over all of them.  The epilogue multiplies the fp32 accumulator by a_scale[m] * w_scale[n] (exact: powers of two).
 // KWRAP (precision mode "split"): the weight's k-tile index wraps after p.kwrap tiles (compile-time flag: the default
 // instantiation keeps the weight source a plain `base + kt * 128`, exactly the round-2 loop)
-// M32 (round 6): the same schedule on v_mfma_f32_32x32x16_bf16.  A wave's 128 x 64 output is 4 x 2 accumulators of 32 x 32 instead
-// of 8 x 4 of 16 x 16; a quadrant (64 n x 32 m x BK) is 8 MFMAs of 32 cycles instead of 16 of 16, fed by the same number of
-// ds_read_b128 (a fragment = 32 rows x 16 k: lane l reads row l % 32, chunk 2 s + l / 32 of k-step s).  Half the MFMA issues per
-// flop, an exact 32-cycle back-to-back cadence (the 16 x 16 x 32 form issues at ~17 instead of 16), and half the operand-register
-// reads per flop.  The tile rows are swizzled by (row >> 1) & 7 instead of row & 7: the 16 lanes of a ds_read_b128 group then
-// cover rows {0-3, 12-15, 20-27} (or {4-11, 16-19, 28-31}) of ONE chunk column — 8 row pairs with distinct (row >> 1) & 7, two
-// parities each = 16 distinct 16-byte bank slots.  C/D: lane l holds token l % 32 and, per register group rg = reg / 4, the 4
-// consecutive features 8 rg + 4 (l / 32) + reg % 4 (cdna_hip_programming.md section 3) — the lane-local epilogues are unchanged.
-template <bool M32> VC_DEV int swz8(int r, int c) { return r * 128 + ((c ^ ((M32 ? r >> 1 : r) & 7)) << 4); }
-
-template <int EPI, bool F8 = false, bool KWRAP = false, bool M32 = false>
+template <int EPI, bool F8 = false, bool KWRAP = false>
 __global__ __launch_bounds__(512) void gemm_bf16_8phase_kernel(GemmArgs p) {
-    static_assert(!(F8 && M32), "the 32 x 32 form is instantiated for bf16 operands");
-    static_assert(!(EPI == EPI_QKV && (M32 || KWRAP)), "the fused QKV epilogue is built on the 16 x 16 accumulator layout of the bf16 / e4m3 forms");
+    static_assert(!(EPI == EPI_QKV && KWRAP), "the fused QKV epilogue has no K-wrapped form");
     constexpr int HALF = 128 * 128, TILE = 4 * HALF;  // bytes
     constexpr int ES = F8 ? 1 : 2;                    // bytes per operand element; a k-tile is 128 bytes of every row
     constexpr int SY0 = 0, SX0 = HALF, SY1 = 2 * HALF, SX1 = 3 * HALF;
@@ -420,7 +314,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_8phase_kernel(GemmArgs p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int row = (i * 8 + wave) * 8 + (lane >> 3);
-            const int sw = ((lane & 7) ^ ((M32 ? row >> 1 : row) & 7)) << 4;
+            const int sw = ((lane & 7) ^ (row & 7)) << 4;
             const int wrow = EPI == EPI_QKV ? qkv_wrow(n0, h, row) : n0 + h * 128 + row;
             int arow = min(m0 + h * 128 + row, p.M - 1);
             if constexpr (EPI == EPI_QKV) arow = qkv_arow(p.qe, arow);
@@ -445,7 +339,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_8phase_kernel(GemmArgs p) {
         glds16(y_src[h][1] + ak, dst + 8192);
     };
     f32x4 acc[2][4][2][2];  // [x half][i][y half][j]
-    f32x16 acc32[2][2][2];  // M32: [x half][32-row fragment][y half]
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -453,54 +346,27 @@ __global__ __launch_bounds__(512) void gemm_bf16_8phase_kernel(GemmArgs p) {
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if constexpr (M32) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc32[a][i >> 1][b][(i & 1) * 8 + j * 4 + e] = 0.f;
-                    } else {
-                        acc[a][i][b][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    }
-                }
-    const int frow = M32 ? lane & 31 : lane & 15, fchunk = M32 ? lane >> 5 : lane >> 4;
+                for (int j = 0; j < 2; ++j) acc[a][i][b][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int frow = lane & 15, fchunk = lane >> 4;
     // X0 is dead after phase 1 and X1 is first read in phase 2: one register set serves both halves
-    u32x4 fx[4][2], fy[2][2][2];  // [fragment][ks], [half][fragment][ks]; M32: fx[2 fi + s / 2][s & 1], fy[half][s / 2][s & 1]
+    u32x4 fx[4][2], fy[2][2][2];  // [fragment][ks], [half][fragment][ks]
     auto read_x = [&](const char* base, int h) {
-        if constexpr (M32) {
 #pragma unroll
-            for (int fi = 0; fi < 2; ++fi)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int s_ = 0; s_ < 4; ++s_)
-                    fx[2 * fi + (s_ >> 1)][s_ & 1] = ld16(base + (h ? SX1 : SX0) + swz8<true>(g * 64 + fi * 32 + frow, 2 * s_ + fchunk));
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-                    fx[i][ks] = ld16(base + (h ? SX1 : SX0) + swz(g * 64 + i * 16 + frow, ks * 4 + fchunk));
-        }
+            for (int ks = 0; ks < 2; ++ks)
+                fx[i][ks] = ld16(base + (h ? SX1 : SX0) + swz(g * 64 + i * 16 + frow, ks * 4 + fchunk));
     };
     auto read_y = [&](const char* base, int h) {
-        if constexpr (M32) {
 #pragma unroll
-            for (int s_ = 0; s_ < 4; ++s_)
-                fy[h][s_ >> 1][s_ & 1] = ld16(base + (h ? SY1 : SY0) + swz8<true>(q * 32 + frow, 2 * s_ + fchunk));
-        } else {
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-                    fy[h][j][ks] = ld16(base + (h ? SY1 : SY0) + swz(q * 32 + j * 16 + frow, ks * 4 + fchunk));
-        }
+            for (int ks = 0; ks < 2; ++ks)
+                fy[h][j][ks] = ld16(base + (h ? SY1 : SY0) + swz(q * 32 + j * 16 + frow, ks * 4 + fchunk));
     };
     auto quadrant = [&](int hx, int hy) {
         set_prio<1>();
-        if constexpr (M32) {
-#pragma unroll
-            for (int s_ = 0; s_ < 4; ++s_)
-#pragma unroll
-                for (int fi = 0; fi < 2; ++fi)
-                    acc32[hx][fi][hy] = mfma32(fx[2 * fi + (s_ >> 1)][s_ & 1], fy[hy][s_ >> 1][s_ & 1], acc32[hx][fi][hy]);
-        } else if constexpr (F8) {
+        if constexpr (F8) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -565,36 +431,6 @@ __global__ __launch_bounds__(512) void gemm_bf16_8phase_kernel(GemmArgs p) {
     }
     if (g == 0) wg_barrier_raw();
 
-    if constexpr (M32) {
-        // lane holds out[m][n .. n + 3] with m = .. + lane % 32 and n = .. + fi * 32 + rg * 8 + (lane / 32) * 4
-        float* wsb = KS > 1 ? p.ws + ((size_t)(pid - p.sk_full) * KS + ks) * 65536 : nullptr;
-        float rs32[2] = {1.f, 1.f};
-        if (p.row_scale && KS == 1) {
-#pragma unroll
-            for (int hy = 0; hy < 2; ++hy) rs32[hy] = p.row_scale[min(m0 + hy * 128 + q * 32 + (lane & 31), p.M - 1)];
-        }
-#pragma unroll
-        for (int hx = 0; hx < 2; ++hx)
-#pragma unroll
-            for (int fi = 0; fi < 2; ++fi)
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) {
-                    const int nl = hx * 128 + g * 64 + fi * 32 + rg * 8 + (lane >> 5) * 4;
-                    f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (KS == 1 && p.bias && n0 + nl < p.N) bv = ld16f(p.bias + n0 + nl);
-#pragma unroll
-                    for (int hy = 0; hy < 2; ++hy) {
-                        const int ml = hy * 128 + q * 32 + (lane & 31);
-                        const f32x4 v = f32x4{acc32[hx][fi][hy][rg * 4], acc32[hx][fi][hy][rg * 4 + 1], acc32[hx][fi][hy][rg * 4 + 2],
-                                              acc32[hx][fi][hy][rg * 4 + 3]};
-                        if (KS > 1) st16f(wsb + ml * 256 + nl, v);
-                        else if constexpr (EPI != EPI_QKV) {
-                            if (n0 + nl < p.N && m0 + ml < p.M) store_out<EPI>(p, m0 + ml, n0 + nl, v * rs32[hy] + bv);
-                        }
-                    }
-                }
-        return;
-    }
     if (KS > 1) {  // partial tile -> workspace [remainder tile][slice][256 m][256 n]; the fix-up launch finishes it
         float* base = p.ws + ((size_t)(pid - p.sk_full) * KS + ks) * 65536;
 #pragma unroll
@@ -886,69 +722,46 @@ void launch_rstd_from_partials(const float* ssq, int npart, int nparts, float* r
     VC_LAUNCH(rstd_from_partials_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ssq, npart, nparts, rstd, rows, D, eps);
 }
 
-template <class K>
-static void allow_big_lds_gemm(K kernel, size_t bytes) {
-#ifndef VC_EMU
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-#endif
-}
-
-// e4m3 x e4m3 (GemmArgs::f8): always the 8-phase kernel, any size (rows are clamped, stores masked)
-static void launch_gemm_f8(const GemmArgs& a, int epilogue, hipStream_t s) {
-    const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-    const size_t sh2 = 2 * (256 * 128 + 256 * 128);
-    static const int sk_on = getenv("VC_GEMM_SPLITK") ? atoi(getenv("VC_GEMM_SPLITK")) : 1;
-    constexpr int tile_group = 4, xcd_on = 1;   // as in launch_gemm below
+// The 8-phase kernel over 256 x 256 tiles, and the fix-up of its split-K remainder round.  Tile order: 4 m-tiles per sweep group
+// (measured: 4 and 2 beat 8 / 16 / 38 by 2-6 %) and the XCD remap on (+-3 %).  Split-K for a short last round: the rem <= 128
+// tiles left over after the full rounds of 256 are cut into ks = 256 / rem K-slices each (at most 8, at most one per k-tile of
+// 128 bytes, within the workspace), so the round is ~1/ks as long; a.ws == nullptr (vc_model_set_batch_invariant) keeps it whole.
+template <int EPI, bool F8, bool KWRAP = false>
+static void launch_gemm_8phase(const GemmArgs& a, hipStream_t s) {
+    constexpr size_t lds = 2 * (256 * 128 + 256 * 128);
+    const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256), rem = t256 % 256;
     GemmArgs ask = a;
-    ask.tile_group = tile_group;
-    ask.xcd_remap_on = xcd_on;
+    ask.tile_group = 4;
+    ask.xcd_remap_on = 1;
     ask.sk_full = (int)t256;
     ask.sk_ks = 1;
-    const long rem = t256 % 256;
-    if (sk_on && a.ws && t256 > 256 && rem > 0 && rem <= 128) {
+    if (a.ws && t256 > 256 && rem > 0 && rem <= 128) {
         int ks = (int)std::min<long>(256 / rem, 8);
-        ks = std::min(ks, a.K / 128);
+        ks = std::min(ks, a.K / (F8 ? 128 : BK));
         while (ks > 1 && (size_t)rem * ks * 65536 * 4 > a.ws_bytes) --ks;
         if (ks > 1) {
             ask.sk_full = (int)(t256 - rem);
             ask.sk_ks = ks;
         }
     }
-    const dim3 gsk((unsigned)(ask.sk_ks > 1 ? ask.sk_full + rem * ask.sk_ks : t256)), b2(512);
-#define VC_G8(E)                                                                                       \
-    do {                                                                                               \
-        static bool once = false;                                                                      \
-        if (!once) {                                                                                   \
-            allow_big_lds_gemm(gemm_bf16_8phase_kernel<E, true>, sh2);                                 \
-            once = true;                                                                               \
-        }                                                                                              \
-        VC_LAUNCH((gemm_bf16_8phase_kernel<E, true>), gsk, b2, sh2, s, ask);                           \
-        if (ask.sk_ks > 1)                                                                             \
-            VC_LAUNCH((gemm_splitk_fixup_kernel<E>), dim3((unsigned)(rem * 64)), dim3(256), 0, s, ask); \
-    } while (0)
-    if (epilogue == EPI_QKV) {
-        static bool once = false;
-        if (!once) {
-            allow_big_lds_gemm(gemm_bf16_8phase_kernel<EPI_QKV, true>, sh2);
-            once = true;
-        }
-        VC_LAUNCH((gemm_bf16_8phase_kernel<EPI_QKV, true>), gsk, b2, sh2, s, ask);
-        if (ask.sk_ks > 1) VC_LAUNCH(gemm_splitk_fixup_qkv_kernel, dim3((unsigned)(rem * 32)), dim3(256), 0, s, ask);
-        return;
-    }
-    switch (epilogue) {
-        case EPI_BF16: VC_G8(EPI_BF16); break;
-        case EPI_RESID_F32: VC_G8(EPI_RESID_F32); break;
-        case EPI_SWIGLU: VC_G8(EPI_SWIGLU); break;
-        default: throw std::runtime_error("fp8 GEMM: epilogue not instantiated");
-    }
-#undef VC_G8
+#ifndef VC_EMU
+    static const hipError_t lds_set = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_8phase_kernel<EPI, F8, KWRAP>),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // once per kernel
+    (void)lds_set;
+#endif
+    const dim3 grid((unsigned)(ask.sk_ks > 1 ? ask.sk_full + rem * ask.sk_ks : t256));
+    VC_LAUNCH((gemm_bf16_8phase_kernel<EPI, F8, KWRAP>), grid, dim3(512), lds, s, ask);
+    if (ask.sk_ks == 1) return;
+    if constexpr (EPI == EPI_QKV) VC_LAUNCH(gemm_splitk_fixup_qkv_kernel, dim3((unsigned)(rem * 32)), dim3(256), 0, s, ask);
+    else VC_LAUNCH((gemm_splitk_fixup_kernel<EPI>), dim3((unsigned)(rem * 64)), dim3(256), 0, s, ask);
 }
 
-// test / benchmark hook (vck_set_gemm_variant): overrides VC_GEMM_VARIANT inside one process; < 0 = the environment's
-static int g_gemm_variant = -1;
-void set_gemm_variant(int v) { g_gemm_variant = v; }
+// test hook (vck_set_gemm_force_8phase): the bf16 8-phase kernel for every size inside one process
+static bool g_force_8phase = false;
+void set_gemm_force_8phase(bool on) { g_force_8phase = on; }
 
+// The e4m3 form (GemmArgs::f8) and the fused QKV epilogue always take the 8-phase kernel (any size: rows are clamped, stores
+// masked); the other bf16 GEMMs take it from M >= 1024 and N >= 512 on, the 128 x 128 LDS-DMA kernel below that.
 void launch_gemm(const GemmArgs& a, int epilogue, hipStream_t s) {
     if (a.xg_out && (epilogue != EPI_RESID_F32 || a.N % 16 != 0 || !a.xg_w || !a.ssq_out || a.npart < a.N / 16))
         throw std::runtime_error("gemm: the folded-RMSNorm producer needs EPI_RESID_F32, N % 16 == 0, xg_w, ssq_out, npart >= N / 16");
@@ -958,136 +771,37 @@ void launch_gemm(const GemmArgs& a, int epilogue, hipStream_t s) {
             a.M != e.B * e.Tp || !e.q || !e.k || !e.vt || !e.rope_cos || !e.rope_sin || (!e.v && !e.v8))
             throw std::runtime_error("gemm: EPI_QKV needs hd 128, D % 256 == 0, N = 3 D, M = B * Tp with Tp = rup(T, 32), q / k / v / vt and the RoPE tables");
     }
-    if (a.f8) return launch_gemm_f8(a, epilogue, s);
-    if (epilogue == EPI_QKV) {   // always the 8-phase 256 x 256 kernel on the 16 x 16 x 32 MFMA (any size: rows are clamped, stores masked)
-        const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-        const size_t sh2 = 2 * (256 * 128 + 256 * 128);
-        static const int sk_on = getenv("VC_GEMM_SPLITK") ? atoi(getenv("VC_GEMM_SPLITK")) : 1;
-        GemmArgs ask = a;
-        ask.tile_group = 4;
-        ask.xcd_remap_on = 1;
-        ask.sk_full = (int)t256;
-        ask.sk_ks = 1;
-        const long rem = t256 % 256;
-        if (sk_on && a.ws && t256 > 256 && rem > 0 && rem <= 128) {
-            int ks = (int)std::min<long>(256 / rem, 8);
-            ks = std::min(ks, a.K / BK);
-            while (ks > 1 && (size_t)rem * ks * 65536 * 4 > a.ws_bytes) --ks;
-            if (ks > 1) {
-                ask.sk_full = (int)(t256 - rem);
-                ask.sk_ks = ks;
-            }
-        }
-        static bool once = false;
-        if (!once) {
-            allow_big_lds_gemm(gemm_bf16_8phase_kernel<EPI_QKV>, sh2);
-            once = true;
-        }
-        VC_LAUNCH((gemm_bf16_8phase_kernel<EPI_QKV>), dim3((unsigned)(ask.sk_ks > 1 ? ask.sk_full + rem * ask.sk_ks : t256)), dim3(512), sh2, s, ask);
-        if (ask.sk_ks > 1) VC_LAUNCH(gemm_splitk_fixup_qkv_kernel, dim3((unsigned)(rem * 32)), dim3(256), 0, s, ask);
-        return;
-    }
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    const dim3 grid(tiles), block(256);
-    const size_t shmem = 4 * TILE_BYTES;
-    // default (1): 256x256 counted-vmcnt 8-phase kernel for large problems, 128x128 LDS-DMA kernel for small ones.
-    // Tuning / regression knobs (VC_GEMM_VARIANT): 0 register-staged 128x128 (8-16 % slower than the DMA form of the
-    // same geometry); 2 force the one-barrier 256x256 DMA kernel (947-1087 TFLOP/s where the 8-phase schedule reaches
-    // 1068-1281); 3 force DMA 128x128; 4 force 256x256 as 4 waves x (128x128) (1 wave per SIMD: 20-25 % slower than 2
-    // with this simple loop); 5 force the 8-phase kernel for every size
-    static const int env_variant = getenv("VC_GEMM_VARIANT") ? atoi(getenv("VC_GEMM_VARIANT")) : 1;
-    int variant = g_gemm_variant >= 0 ? g_gemm_variant : env_variant;
-    // 6 / 7: the 8-phase kernel on the 32 x 32 x 16 MFMA for large problems / for every size (the folded-RMSNorm producer's row
-    // sums assume the 16 x 16 accumulator layout: it keeps the 16 x 16 form)
-    const bool m32 = (variant == 6 || variant == 7) && !a.xg_out;
-    if (variant == 6) variant = 1;
-    if (variant == 7) variant = 5;
-    if (variant >= 1) {
-        const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-        const bool big = variant == 2 || variant == 4 || variant == 5 || (variant == 1 && a.M >= 1024 && a.N >= 512);
-        if (big) {
-            const size_t sh2 = 2 * (256 * 128 + 256 * 128);
-            const bool wide = variant == 4;  // 4 waves x (128 x 128): fewer LDS fragment reads per MFMA, 1 wave per SIMD
-            const bool phased = variant == 5 || variant == 1;  // counted-vmcnt 8-phase schedule
-            const dim3 g2((unsigned)t256), b2(wide ? 256 : 512);
-            // split-K for a short last round of the 8-phase kernel (VC_GEMM_SPLITK=0 disables): rem tiles left over
-            // after the full rounds of 256 are cut into ks = 256 / rem K-slices each, so the round is ~1/ks as long
-            static const int sk_on = getenv("VC_GEMM_SPLITK") ? atoi(getenv("VC_GEMM_SPLITK")) : 1;
-            // m-tiles per sweep group (measured: 4 and 2 beat 8 / 16 / 38 by 2-6 %) and the XCD remap of the tile order (on: +-3 %)
-            constexpr int tile_group = 4, xcd_on = 1;
-            GemmArgs ask = a;
-            ask.tile_group = tile_group;
-            ask.xcd_remap_on = xcd_on;
-            ask.sk_full = (int)t256;
-            ask.sk_ks = 1;
-            long rem = t256 % 256;
-            if (phased && sk_on && a.ws && t256 > 256 && rem > 0 && rem <= 128) {
-                int ks = (int)std::min<long>(256 / rem, 8);
-                ks = std::min(ks, a.K / BK);
-                while (ks > 1 && (size_t)rem * ks * 65536 * 4 > a.ws_bytes) --ks;
-                if (ks > 1) {
-                    ask.sk_full = (int)(t256 - rem);
-                    ask.sk_ks = ks;
-                }
-            }
-            const dim3 gsk((unsigned)(ask.sk_ks > 1 ? ask.sk_full + rem * ask.sk_ks : t256));
-#define VC_G256(E)                                                                                         \
-    do {                                                                                                   \
-        static bool once = false;                                                                          \
-        if (!once) {                                                                                       \
-            allow_big_lds_gemm(gemm_bf16_dma_kernel<E, 2, 4, 8, 4>, sh2);                                  \
-            allow_big_lds_gemm(gemm_bf16_dma_kernel<E, 2, 2, 8, 8>, sh2);                                  \
-            allow_big_lds_gemm(gemm_bf16_8phase_kernel<E>, sh2);                                           \
-            allow_big_lds_gemm(gemm_bf16_8phase_kernel<E, false, true>, sh2);                              \
-            allow_big_lds_gemm(gemm_bf16_8phase_kernel<E, false, false, true>, sh2);                       \
-            allow_big_lds_gemm(gemm_bf16_8phase_kernel<E, false, true, true>, sh2);                        \
-            once = true;                                                                                   \
-        }                                                                                                  \
-        if (phased && m32) {                                                                               \
-            if (ask.kwrap > 0) VC_LAUNCH((gemm_bf16_8phase_kernel<E, false, true, true>), gsk, b2, sh2, s, ask);   \
-            else VC_LAUNCH((gemm_bf16_8phase_kernel<E, false, false, true>), gsk, b2, sh2, s, ask);        \
-            if (ask.sk_ks > 1)                                                                             \
-                VC_LAUNCH((gemm_splitk_fixup_kernel<E>), dim3((unsigned)(rem * 64)), dim3(256), 0, s, ask); \
-        } else if (phased && ask.kwrap > 0) {                                                              \
-            VC_LAUNCH((gemm_bf16_8phase_kernel<E, false, true>), gsk, b2, sh2, s, ask);                    \
-            if (ask.sk_ks > 1)                                                                             \
-                VC_LAUNCH((gemm_splitk_fixup_kernel<E>), dim3((unsigned)(rem * 64)), dim3(256), 0, s, ask); \
-        } else if (phased) {                                                                               \
-            VC_LAUNCH((gemm_bf16_8phase_kernel<E>), gsk, b2, sh2, s, ask);                                 \
-            if (ask.sk_ks > 1)                                                                             \
-                VC_LAUNCH((gemm_splitk_fixup_kernel<E>), dim3((unsigned)(rem * 64)), dim3(256), 0, s, ask); \
-        }                                                                                                  \
-        else if (wide) VC_LAUNCH((gemm_bf16_dma_kernel<E, 2, 2, 8, 8>), g2, b2, sh2, s, a);                \
-        else VC_LAUNCH((gemm_bf16_dma_kernel<E, 2, 4, 8, 4>), g2, b2, sh2, s, a);                          \
-    } while (0)
-            switch (epilogue) {
-                case EPI_BF16: VC_G256(EPI_BF16); break;
-                case EPI_BF16_QGELU: VC_G256(EPI_BF16_QGELU); break;
-                case EPI_BF16_GELU: VC_G256(EPI_BF16_GELU); break;
-                case EPI_F32: VC_G256(EPI_F32); break;
-                case EPI_RESID_F32: VC_G256(EPI_RESID_F32); break;
-                default: VC_G256(EPI_SWIGLU); break;
-            }
-#undef VC_G256
-            return;
-        }
+    if (a.f8) {
         switch (epilogue) {
-            case EPI_BF16: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_BF16, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
-            case EPI_BF16_QGELU: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_BF16_QGELU, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
-            case EPI_BF16_GELU: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_BF16_GELU, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
-            case EPI_F32: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_F32, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
-            case EPI_RESID_F32: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_RESID_F32, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
-            default: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_SWIGLU, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
+            case EPI_QKV: return launch_gemm_8phase<EPI_QKV, true>(a, s);
+            case EPI_BF16: return launch_gemm_8phase<EPI_BF16, true>(a, s);
+            case EPI_RESID_F32: return launch_gemm_8phase<EPI_RESID_F32, true>(a, s);
+            case EPI_SWIGLU: return launch_gemm_8phase<EPI_SWIGLU, true>(a, s);
+            default: throw std::runtime_error("fp8 GEMM: epilogue not instantiated");
         }
-        return;
     }
+    if (epilogue == EPI_QKV) return launch_gemm_8phase<EPI_QKV, false>(a, s);
+    if (g_force_8phase || (a.M >= 1024 && a.N >= 512)) {
+#define VC_G8(E) return a.kwrap > 0 ? launch_gemm_8phase<E, false, true>(a, s) : launch_gemm_8phase<E, false>(a, s)
+        switch (epilogue) {
+            case EPI_BF16: VC_G8(EPI_BF16);
+            case EPI_BF16_QGELU: VC_G8(EPI_BF16_QGELU);
+            case EPI_BF16_GELU: VC_G8(EPI_BF16_GELU);
+            case EPI_F32: VC_G8(EPI_F32);
+            case EPI_RESID_F32: VC_G8(EPI_RESID_F32);
+            default: VC_G8(EPI_SWIGLU);
+        }
+#undef VC_G8
+    }
+    const dim3 grid(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN)), block(256);
+    const size_t shmem = 4 * TILE_BYTES;
     switch (epilogue) {
-        case EPI_BF16: VC_LAUNCH((gemm_bf16_kernel<EPI_BF16>), grid, block, shmem, s, a); break;
-        case EPI_BF16_QGELU: VC_LAUNCH((gemm_bf16_kernel<EPI_BF16_QGELU>), grid, block, shmem, s, a); break;
-        case EPI_BF16_GELU: VC_LAUNCH((gemm_bf16_kernel<EPI_BF16_GELU>), grid, block, shmem, s, a); break;
-        case EPI_F32: VC_LAUNCH((gemm_bf16_kernel<EPI_F32>), grid, block, shmem, s, a); break;
-        case EPI_RESID_F32: VC_LAUNCH((gemm_bf16_kernel<EPI_RESID_F32>), grid, block, shmem, s, a); break;
-        default: VC_LAUNCH((gemm_bf16_kernel<EPI_SWIGLU>), grid, block, shmem, s, a); break;
+        case EPI_BF16: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_BF16, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
+        case EPI_BF16_QGELU: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_BF16_QGELU, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
+        case EPI_BF16_GELU: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_BF16_GELU, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
+        case EPI_F32: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_F32, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
+        case EPI_RESID_F32: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_RESID_F32, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
+        default: VC_LAUNCH((gemm_bf16_dma_kernel<EPI_SWIGLU, 2, 2, 4, 4>), grid, block, shmem, s, a); break;
     }
 }
 

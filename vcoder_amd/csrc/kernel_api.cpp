@@ -284,7 +284,7 @@ VCK_EXPORT void vck_gemv_full(const uint16_t* X, const void* Wp, const float* ws
 }
 /* split-mode GEMV: 0 = per-wave rings, 1 / -1 = workgroup-shared activation chunks (default) */
 VCK_EXPORT void vck_set_gemv_variant(int v) { set_gemv_variant(v); }
-VCK_EXPORT void vck_set_gemm_variant(int v) { set_gemm_variant(v); }
+VCK_EXPORT void vck_set_gemm_force_8phase(int on) { set_gemm_force_8phase(on != 0); }
 VCK_EXPORT void vck_set_gemv_wide(int v) { set_gemv_wide(v); }
 VCK_EXPORT unsigned long long vck_gemv_wide_launches() { return gemv_wide_launches(); }
 VCK_EXPORT unsigned long long vck_gemv_wg_launches() { return gemv_wg_launches(); }

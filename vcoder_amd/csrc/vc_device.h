@@ -40,7 +40,6 @@ inline void check_launch(const char* what) {
 namespace vc {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef uint16_t bf16_t;  // raw bf16 bit pattern
@@ -232,15 +231,6 @@ VC_DEV f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
                                                    __builtin_bit_cast(bf16x8_hw, b), c, 0, 0, 0);
 }
 #endif
-// v_mfma_f32_32x32x16_bf16: A[i][k]: lane i + 32 (k / 8), elem k % 8 (i < 32, k < 16); B[k][j]: lane j + 32 (k / 8), elem k % 8;
-// D[i][j]: lane j + 32 ((i / 4) % 2), reg i % 4 + 4 (i / 8)  (cdna_hip_programming.md section 3)
-VC_DEV f32x16 mfma32(u32x4 a, u32x4 b, f32x16 c) {
-#ifdef VC_F16
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(bf16x8_hw, a), __builtin_bit_cast(bf16x8_hw, b), c, 0, 0, 0);
-#else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_hw, a), __builtin_bit_cast(bf16x8_hw, b), c, 0, 0, 0);
-#endif
-}
 // v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain): A[i][k]: lane i+16k; B[k][j]: lane j+16k; D as for bf16
 VC_DEV f32x4 mfma16_f32(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 // v_mfma_scale_f32_16x16x128_f8f6f4 with both operands OCP e4m3 and every block scale 2^0 (E8M0 127): the K = 128 fp8
