@@ -5,8 +5,13 @@ One "step" = one full pass of the hot path over one batch per GPU:
     3x CLIP ViT-L/14@336 encode (RGB, seg, depth) + adapters + splice + Llama prefill (S=1216)
     + 128 greedy tokens (1 from the prefill + 127 hipGraph-replayed decode steps), EOS disabled.
 Synthetic COST-shaped inputs, seeded synthetic weights (no network), bf16 MFMA compute, fp32 accumulate.
-`value`: inputs resident in HBM when the timed region starts (the task contract); the PCIe-inclusive rate (pixels
-handed over as host buffers) is measured in the same run and reported as `pcie_inclusive`.
+`value`: inputs resident in HBM when the timed region starts (the task contract).
+
+A plain run does what `value` needs and no more: it builds the model, generates the batch once alone (the ids every timed step
+must reproduce), warms up, times `--steps` steps, checks their ids, writes `--dump-outputs` / `--dump-ids`, and prints the line.
+`--full` appends, outside the timed region and without changing it, everything else the benchmark measures: the PCIe-inclusive
+rate (pixels handed over as host buffers) as `pcie_inclusive`, inter-token latency, one batch at a time, the
+composite and per-kernel rooflines, the precision-mode / fp16-library / 13b legs, and the CPU baseline (minutes in all).
 
 N > 1: one process per GPU, batch sharded data-parallel with no collective on the data path; the only exchange is
 one all-gather of the generated token ids per step over RCCL/xGMI.  `python bench.py --gpus N` starts its own N
@@ -47,9 +52,14 @@ def parse_args():
     ap.add_argument("--inflight", type=int, default=4,
                     help="batches in flight per GPU: independent generate() calls (own stream + prefill workspaces, shared "
                          "weights) driven by host threads.  1 = strictly one batch at a time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and report everything beside the headline: the other residency of the "
+                         "inputs, inter-token latency, one batch at a time, the composite and per-kernel rooflines (isolated replays), "
+                         "the compact legs (see --no-extra-legs) and the CPU baseline.  `value`, `ms_per_step` and the dumped outputs "
+                         "are those of the plain run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: do not time the CPU baseline")
     ap.add_argument("--cpu-c1", action="store_true",
-                    help="additionally run BASELINE configs[0] IN FULL on the host cores (VCoder 7b shape, B=1, RGB+seg, 32 "
+                    help="with --full: additionally run BASELINE configs[0] IN FULL on the host cores (VCoder 7b shape, B=1, RGB+seg, 32 "
                          "greedy tokens through oracle/cpu_ref.py; minutes) and report it as cpu_c1")
     ap.add_argument("--host-pixels", action="store_true",
                     help="make the PCIe-inclusive form the timed one (pixels handed over as pageable host fp32 buffers)")
@@ -72,18 +82,20 @@ def parse_args():
     ap.add_argument("--gemv-variant", type=int, default=None,
                     help="A/B: vck_set_gemv_variant — 2 = four waves per workgroup in the split step's GEMV everywhere (rounds 4-5), default = the launcher's choice")
     ap.add_argument("--no-insitu", action="store_true",
-                    help="do not stamp the pool's decode-step launches (roofline then reports the isolated replay); A/B of the stamps' cost")
+                    help="do not stamp the pool's decode-step launches (the roofline of --full then reports the isolated replay); A/B of the stamps' cost")
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the compact legs the default single-GPU run appends outside the timed region: parity_mode "
+                    help="with --full: skip the compact legs a single-GPU run appends outside the timed region: parity_mode "
                          "(images/s of the precision modes that meet the 1e-3 / bit-exact-ids bar), BASELINE configs[2] "
                          "(13b bf16, batch 16) and the per-GPU slice of configs[4] (13b fp8, batch 16)")
-    ap.add_argument("--extra-steps", type=int, default=2, help="steps of each compact leg")
+    ap.add_argument("--extra-steps", type=int, default=2, help="with --full: steps of each compact leg")
     ap.add_argument("--pmc-traffic-bytes", type=float, default=None,
-                    help="HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc pass "
+                    help="with --full: HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc pass "
                          "(default: the committed FETCH_SIZE pass of this kernel under profiles/)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full and (args.cpu_c1 or args.pmc_traffic_bytes is not None):
+        ap.error("--cpu-c1 and --pmc-traffic-bytes belong to the legs that only --full runs")
     return args
 
 
@@ -299,7 +311,7 @@ def run_leg(eng, cfg, ids, px, n_new, steps, inflight, check_against=None, preci
 
 
 def extra_legs(args, eng7, cfg7, ids7, dev_px7, lone_ids7, fast_value, n_new):
-    """The compact legs of the default single-GPU run (outside the timed region): parity_mode on the benchmark model, then —
+    """The compact legs of a single-GPU --full run (outside the timed region): parity_mode on the benchmark model, then —
     the 7b engine released — BASELINE configs[2] and the per-GPU slice of configs[4] on a 13b model."""
     import numpy as np
     import torch
@@ -486,7 +498,8 @@ def main():
 
     n_sess = max(1, min(args.inflight, args.steps))
     # in-situ timing of the pool's decode-step kernels (vc_pool_profile): every launch of the timed region stamps its earliest
-    # workgroup start / latest workgroup end with the device's wall clock; `roofline` is computed from those sums
+    # workgroup start / latest workgroup end with the device's wall clock; the `roofline` of --full is computed from those sums.
+    # A plain run leaves the stamps on as well and does not read them: the timed steps are the same launches with and without --full
     pooled_run = os.environ.get("VC_POOL", "1") != "0"
     insitu_on = not args.no_insitu and pooled_run
     if insitu_on:
@@ -557,8 +570,8 @@ def main():
         eng.pool_profile_read(reset=True)      # drop the warm-up's launches
     dt, outs = timed(args.steps, timed_px)
     step_mix = [a - b for a, b in zip(eng.pool_step_counts(), steps0)]   # pooled decode steps of the timed region by 8/16/24/32 rows
-    insitu = eng.pool_profile_read(reset=True) if insitu_on else None    # every decode-step launch of the timed region, as it ran
-    if insitu_on:
+    insitu = eng.pool_profile_read(reset=True) if insitu_on and args.full else None   # every decode-step launch of the timed region, as it ran
+    if insitu is not None:
         # the side legs below run without the stamps (their fold launch costs a lone batch ~1 %: 34 us of a 3.4-ms step); the pool is
         # re-captured without them by the next call, outside any timed region
         eng.pool_profile(False)
@@ -572,7 +585,53 @@ def main():
         assert last.max() < 2 ** 24   # token ids are exact in float32
         os.makedirs(args.dump_outputs, exist_ok=True)
         np.save(os.path.join(args.dump_outputs, "new_token_ids.npy"), last.astype(np.float32))
-    # ---- transparency legs, outside the timed region -----------------------------------------------------------------
+    pooled = pooled_run and sum(step_mix) > 0
+    S_prompt = 64 + 2 * cfg.num_patches
+    res = None
+    if rank == 0:   # the headline: all of a plain run's line, and the head of a --full one
+        res = {
+            "metric": "images/sec (3xViT encode + 128-tok decode), VCoder-DS-7b" if args.model == "7b"
+                      else "images/sec (3xViT encode + 128-tok decode), VCoder-DS-13b",
+            "value": world * B * args.steps / dt, "unit": "images/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "bf16" if args.weights != "fp8" else "fp8-e4m3 prefill linears / bf16", "data": "synthetic",
+            "config": {"workload": f"VCoder-DS LLaVA-1.5-{args.model} {WEIGHTS_DESC[args.weights]}, batch={B}/GPU RGB+seg+depth 336x336, "
+                                   f"prefill S={S_prompt}, {N_new}-token greedy decode", "global_batch": world * B,
+                       "parallelism": f"dp{world}", "weights": "seeded synthetic (vcoder_amd/synth.py)",
+                       "in_flight_batches_per_gpu": n_sess,
+                       "value_is": (f"{n_sess} generate() calls of batch {B} in flight per GPU, each a complete, independent hot-path "
+                                    f"pass; their cached decode steps " + ("share weight passes in the decode pool" if pooled else "run on private loops (VC_POOL=0)")
+                                    + "; --full adds one_batch_at_a_time for a lone batch") if n_sess > 1 else "one batch at a time",
+                       "decode_pool": pooled,
+                       "inputs": "host buffers (PCIe inclusive)" if args.host_pixels else "resident in HBM",
+                       "token_gather": ("vc_allgather_tokens (RCCL via the C ABI%s)" % ("" if comm.uses_rccl else "; world 1: host copy")) if comm is not None else
+                                       ("torch.distributed all_gather_into_tensor (%s)" % backend if dist is not None else "none (1 GPU)"),
+                       "force_dist": bool(args.force_dist),
+                       "in_situ_timing_stamps": bool(insitu_on), "qkv_epilogue_fused": not args.no_qkv_fused},
+            "ids_checked": bool(ids_checked),
+            "ids_check": {"what": "ids of EVERY step of the timed region == ids of the same batch generated alone, bit for bit",
+                          "steps_checked": args.steps, "mismatching_timed_steps": bad_steps},
+        }
+
+    def teardown():
+        if comm is not None:
+            comm.close()
+        if dist is not None:
+            fence()
+            dist.destroy_process_group()
+
+    def fail_if_ids_differ():
+        if not ids_checked:
+            raise SystemExit("bench.py: the ids of the timed region differ from the ids of the same batch generated alone "
+                             "(steps %s) - the measurement is void" % bad_steps)
+
+    if not args.full:
+        teardown()
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        fail_if_ids_differ()
+        return
+    # ---- transparency legs of --full, outside the timed region --------------------------------------------------------
     # (a) the other residency of the inputs (PCIe-inclusive when `value` is resident, and vice versa)
     k_side = max(n_sess, min(args.steps, 2 * n_sess))
     other_px = dev_px if args.host_pixels else host_px
@@ -627,8 +686,6 @@ def main():
     # The two HBM-bound kernels of a decode step, measured live (HIP events on the engine's stream, real arguments, all
     # layers) at every row count the timed region ran its steps at: the pool steps over 8 / 16 / 24 / 32 rows as requests
     # join and leave (step_mix), a private loop over the batch's own rows.
-    pooled = os.environ.get("VC_POOL", "1") != "0" and sum(step_mix) > 0
-    S_prompt = 64 + 2 * cfg.num_patches
     if pooled:
         mix = {8 * (i + 1): n for i, n in enumerate(step_mix) if n > 0}
     else:
@@ -761,30 +818,12 @@ def main():
                     "measured": how, "rows_per_launch": {str(r_): n for r_, n in sorted(mix.items())}}
         if "isolated_replay" in k:
             roofline["isolated_replay"] = {"frac": k["isolated_replay"]["frac"], "avg_launch_us": k["isolated_replay"]["avg_launch_us"]}
-        res = {
-            "metric": "images/sec (3xViT encode + 128-tok decode), VCoder-DS-7b" if args.model == "7b"
-                      else "images/sec (3xViT encode + 128-tok decode), VCoder-DS-13b",
-            "value": world * B * args.steps / dt, "unit": "images/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16" if args.weights != "fp8" else "fp8-e4m3 prefill linears / bf16", "data": "synthetic",
-            "config": {"workload": f"VCoder-DS LLaVA-1.5-{args.model} {WEIGHTS_DESC[args.weights]}, batch={B}/GPU RGB+seg+depth 336x336, "
-                                   f"prefill S={S}, {N_new}-token greedy decode", "global_batch": world * B,
-                       "parallelism": f"dp{world}", "weights": "seeded synthetic (vcoder_amd/synth.py)",
-                       "in_flight_batches_per_gpu": n_sess,
-                       "value_is": (f"{n_sess} generate() calls of batch {B} in flight per GPU, each a complete, independent hot-path "
-                                    f"pass; their cached decode steps " + ("share weight passes in the decode pool" if pooled else "run on private loops (VC_POOL=0)")
-                                    + "; see one_batch_at_a_time for a lone batch") if n_sess > 1 else "one batch at a time",
-                       "decode_pool": pooled,
-                       "inputs": "host buffers (PCIe inclusive)" if args.host_pixels else "resident in HBM",
-                       "token_gather": ("vc_allgather_tokens (RCCL via the C ABI%s)" % ("" if comm.uses_rccl else "; world 1: host copy")) if comm is not None else
-                                       ("torch.distributed all_gather_into_tensor (%s)" % backend if dist is not None else "none (1 GPU)"),
-                       "force_dist": bool(args.force_dist),
-                       # the whole story in the one object a reader of the parsed line keeps: what `value` is NOT
-                       "c2_as_written_images_per_s": B / solo,
-                       "in_situ_timing_stamps": bool(insitu_on), "qkv_epilogue_fused": not args.no_qkv_fused},
-            "ids_checked": bool(ids_checked),
-            "ids_check": {"what": "ids of EVERY step of the timed region (and of the side legs) == ids of the same batch generated "
-                                  "alone, bit for bit", "steps_checked": args.steps + k_side + 2, "mismatching_timed_steps": bad_steps},
+        # the whole story in the one object a reader of the parsed line keeps: what `value` is NOT
+        res["config"]["c2_as_written_images_per_s"] = B / solo
+        res["ids_checked"] = bool(ids_checked)
+        res["ids_check"].update({"what": "ids of EVERY step of the timed region (and of the side legs) == ids of the same batch generated "
+                                         "alone, bit for bit", "steps_checked": args.steps + k_side + 2})
+        res.update({
             "inter_token_latency_ms": lat,
             "phase_ms_one_session": timings,  # encode / prefill / decode wall time of one batch run alone
             "one_batch_at_a_time": {"value": B / solo, "unit": "images/s per GPU", "ms_per_step": solo * 1e3,
@@ -802,7 +841,7 @@ def main():
                                    "measured_legs_ms": {"mfma": timings["encode_ms"] + timings["prefill_ms"], "hbm": timings["decode_ms"]}},
             "roofline": roofline,
             "decode_step_kernels": kernels,
-        }
+        })
         if args.cpu_c1 and world == 1:
             res["cpu_c1"] = cpu_c1_full()
         if world == 1 and not args.no_extra_legs and args.model == "7b" and args.weights == "bf16" and not args.force_dist:
@@ -812,11 +851,7 @@ def main():
             pm_ = res.get("parity_mode", {})
             res["config"]["parity_mode_split_images_per_s"] = pm_.get("split", {}).get("value")   # the mode that meets the 1e-3 / bit-exact bar
             res["config"]["fp16_operand_library_images_per_s"] = pm_.get("fp16", {}).get("value")
-    if comm is not None:
-        comm.close()
-    if dist is not None:
-        fence()
-        dist.destroy_process_group()
+    teardown()
     if rank == 0:
         # The CPU baseline is TIMED at N = 1 only (the contract: rank 0, N = 1) and cached on the box; a world > 1 line carries that
         # cached N = 1 measurement when the box has one (the driver runs N = 1, 2, 4, 8 back to back) and says so otherwise — it
@@ -845,9 +880,7 @@ def main():
                           "note": "the CPU baseline is timed at N = 1 only; this box holds no cached N = 1 run of bench.py"}
             res["cpu_baseline"] = cb
         print(json.dumps(res), flush=True)
-    if not ids_checked:
-        raise SystemExit("bench.py: the ids of the timed region differ from the ids of the same batch generated alone "
-                         "(steps %s) - the measurement is void" % bad_steps)
+    fail_if_ids_differ()
 
 
 if __name__ == "__main__":

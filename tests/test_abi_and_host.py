@@ -193,3 +193,19 @@ def test_bench_refuses_to_run_without_a_gpu():
                        text=True)
     assert r.returncode != 0 and "no CPU fallback" in (r.stderr + r.stdout)
     assert not any(line.startswith("{") for line in r.stdout.splitlines()), "no result line may be printed"
+
+
+def test_bench_full_option(monkeypatch):
+    """--full is off by default; the options that only make sense for the legs it appends are refused without it."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--cpu-c1"])
+    a = bench.parse_args()
+    assert a.full is True and a.cpu_c1 is True
+    for extra in (["--cpu-c1"], ["--pmc-traffic-bytes", "1e8"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + extra)
+        with pytest.raises(SystemExit):
+            bench.parse_args()

@@ -835,7 +835,8 @@ def test_bench_two_ranks_self_launched(tmp_path):
     """`python bench.py --gpus 2` with WORLD_SIZE unset starts its own two ranks (torch.distributed.run on 127.0.0.1), shards
     the global batch contiguously, and the gathered token stream equals the single-process one.  On this 1-GPU box both
     ranks share device 0 and the id gather runs over gloo (VC_BENCH_FORCE_DEVICE / VC_BENCH_BACKEND: RCCL refuses two ranks
-    on one GPU); on a multi-GPU node the same command uses one GPU per rank and RCCL."""
+    on one GPU); on a multi-GPU node the same command uses one GPU per rank and RCCL.  Run with --full: the line carries the
+    rooflines, the other residency of the inputs and the CPU baseline entry beside the headline."""
     import json
     import os
     import subprocess
@@ -847,7 +848,7 @@ def test_bench_two_ranks_self_launched(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(VC_BENCH_FORCE_DEVICE="0", VC_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "0", "--batch",
-                        "2", "--new-tokens", "6", "--inflight", "2", "--dump-ids", dump, "--dump-outputs", outputs], env=env,
+                        "2", "--new-tokens", "6", "--inflight", "2", "--full", "--dump-ids", dump, "--dump-outputs", outputs], env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -909,6 +910,42 @@ def test_batch_invariant_mode_true_dims():
     eng.set_precision("bf16")
     print("default mode: a batch of 4 and a batch of 2 differ in the low-order bits of the prefill logits:", differs_by_default)
     eng.close()
+
+
+def test_bench_plain_run_reports_the_headline_only(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the line is the headline (value, ms_per_step, what was run, the id
+    check of the timed steps) and carries none of the legs that --full appends; --dump-outputs still writes the last timed step."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outputs = str(tmp_path / "outputs")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--new-tokens", "6", "--inflight", "2", "--dump-outputs", outputs], env=env, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert set(res) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                        "vs_baseline", "dtype", "data", "config", "ids_checked", "ids_check"}
+    assert res["unit"] == "images/s" and res["higher_is_better"] is True and res["dtype"] == "bf16"
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ids_checked"] is True and res["ids_check"]["steps_checked"] == 3
+    assert res["ms_per_step"] > 0 and res["value"] == pytest.approx(2 * 1e3 / res["ms_per_step"])
+    out = np.load(os.path.join(outputs, "new_token_ids.npy"))
+    assert os.listdir(outputs) == ["new_token_ids.npy"] and out.dtype == np.float32 and out.shape == (2, 6)
+    cfg = vcfg.vicuna_7b("vcoder_ds")
+    eng = HipEngine(cfg)
+    eng.load_synthetic(42)
+    eng.finalize()
+    ids = np.stack([synth.synth_prompt_ids(cfg.vocab_size, "vcoder_ds", sample=b) for b in range(2)])
+    imgs, segs, deps = synth.synth_batch(2, 336)
+    ref = eng.generate_greedy(ids, imgs, segs, deps, max_new_tokens=6)
+    eng.close()
+    assert np.array_equal(out, ref)
 
 
 @pytest.mark.parametrize("gather", ["torch", "cabi"])
