@@ -57,6 +57,9 @@ void vck_interleave_rows(const uint16_t* gate, const uint16_t* up, uint16_t* out
 /* nn.LayerNorm ([HF] clip :370,379) and LlamaRMSNorm ([HF] llama :53-70); fp32 in, bf16 out */
 void vck_layernorm(const float* x, const float* w, const float* b, uint16_t* y, int rows, int D, float eps, void* stream);
 void vck_rmsnorm(const float* x, const int* row_idx, const float* w, uint16_t* y, int rows, int D, float eps, void* stream);
+/* the same with a row stride: row r at y + r * ldy (elements; columns [D, ldy) are not written).  A prefill writes the bf16
+ * operand rows of its QKV and gate / up GEMMs this way (ldy = D + 64 = their lda) */
+void vck_rmsnorm_ld(const float* x, const float* w, uint16_t* y, int rows, int D, float eps, int ldy, void* stream);
 /* CLIPVisionEmbeddings ([HF] clip :202-218): im2col of the k=s=14 conv; CLS + position + pre_layrnorm */
 void vck_im2col(const float* pixels, uint16_t* cols, int n_img, int image, int patch, int Kpad, void* stream);
 void vck_vit_embed_ln(const float* patches, const float* cls, const float* pos, const float* w, const float* b, float* x,
@@ -178,6 +181,10 @@ void vck_gemm_qkv(const void* A, const float* a_scale, const void* W, const floa
 /* test hook, inside one process: on != 0 sends the bf16 GEMMs of every size to the 8-phase 256 x 256 kernel (default 0: only
  * M >= 1024 and N >= 512; the e4m3 and fused-QKV GEMMs always take it) */
 void vck_set_gemm_force_8phase(int on);
+/* launches the GEMM launcher has sent to the 128 x 128 LDS-DMA kernel / to the 8-phase 256 x 256 kernel (the e4m3 and fused-QKV
+ * forms included; a split-K fix-up launch is not counted) since the library was loaded (tests) */
+unsigned long long vck_gemm_dma_launches(void);
+unsigned long long vck_gemm_8phase_launches(void);
 /* NT = ceil(tiles / 256) tiles per workgroup for bf16 matrices of more than 512 tiles, one deep-ringed workgroup per CU (NT in
  * 3, 4, 6, 7): -1 / 1 = the classes that measured faster (default), 0 = off, 2 = every class.  Results are bit-identical
  * whichever is set. */

@@ -90,6 +90,9 @@ class EmuBackend:
     def i32(self, a):
         return self._guard(np.ascontiguousarray(a, dtype=np.int32))
 
+    def bits16(self, a):   # raw uint16 bit patterns of the operand format, any shape (the strided operands: pads, tight ends)
+        return self._guard(np.ascontiguousarray(a, dtype=np.uint16))
+
     def zeros(self, shape, kind):
         return self._guard(np.zeros(shape, dtype={"f32": np.float32, "bf16": np.uint16, "i32": np.int32, "u8": np.uint8}[kind]))
 
@@ -124,6 +127,9 @@ class HipBackend:
 
     def i32(self, a):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.dev)
+
+    def bits16(self, a):   # raw uint16 bit patterns of the operand format, any shape
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint16).view(np.int16)).to(self.dev)
 
     def zeros(self, shape, kind):
         dt = {"f32": torch.float32, "bf16": torch.int16, "i32": torch.int32, "u8": torch.uint8}[kind]
@@ -165,9 +171,54 @@ def rel_err(got, ref):
     return float(np.abs(got - ref).max() / (np.abs(ref).max() + 1e-12))
 
 
+def raw_bits(t):
+    """a backend array as the host bytes it holds (bf16 / fp16 as 16-bit patterns, fp32 as 32-bit patterns): for bit-for-bit comparisons"""
+    a = np.ascontiguousarray(t.cpu().numpy() if hasattr(t, "cpu") else np.array(t))
+    return a.view({1: np.uint8, 2: np.uint16, 4: np.uint32}[a.dtype.itemsize])
+
+
+def _addr(a):
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+def nan_bits(be):
+    """a quiet NaN of the library's 16-bit operand format"""
+    return 0x7E00 if be.operands == "fp16" else 0x7FC0
+
+
+def padded_operand(be, X, pad, tight=None):
+    """the [R, C] values X as an operand of row stride C + pad whose pad columns hold NaN: a pad column that reaches the contraction
+    poisons the output.  tight (default: on the emulator): the array ends behind the last row's valid columns — (R - 1) * ld + C
+    elements, the guard page right behind them — so reading the last row's pad faults."""
+    R, C = X.shape
+    if tight is None:
+        tight = be.name == "emu"
+    full = np.full((R, C + pad), nan_bits(be), np.uint16)
+    full[:, :C] = _op_bits(X, be.operands)
+    return be.bits16(full.reshape(-1)[: (R - 1) * (C + pad) + C] if tight else full)
+
+
+def gemm_launch_counts(be):
+    """(launches served by the 128 x 128 LDS-DMA kernel, by the 8-phase 256 x 256 kernel) so far"""
+    be.lib.vck_gemm_dma_launches.restype = be.lib.vck_gemm_8phase_launches.restype = ctypes.c_ulonglong
+    return int(be.lib.vck_gemm_dma_launches()), int(be.lib.vck_gemm_8phase_launches())
+
+
+def assert_gemm_path(be, before, path, n, what=""):
+    """the n GEMM launches since `before` (gemm_launch_counts) all took kernel `path` ("dma" = 128 x 128 LDS-DMA, "8phase"); None: no claim"""
+    if path is None:
+        return
+    d = tuple(a - b for a, b in zip(gemm_launch_counts(be), before))
+    assert d == ((n, 0) if path == "dma" else (0, n)), f"{what}: expected {n} launches of the {path} kernel, counted (dma, 8phase) = {d}"
+
+
 # ------------------------------------------------------------------------------------------------
-def check_gemm(be, M, N, K, epi, bias=True, seed=0, ws_mb=0):
-    """ws_mb > 0: through vck_gemm_ws with an fp32 workspace of that many MiB (enables the split-K remainder round)."""
+def check_gemm(be, M, N, K, epi, bias=True, seed=0, ws_mb=0, lda_pad=0, ldw_pad=0, path=None):
+    """ws_mb > 0: through vck_gemm_ws with an fp32 workspace of that many MiB (enables the split-K remainder round).
+    lda_pad / ldw_pad > 0: a second launch reads the same values through row strides K + pad with NaN in the pad columns (the
+    form of every RMSNorm -> GEMM pair of a prefill: lda = D + 64); it must meet the same tolerance and equal the lda = K launch
+    bit for bit — same kernel, tiles, K-slices and k order, only the addresses differ.
+    path: "dma" / "8phase" — the kernel every launch of this case must have taken (launch counters of the library)."""
     rng = np.random.RandomState(seed)
     A = bf16_round(rng.randn(M, K))
     W = bf16_round(rng.randn(N, K) * 0.05)
@@ -190,19 +241,37 @@ def check_gemm(be, M, N, K, epi, bias=True, seed=0, ws_mb=0):
         out = be.zeros((M, N // 2), "bf16")
         t = torch.nn.functional.silu(t[:, 0::2]) * t[:, 1::2]
     ldo = N // 2 if epi == 5 else N
-    if ws_mb:
-        Ad, Wd, bd = be.bf16(A), be.bf16(W), (be.f32(b) if bias else None)
-        ws = be.zeros((ws_mb << 18,), "f32")
-        be.lib.vck_gemm_ws(be.ptr(Ad), be.ptr(Wd), be.ptr(bd), be.ptr(out), M, N, K, K, K, ldo, epi, be.ptr(ws),
-                           ctypes.c_size_t(ws_mb << 20), None)
-        be.sync()
-    else:
-        _call(be, "vck_gemm", be.bf16(A), be.bf16(W), be.f32(b) if bias else None, out, M, N, K, K, K, ldo, epi)
+    before = gemm_launch_counts(be)
+    bd = be.f32(b) if bias else None
+    ws = be.zeros((ws_mb << 18,), "f32") if ws_mb else None
+
+    def launch(Ad, Wd, lda, ldw, o):
+        if ws_mb:
+            be.lib.vck_gemm_ws(be.ptr(Ad), be.ptr(Wd), be.ptr(bd), be.ptr(o), M, N, K, lda, ldw, ldo, epi, be.ptr(ws),
+                               ctypes.c_size_t(ws_mb << 20), None)
+            be.sync()
+        else:
+            _call(be, "vck_gemm", Ad, Wd, bd, o, M, N, K, lda, ldw, ldo, epi)
+
+    launch(be.bf16(A), be.bf16(W), K, K, out)
     got = be.host_f32(out)
     ref = t.numpy()
     tol = 2 ** -8 if epi in (0, 1, 2, 5) else 1e-5  # bf16 output rounding vs fp32 accumulate
     e = rel_err(got, ref)
+    print(f"gemm M{M} N{N} K{K} epi{epi}: rel err {e:.3e}")
     assert e < tol, f"gemm M{M} N{N} K{K} epi{epi}: rel err {e}"
+    if lda_pad or ldw_pad:
+        out2 = be.f32(r0.copy()) if epi == 4 else be.zeros(tuple(out.shape), "f32" if epi == 3 else "bf16")
+        Ad = padded_operand(be, A, lda_pad) if lda_pad else be.bf16(A)
+        Wd = padded_operand(be, W, ldw_pad) if ldw_pad else be.bf16(W)
+        launch(Ad, Wd, K + lda_pad, K + ldw_pad, out2)
+        e2 = rel_err(be.host_f32(out2), ref)
+        print(f"gemm M{M} N{N} K{K} epi{epi} lda {K + lda_pad} ldw {K + ldw_pad}: rel err {e2:.3e}")
+        assert e2 < tol, f"gemm M{M} N{N} K{K} epi{epi} lda {K + lda_pad} ldw {K + ldw_pad}: rel err {e2}"
+        g1, g2 = raw_bits(out), raw_bits(out2)
+        assert np.array_equal(g1, g2), f"gemm M{M} N{N} K{K} epi{epi}: the lda {K + lda_pad} / ldw {K + ldw_pad} launch differs from " \
+                                       f"the lda = ldw = K launch in {int((g1 != g2).sum())} of {g1.size} elements"
+    assert_gemm_path(be, before, path, 2 if (lda_pad or ldw_pad) else 1, f"gemm M{M} N{N} K{K} epi{epi}")
     return e
 
 
@@ -294,10 +363,11 @@ def check_gemv_fp8(be, M, N, K, epi, norm=False, seed=0):
     return e
 
 
-def check_gemm_f8(be, M, N, K, epi, seed=0, ws_mb=0):
-    """W8A8 prefill GEMM: the device's activation quantiser equals vcoder_amd/quant.py row for row (bytes + scales), the
-    row-major weight bytes equal quant.quantize_rows, and the e4m3 x e4m3 MFMA GEMM equals A_eff @ W_eff^T (exact
-    products, fp32 accumulation) through the epilogue."""
+def check_gemm_f8(be, M, N, K, epi, seed=0, ws_mb=0, path=None):
+    """W8A8 prefill GEMM: the device's activation quantiser equals vcoder_amd/quant.py row for row (bytes + scales) — from rows
+    of stride K and from rows of stride K + 64 with NaN in the pad —, the row-major weight bytes equal quant.quantize_rows, and
+    the e4m3 x e4m3 MFMA GEMM equals A_eff @ W_eff^T (exact products, fp32 accumulation) through the epilogue.
+    path: the kernel the GEMM launch must have taken (assert_gemm_path)."""
     from vcoder_amd import quant
 
     rng = np.random.RandomState(seed)
@@ -306,6 +376,7 @@ def check_gemm_f8(be, M, N, K, epi, seed=0, ws_mb=0):
     A[rng.randint(M), rng.randint(K)] = 300.0     # a massive activation: the rest of the row loses bits
     A = bf16_round(A)
     W = bf16_round(rng.randn(N, K) * 0.05 * np.exp2(rng.randint(-3, 3, size=(N, 1))))
+    A, W = (_op_decode(_op_bits(X, be.operands), be.operands) for X in (A, W))   # (fp16 operand library: the values it can hold)
     qa, sa, a_eff = quant.quantize_rows(A)
     qw, sw, w_eff = quant.quantize_rows(W)
     Ad, Q, sad = be.bf16(A), be.zeros((M, K), "u8"), be.zeros((M,), "f32")
@@ -315,6 +386,10 @@ def check_gemm_f8(be, M, N, K, epi, seed=0, ws_mb=0):
     host = lambda t: np.asarray(t.cpu().numpy() if hasattr(t, "cpu") else t)
     assert np.array_equal(host(Q), qa), "activation bytes differ from quant.quantize_rows"
     assert np.array_equal(be.host_f32(sad), sa), "activation row scales differ"
+    Ap, Qp, sap = padded_operand(be, A, 64), be.zeros((M, K), "u8"), be.zeros((M,), "f32")
+    _call(be, "vck_quant_act_rows", Ap, K + 64, Qp, sap, M, K)
+    assert np.array_equal(host(Qp), qa), "activation bytes from rows of stride K + 64 differ from quant.quantize_rows"
+    assert np.array_equal(be.host_f32(sap), sa), "activation row scales from rows of stride K + 64 differ"
     assert np.array_equal(host(Wrow), qw), "row-major weight bytes differ from quant.quantize_rows"
     assert np.array_equal(host(Wq), quant.pack_supertiles(qw))
     t = torch.from_numpy(a_eff.astype(np.float64) @ w_eff.T.astype(np.float64)).float()
@@ -328,9 +403,11 @@ def check_gemm_f8(be, M, N, K, epi, seed=0, ws_mb=0):
         out = be.zeros((M, N // 2), "bf16")
         t = torch.nn.functional.silu(t[:, 0::2]) * t[:, 1::2]
     ws = be.zeros((max(ws_mb, 1) << 18,), "f32")
+    before = gemm_launch_counts(be)
     be.lib.vck_gemm_f8(be.ptr(Q), be.ptr(sad), be.ptr(Wrow), be.ptr(swd), be.ptr(out), M, N, K, N // 2 if epi == 5 else N, epi,
                        be.ptr(ws) if ws_mb else None, ctypes.c_size_t(ws_mb << 20), None)
     be.sync()
+    assert_gemm_path(be, before, path, 1, f"gemm_f8 M{M} N{N} K{K} epi{epi}")
     e = rel_err(be.host_f32(out), t.numpy())
     # fp32 outputs: the emulator's MFMA sums the 128 exact products of a step in fp32; the hardware's scaled MFMA aligns them
     # to the largest and keeps ~13 bits below it (tools/experiments/f8_precision.py: 2e-5 of the row maximum on random
@@ -389,7 +466,10 @@ def check_layernorm(be, rows, D, seed=0):
     assert e < 2 ** -8, f"layernorm rel err {e}"
 
 
-def check_rmsnorm(be, rows, D, gather=False, seed=0):
+def check_rmsnorm(be, rows, D, gather=False, seed=0, chain_n=128):
+    """... and (not gathered) the row-stride form a prefill uses, vck_rmsnorm_ld with ldy = D + 64: the valid columns carry the bits
+    of the ldy = D launch, the pad columns keep what they held; then the pair as the engine chains it, rmsnorm_ld -> gemm(lda =
+    D + 64, chain_n output columns), against rmsnorm -> gemm(lda = D): bit for bit (the pad holds NaN)."""
     rng = np.random.RandomState(seed)
     x = (rng.randn(rows * (3 if gather else 1), D) * 3).astype(np.float32)
     w = (rng.rand(D) + 0.5).astype(np.float32)
@@ -400,6 +480,19 @@ def check_rmsnorm(be, rows, D, gather=False, seed=0):
     ref = cpu_ref.rms_norm(torch.from_numpy(src), torch.from_numpy(w), 1e-5).numpy()
     e = rel_err(be.host_f32(y), ref)
     assert e < 2 ** -8, f"rmsnorm rel err {e}"
+    if gather:
+        return
+    ld = D + 64
+    y2 = be.bits16(np.full((rows, ld), nan_bits(be), np.uint16))
+    _call(be, "vck_rmsnorm_ld", be.f32(x), be.f32(w), y2, rows, D, 1e-5, ld)
+    g1, g2 = raw_bits(y), raw_bits(y2)
+    assert np.array_equal(g2[:, :D], g1), "rmsnorm: the ldy = D + 64 rows differ from the ldy = D rows"
+    assert (g2[:, D:] == nan_bits(be)).all(), "rmsnorm: ldy = D + 64 wrote into the pad columns"
+    W = be.bf16(bf16_round(rng.randn(chain_n, D) * 0.05))
+    o1, o2 = be.zeros((rows, chain_n), "bf16"), be.zeros((rows, chain_n), "bf16")
+    _call(be, "vck_gemm", y, W, None, o1, rows, chain_n, D, D, D, chain_n, 0)
+    _call(be, "vck_gemm", y2, W, None, o2, rows, chain_n, D, ld, D, chain_n, 0)
+    assert raw_bits(o1).any() and np.array_equal(raw_bits(o1), raw_bits(o2)), "rmsnorm_ld -> gemm(lda = D + 64) != rmsnorm -> gemm(lda = D)"
 
 
 def check_quant_act_rows_exhaustive(be):
@@ -554,11 +647,62 @@ def check_qkv_split(be, B, T, H, hd, rope):
     assert np.array_equal(be.host_f32(vt2), gv)
 
 
-def check_gemm_qkv_fused(be, B, T, H, K, bias=False, ws_mb=0, f8=False, kv8=False, seed=0):
+def check_qkv_split_at_offset(be, B, n, H, hd, P, kv8):
+    """vck_qkv_split_kv / _kv8 as a multi-token continuation calls them: n new rows per sequence behind P cached ones.  The cache
+    pointers and the RoPE tables are advanced by P rows, q_stride = n (not a multiple of 64), kv_stride = the cache's S keys, the
+    V^T scratch (and, with e4m3 caches, the bf16 K scratch) has stride rup(n, 64).  Q and the K rows P .. P+n-1 against the
+    oracle at pos0 = P, V rows and the e4m3 bytes bit for bit, and every cache row outside [P, P + n) keeps its bits."""
+    rng = np.random.RandomState(11)
+    D = H * hd
+    S, nr = (P + n + 63) // 64 * 64 + 64, (n + 63) // 64 * 64
+    qkv = _op_decode(_op_bits(bf16_round(rng.randn(B * n, 3 * D)), be.operands), be.operands)   # exact in the operand format
+    cos, sin = rope_tables(S, hd)
+    qd, cd, sd = be.bf16(qkv), be.f32(cos), be.f32(sin)
+    q, vt = be.zeros((B, H, n, hd), "bf16"), be.zeros((B, H, hd, nr), "bf16")
+    adv = lambda a, nbytes: c_p(_addr(a) + nbytes)
+    rope_off = P * (hd // 2) * 4
+    rq, rk, rv = _split_ref(qkv, B, n, H, hd, True, pos0=P)
+    keep = np.ones(S, bool)
+    keep[P:P + n] = False
+    if kv8:
+        k8_0, v8_0 = rng.randint(0, 256, size=(B, H, S, hd)).astype(np.uint8), rng.randint(0, 256, size=(B, H, S, hd)).astype(np.uint8)
+        k8, v8, ks = _u8_dev(be, k8_0), _u8_dev(be, v8_0), be.zeros((B, H, nr, hd), "bf16")
+        be.lib.vck_qkv_split_kv8(be.ptr(qd), be.ptr(q), be.ptr(ks), adv(k8, P * hd), adv(v8, P * hd), be.ptr(vt), B, n, H, hd, n, nr, nr, S,
+                                 adv(cd, rope_off), adv(sd, rope_off), None)
+        be.sync()
+        gk = be.host_f32(ks)
+        g8k, g8v = _u8_host(be, k8), _u8_host(be, v8)
+        assert not raw_bits(ks)[:, :, n:].any(), "the bf16 K scratch was written behind its n rows"
+        assert np.array_equal(g8k[:, :, P:P + n], e4m3_bytes(gk[:, :, :n])), "K cache bytes != e4m3(bf16 K rows)"
+        assert np.array_equal(g8v[:, :, P:P + n], e4m3_bytes(rv)), "V cache bytes != e4m3(V rows)"
+        assert np.array_equal(g8k[:, :, keep], k8_0[:, :, keep]) and np.array_equal(g8v[:, :, keep], v8_0[:, :, keep]), \
+            "a cache row outside [P, P + n) changed"
+        gk = gk[:, :, :n]
+    else:
+        k0, v0 = _op_bits(bf16_round(rng.randn(B, H, S, hd)), be.operands), _op_bits(bf16_round(rng.randn(B, H, S, hd)), be.operands)
+        k, v = be.bits16(k0), be.bits16(v0)
+        be.lib.vck_qkv_split_kv(be.ptr(qd), be.ptr(q), adv(k, P * hd * 2), adv(v, P * hd * 2), be.ptr(vt), B, n, H, hd, n, S, nr,
+                                adv(cd, rope_off), adv(sd, rope_off), None)
+        be.sync()
+        gk = be.host_f32(k)[:, :, P:P + n]
+        assert np.array_equal(be.host_f32(v)[:, :, P:P + n], rv), "V rows"
+        assert np.array_equal(raw_bits(k)[:, :, keep], k0[:, :, keep]) and np.array_equal(raw_bits(v)[:, :, keep], v0[:, :, keep]), \
+            "a cache row outside [P, P + n) changed"
+    gq = be.host_f32(q)
+    eq, ek = np.abs(gq - rq).max() / np.abs(rq).max(), np.abs(gk - rk).max() / np.abs(rk).max()
+    print(f"qkv_split at offset B{B} n{n} H{H} hd{hd} P{P} kv8={kv8}: q err {eq:.3e} k err {ek:.3e} of max")
+    assert np.abs(gq - rq).max() <= 2 ** -7 * np.abs(rq).max()
+    assert np.abs(gk - rk).max() <= 2 ** -7 * np.abs(rk).max()
+
+
+def check_gemm_qkv_fused(be, B, T, H, K, bias=False, ws_mb=0, f8=False, kv8=False, seed=0, lda_pad=0):
     """EPI_QKV (round 6): the QKV GEMM whose epilogue applies RoPE, splits the heads and writes Q, the K / V cache rows
     (bf16 and / or e4m3) and the V^T scratch — against the two launches it replaces (vck_gemm EPI_BF16 + vck_qkv_split_kv / _kv8):
     every output BIT FOR BIT, nothing written behind T, for sample lengths that are and are not multiples of 32 (padded token
-    rows), ragged last tiles, split-K remainder rounds, the e4m3 operand form."""
+    rows), ragged last tiles, split-K remainder rounds, the e4m3 operand form.
+    lda_pad > 0 (bf16 operand form): the fused launch once more over token rows of stride K + lda_pad with NaN in the pad (how a
+    prefill's RMSNorm leaves them; the clamped padded token rows address through lda as well): the same comparison against
+    GEMM + split, and every output bit for bit what the lda = K launch of the fused kernel wrote."""
     from vcoder_amd import quant
 
     rng = np.random.RandomState(seed)
@@ -599,28 +743,50 @@ def check_gemm_qkv_fused(be, B, T, H, K, bias=False, ws_mb=0, f8=False, kv8=Fals
                                 be.ptr(sd), None)
     be.sync()
     bd = be.f32(b) if (bias and not f8) else None
-    be.lib.vck_gemm_qkv(be.ptr(Aop), be.ptr(asc), be.ptr(Wop), be.ptr(wsc), be.ptr(bd), B, T, H, K, K, be.ptr(q2), be.ptr(k2),
-                        None if kv8 else be.ptr(v2), be.ptr(vt2), be.ptr(k82) if kv8 else None, be.ptr(v82) if kv8 else None,
-                        Ts, Ts if kv8 else S_cap, Ts, S_cap, be.ptr(cd), be.ptr(sd), int(f8), wsp, wsb, None)
-    be.sync()
+
+    def fused(Ad, lda, o):
+        q, k, v, vt, k8, v8 = o
+        be.lib.vck_gemm_qkv(be.ptr(Ad), be.ptr(asc), be.ptr(Wop), be.ptr(wsc), be.ptr(bd), B, T, H, K, lda, be.ptr(q), be.ptr(k),
+                            None if kv8 else be.ptr(v), be.ptr(vt), be.ptr(k8) if kv8 else None, be.ptr(v8) if kv8 else None,
+                            Ts, Ts if kv8 else S_cap, Ts, S_cap, be.ptr(cd), be.ptr(sd), int(f8), wsp, wsb, None)
+        be.sync()
+
     host = lambda t: np.asarray(t.cpu().numpy() if hasattr(t, "cpu") else t)
     # With a split-K workspace and T off the 32-token grid the padded and the plain token rows sit in different tiles, so a row may
     # be summed in K-slices by one launch and in one piece by the other: fp32 summation order, i.e. single bf16 roundings, may differ
     exact = not (ws_mb and T % 32)
-    for name, a1, a2 in (("q", q1, q2), ("k", k1, k2), ("v", v1, v2), ("vt", vt1, vt2)):
-        g1, g2 = be.host_f32(a1), be.host_f32(a2)
+
+    def against_two_launches(o):
+        q2, k2, v2, vt2, k82, v82 = o
+        for name, a1, a2 in (("q", q1, q2), ("k", k1, k2), ("v", v1, v2), ("vt", vt1, vt2)):
+            g1, g2 = be.host_f32(a1), be.host_f32(a2)
+            if exact:
+                assert np.array_equal(g1, g2), f"fused QKV epilogue: {name} differs from gemm + qkv_split (B{B} T{T} H{H} K{K} f8={f8} kv8={kv8}): " \
+                                               f"{int((g1 != g2).sum())} of {g1.size} elements, max {np.abs(g1 - g2).max()}"
+            else:
+                assert np.array_equal(g1 == 0, g2 == 0) or np.abs(g1 - g2).max() <= 2.0 ** -7 * np.abs(g1).max()
+                assert np.abs(g1 - g2).max() <= 2.0 ** -7 * np.abs(g1).max() and (g1 != g2).mean() < 0.02, \
+                    f"fused QKV epilogue: {name}: {(g1 != g2).mean():.4f} of the elements differ, max {np.abs(g1 - g2).max()}"
         if exact:
-            assert np.array_equal(g1, g2), f"fused QKV epilogue: {name} differs from gemm + qkv_split (B{B} T{T} H{H} K{K} f8={f8} kv8={kv8}): " \
-                                           f"{int((g1 != g2).sum())} of {g1.size} elements, max {np.abs(g1 - g2).max()}"
+            assert np.array_equal(host(k81), host(k82)) and np.array_equal(host(v81), host(v82)), "fused QKV epilogue: e4m3 cache rows differ"
         else:
-            assert np.array_equal(g1 == 0, g2 == 0) or np.abs(g1 - g2).max() <= 2.0 ** -7 * np.abs(g1).max()
-            assert np.abs(g1 - g2).max() <= 2.0 ** -7 * np.abs(g1).max() and (g1 != g2).mean() < 0.02, \
-                f"fused QKV epilogue: {name}: {(g1 != g2).mean():.4f} of the elements differ, max {np.abs(g1 - g2).max()}"
-    if exact:
-        assert np.array_equal(host(k81), host(k82)) and np.array_equal(host(v81), host(v82)), "fused QKV epilogue: e4m3 cache rows differ"
-    else:
-        assert (host(k81) != host(k82)).mean() < 0.02 and (host(v81) != host(v82)).mean() < 0.02
-    assert be.host_f32(q2).any() and be.host_f32(vt2).any()
+            assert (host(k81) != host(k82)).mean() < 0.02 and (host(v81) != host(v82)).mean() < 0.02
+        assert be.host_f32(q2).any() and be.host_f32(vt2).any()
+
+    o2 = (q2, k2, v2, vt2, k82, v82)
+    fused(Aop, K, o2)
+    against_two_launches(o2)
+    if lda_pad:
+        assert not f8, "the e4m3 operand has no padded form"
+        o3 = list(mk())
+        if kv8:
+            o3[1] = be.zeros((B, H, Ts, hd), "bf16")
+        fused(padded_operand(be, A, lda_pad), K + lda_pad, o3)
+        against_two_launches(o3)
+        for name, a2, a3 in zip(("q", "k", "v", "vt", "k8", "v8"), o2, o3):
+            g2, g3 = raw_bits(a2), raw_bits(a3)
+            assert np.array_equal(g2, g3), f"fused QKV epilogue (B{B} T{T} H{H} K{K} kv8={kv8}): {name} of the lda = {K + lda_pad} launch " \
+                                           f"differs from the lda = K launch in {int((g2 != g3).sum())} of {g2.size} elements"
 
 
 def check_attention(be, B, H, T, hd, causal, seed=0, spike=False):

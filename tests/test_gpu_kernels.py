@@ -37,6 +37,16 @@ def test_fp16_operand_library_kernels(be16):
     kc.check_attention(be16, 2, 32, 1216, 128, True)
     kc.check_attention(be16, 3, 16, 577, 64, False)
     kc.check_gemm_qkv_fused(be16, 2, 1216, 32, 4096)
+    # the call forms of a prefill / a continuation: padded activation rows on both GEMM kernels and the fused QKV tile, the
+    # mid-size row class on the 128 x 128 kernel and the e4m3 GEMM, RMSNorm with a row stride, qkv_split behind cached rows
+    kc.check_gemm(be16, 1216, 12288, 4096, 0, False, lda_pad=64, path="8phase")
+    kc.check_gemm(be16, 640, 12288, 4096, 0, False, lda_pad=64, path="dma")
+    kc.check_gemm(be16, 136, 4096, 11008, 4, False, path="dma")
+    kc.check_gemm_qkv_fused(be16, 2, 1217, 40, 5120, lda_pad=64)
+    kc.check_gemm_f8(be16, 136, 12288, 4096, 0, path="8phase")
+    kc.check_rmsnorm(be16, 640, 4096, chain_n=512)
+    kc.check_qkv_split_at_offset(be16, 1, 257, 32, 128, 1215, False)
+    kc.check_qkv_split_at_offset(be16, 8, 17, 32, 128, 1216, True)
 
 
 # (M, N, K, epilogue): ViT QKV/out/fc1/fc2, patchify, adapters, Llama qkv/o/gate-up/down, ragged edges
@@ -47,6 +57,53 @@ def test_fp16_operand_library_kernels(be16):
     (1216, 4096, 11008, 4, False), (70, 264, 192, 0, True), (300, 320, 256, 3, False)])
 def test_gemm(be, M, N, K, epi, bias):
     kc.check_gemm(be, M, N, K, epi, bias)
+
+
+# ---- the GEMMs as the engine calls them --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("M,N,K,epi,bias,ws,path", [
+    (1216, 12288, 4096, 0, False, 0, "8phase"), (1216, 22016, 4096, 5, False, 0, "8phase"), (9728, 12288, 4096, 0, False, 64, "8phase"),
+    (2432, 15360, 5120, 0, False, 0, "8phase"), (640, 12288, 4096, 0, False, 0, "dma"), (577, 3072, 1024, 0, True, 0, "dma")])
+def test_gemm_padded_activation_rows(be, M, N, K, epi, bias, ws, path):
+    """Every RMSNorm -> GEMM pair of a prefill or a continuation reads activation rows of stride D + 64 (the norm's ldy): the QKV and
+    gate / up shapes of 7b and 13b on the 8-phase kernel (one with a split-K remainder round), the 128 x 128 LDS-DMA kernel at a
+    continuation's and a ViT's row counts.  NaN in the pad columns; float64 tolerance unchanged and the bits of the lda = K launch."""
+    kc.check_gemm(be, M, N, K, epi, bias, ws_mb=ws, lda_pad=64, path=path)
+
+
+@pytest.mark.parametrize("B,T,H,K,ws", [(8, 1216, 32, 4096, 64), (2, 1217, 40, 5120, 0), (1, 96, 2, 256, 0)])
+def test_gemm_qkv_fused_epilogue_padded_activation_rows(be, B, T, H, K, ws):
+    """the fused-QKV tile over rows of stride K + 64 (its clamped padded token rows included): q, k, v, vt bit for bit the lda = K launch"""
+    kc.check_gemm_qkv_fused(be, B, T, H, K, ws_mb=ws, lda_pad=64)
+
+
+@pytest.mark.parametrize("M,N,K,epi,bias,pad", [
+    (136, 12288, 4096, 0, False, 64), (136, 4096, 11008, 4, False, 0), (136, 32000, 4096, 3, False, 64), (640, 4096, 4096, 4, False, 0),
+    (1023, 22016, 4096, 5, False, 64), (257, 15360, 5120, 0, False, 64), (257, 5120, 13824, 4, False, 0), (577, 4096, 1024, 1, True, 0),
+    (577, 1024, 4096, 4, True, 64)])
+def test_gemm_mid_size_rows(be, M, N, K, epi, bias, pad):
+    """129 .. 1023 rows — every linear of a continuation above the GEMV crossover, a short B = 1 prefill, one image's ViT — at the
+    full 7b / 13b / ViT-L shapes: the 128 x 128 LDS-DMA kernel (asserted through the launch counter) against float64, half of the
+    cases over rows of stride K + 64"""
+    kc.check_gemm(be, M, N, K, epi, bias, lda_pad=pad, path="dma")
+
+
+@pytest.mark.parametrize("M,N,K,epi,path", [(1023, 512, 4096, 0, "dma"), (1024, 504, 4096, 0, "dma"), (1024, 512, 4096, 0, "8phase"),
+                                            (1023, 4096, 4096, 4, "dma"), (1024, 4096, 4096, 4, "8phase")])
+def test_gemm_dispatch_edges(be, M, N, K, epi, path):
+    """either side of the launcher's rule (8-phase from M >= 1024 and N >= 512 on), each against float64 and the counter"""
+    kc.check_gemm(be, M, N, K, epi, False, path=path)
+
+
+@pytest.mark.parametrize("M,N,K,epi", [(136, 12288, 4096, 0), (640, 4096, 11008, 4), (1023, 22016, 4096, 5), (257, 5120, 13824, 4)])
+def test_gemm_f8_mid_size_rows(be, M, N, K, epi):
+    """the e4m3 GEMM of an fp8 continuation: the 8-phase kernel with clamped rows at 129 .. 1023 rows"""
+    kc.check_gemm_f8(be, M, N, K, epi, path="8phase")
+
+
+@pytest.mark.parametrize("B,n,H,hd,P", [(1, 257, 32, 128, 1215), (8, 17, 32, 128, 1216), (2, 33, 40, 128, 2047)])
+@pytest.mark.parametrize("kv8", [False, True])
+def test_qkv_split_at_offset(be, B, n, H, hd, P, kv8):
+    kc.check_qkv_split_at_offset(be, B, n, H, hd, P, kv8)
 
 
 @pytest.mark.parametrize("B,T,H,K,ws,f8,kv8", [(8, 1216, 32, 4096, 64, False, False), (2, 1217, 40, 5120, 0, False, False),
@@ -102,7 +159,8 @@ def test_small_ops(be):
     kc.check_interleave(be, 11008, 256)
     kc.check_layernorm(be, 4616, 1024)
     kc.check_layernorm(be, 5, 128)
-    kc.check_rmsnorm(be, 9728, 4096)
+    kc.check_rmsnorm(be, 9728, 4096, chain_n=512)            # (the rmsnorm_ld -> gemm chain on the 8-phase kernel; the others on the 128 x 128 one)
+    kc.check_rmsnorm(be, 640, 5120)
     kc.check_rmsnorm(be, 8, 5120, gather=True)
     kc.check_rmsnorm(be, 3, 256)
     kc.check_rmsnorm_q8(be, 9728, 4096)
@@ -213,22 +271,30 @@ def test_split_small_and_attention_kernels(be):
 
 
 def test_dma_kernels_are_race_free_and_bit_reproducible(be):
-    """The counted-vmcnt schedules (8-phase GEMM, LDS-DMA ring GEMV) order LDS-DMA writes against ds_reads by hand; a
+    """The counted-vmcnt schedules (8-phase GEMM, 128 x 128 LDS-DMA GEMM, LDS-DMA ring GEMV) order LDS-DMA writes against ds_reads by hand; a
     misplaced wait shows up as rare wrong tiles that depend on timing.  Screen: many back-to-back launches of the true
     shapes (odd k-tile counts, ragged M, both ring geometries) must all produce the bit pattern of the first launch, and
-    that pattern must match the oracle (checked by test_gemm / test_gemv on the same shapes)."""
+    that pattern must match the oracle (checked by test_gemm / test_gemm_mid_size_rows / test_gemv on the same shapes)."""
     import numpy as np
     import torch
 
     rng = np.random.RandomState(3)
-    for (M, N, K, epi) in [(1216, 4096, 11008, 0), (9728, 1024, 4096, 3), (2000, 768, 4160, 0)]:
-        A, W = be.bf16(kc.bf16_round(rng.randn(M, K))), be.bf16(kc.bf16_round(rng.randn(N, K) * 0.05))
+    # (M, N, K, epi, lda pad, kernel): the three 8-phase shapes; the 128 x 128 LDS-DMA kernel at a continuation's rows (172 k-tiles,
+    # SwiGLU, padded activation rows) — the launch counters prove which kernel was screened
+    for (M, N, K, epi, pad, path) in [(1216, 4096, 11008, 0, 0, "8phase"), (9728, 1024, 4096, 3, 0, "8phase"), (2000, 768, 4160, 0, 0, "8phase"),
+                                      (640, 4096, 11008, 0, 0, "dma"), (136, 22016, 4096, 5, 0, "dma"), (1023, 12288, 4096, 3, 64, "dma")]:
+        Ah, W = kc.bf16_round(rng.randn(M, K)), be.bf16(kc.bf16_round(rng.randn(N, K) * 0.05))
+        A = kc.padded_operand(be, Ah, pad) if pad else be.bf16(Ah)
+        ldo = N // 2 if epi == 5 else N
+        before = kc.gemm_launch_counts(be)
         outs = []
         for it in range(12):
-            out = be.zeros((M, N), "f32" if epi == 3 else "bf16")
-            be.lib.vck_gemm(be.ptr(A), be.ptr(W), None, be.ptr(out), M, N, K, K, K, N, epi, None)   # no sync in between
+            out = be.zeros((M, ldo), "f32" if epi == 3 else "bf16")
+            be.lib.vck_gemm(be.ptr(A), be.ptr(W), None, be.ptr(out), M, N, K, K + pad, K, ldo, epi, None)   # no sync in between
             outs.append(out)
         be.sync()
+        kc.assert_gemm_path(be, before, path, 12, f"gemm M{M} N{N} K{K}")
+        assert outs[0].any()
         for o in outs[1:]:
             assert torch.equal(o, outs[0]), f"gemm M{M} N{N} K{K}: launches differ"
     for (M, N, K, epi) in [(8, 12288, 4096, 0), (8, 22016, 4096, 3), (8, 4096, 11008, 1), (16, 5120, 13824, 1), (3, 48, 288, 1)]:

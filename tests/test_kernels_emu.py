@@ -19,15 +19,39 @@ QKV_CASES = [(2, 96, 2, 128, False, 0, False, False), (2, 70, 2, 192, True, 0, F
              (1, 64, 2, 256, False, 0, True, True)]
 
 
+@pytest.fixture(scope="module")
+def be16():
+    """libvcoder_emu_f16.so: the same sources built with -DVC_F16 (IEEE fp16 MFMA operands)"""
+    return kc.EmuBackend("fp16")
+
+
+# (B, n, H, hd, P, kv8): qkv_split as a continuation calls it — n ragged, P off the 64-key grid
+QKV_OFFSET_CASES = [(1, 21, 2, 128, 75, False), (2, 5, 2, 128, 130, True), (1, 70, 1, 64, 37, False), (3, 13, 2, 128, 1, True),
+                    (1, 99, 2, 128, 89, True)]
+
+
 @pytest.mark.parametrize("M,N,K,epi,bias", GEMM_CASES)
 def test_gemm(be, M, N, K, epi, bias):
-    kc.check_gemm(be, M, N, K, epi, bias)
+    kc.check_gemm(be, M, N, K, epi, bias, path=_path(be, "dma"))
+
+
+def _path(be, default):
+    """the kernel the launcher must choose for the small bf16 shapes of this file: the 128 x 128 one unless the test hook is on"""
+    return "8phase" if getattr(be, "forced_8phase", False) else default
+
+
+@pytest.mark.parametrize("M,N,K,epi,bias", GEMM_CASES)
+def test_gemm_padded_rows(be, M, N, K, epi, bias):
+    """the activation rows with the row stride of a prefill's RMSNorm output (lda = K + 64, NaN in the pad, the array ending behind
+    the last row's valid columns), and the weight rows strided as well: same tolerance, same bits as lda = ldw = K"""
+    kc.check_gemm(be, M, N, K, epi, bias, lda_pad=64, path=_path(be, "dma"))
+    kc.check_gemm(be, M, N, K, epi, bias, seed=1, lda_pad=64, ldw_pad=8 * (1 + epi), ws_mb=1, path=_path(be, "dma"))   # through vck_gemm_ws
 
 
 def test_gemm_splitk_remainder_round(be):
     """260 tiles of 256x256 = one full round + 4 remainder tiles, cut into 2 K-slices each and finished by the fix-up
-    launch (bias + quick-GELU epilogue; ragged M)."""
-    kc.check_gemm(be, 1000 + 24, 16640 - 8, 128, 1, True, seed=2, ws_mb=4)
+    launch (bias + quick-GELU epilogue; ragged M); again over activation rows of stride K + 64, bit for bit."""
+    kc.check_gemm(be, 1000 + 24, 16640 - 8, 128, 1, True, seed=2, ws_mb=4, lda_pad=64, path="8phase")
 
 
 @pytest.mark.parametrize("M,N,K,epi", [(8, 64, 256, 0), (3, 32, 1024, 1), (16, 48, 288, 2), (8, 64, 256, 3),
@@ -45,7 +69,7 @@ def test_gemv_fp8(be, M, N, K, epi, norm):
 
 @pytest.mark.parametrize("M,N,K,epi", GEMM_F8_CASES)
 def test_gemm_f8(be, M, N, K, epi):
-    kc.check_gemm_f8(be, M, N, K, epi)
+    kc.check_gemm_f8(be, M, N, K, epi, path="8phase")
 
 
 def test_gemm_f8_splitk_remainder_round(be):
@@ -88,7 +112,7 @@ def test_layernorm(be, rows, D):
     kc.check_layernorm(be, rows, D)
 
 
-@pytest.mark.parametrize("rows,D,gather", [(3, 256, False), (6, 4096, False), (2, 5120, True)])
+@pytest.mark.parametrize("rows,D,gather", [(3, 256, False), (6, 4096, False), (2, 5120, True), (9, 5120, False)])
 def test_rmsnorm(be, rows, D, gather):
     kc.check_rmsnorm(be, rows, D, gather)
 
@@ -108,6 +132,11 @@ def test_vit_front(be):
 @pytest.mark.parametrize("B,T,H,hd,rope", [(1, 70, 2, 128, True), (2, 17, 2, 64, False)])
 def test_qkv_split(be, B, T, H, hd, rope):
     kc.check_qkv_split(be, B, T, H, hd, rope)
+
+
+@pytest.mark.parametrize("B,n,H,hd,P,kv8", QKV_OFFSET_CASES)
+def test_qkv_split_at_offset(be, B, n, H, hd, P, kv8):
+    kc.check_qkv_split_at_offset(be, B, n, H, hd, P, kv8)
 
 
 
@@ -180,6 +209,13 @@ def test_gemm_qkv_fused_epilogue(be, B, T, H, K, bias, ws, f8, kv8):
     kc.check_gemm_qkv_fused(be, B, T, H, K, bias=bias, ws_mb=ws, f8=f8, kv8=kv8)
 
 
+@pytest.mark.parametrize("B,T,H,K,bias,ws,f8,kv8", [c for c in QKV_CASES if not c[6]] + [(2, 37, 2, 128, False, 1, False, True)])
+def test_gemm_qkv_fused_epilogue_padded_rows(be, B, T, H, K, bias, ws, f8, kv8):
+    """token rows of stride K + 64 (NaN pad, tight end): the clamped padded token rows of a sample length off the 32-token grid
+    address through lda too"""
+    kc.check_gemm_qkv_fused(be, B, T, H, K, bias=bias, ws_mb=ws, f8=f8, kv8=kv8, lda_pad=64)
+
+
 def test_gemm_qkv_fused_epilogue_splitk_round(be):
     """more than one round of 256 tiles with a short last round: K-slices + the QKV fix-up launch (2 x 640 tokens, H = 22:
     5 x 66 = 330 tiles -> 74 remainder tiles in 3 slices)"""
@@ -190,18 +226,40 @@ def test_alternate_kernel_variants(be):
     """Every GEMM case above again with the bf16 8-phase kernel forced onto every size (vck_set_gemm_force_8phase): small, ragged
     and 1-3 k-tile problems, the split-K rounds of the bf16 and the e4m3 form, the fused QKV epilogue against that GEMM."""
     be.lib.vck_set_gemm_force_8phase(1)
+    be.forced_8phase = True
     try:
         for case in GEMM_CASES:
             test_gemm(be, *case)
+            test_gemm_padded_rows(be, *case)
+        kc.check_rmsnorm(be, 6, 4096)      # rmsnorm_ld -> gemm(lda = D + 64) on the 8-phase kernel
         test_gemm_splitk_remainder_round(be)
         for case in GEMM_F8_CASES:
             test_gemm_f8(be, *case)
         test_gemm_f8_splitk_remainder_round(be)
         for case in QKV_CASES:
             test_gemm_qkv_fused_epilogue(be, *case)
+            if not case[6]:
+                test_gemm_qkv_fused_epilogue_padded_rows(be, *case)
         test_gemm_qkv_fused_epilogue_splitk_round(be)
     finally:
         be.lib.vck_set_gemm_force_8phase(0)
+        be.forced_8phase = False
+
+
+def test_fp16_operand_library_new_call_forms(be16):
+    """one case of each strided / offset call form on the -DVC_F16 build (its NaN pad pattern, its conversions)"""
+    assert be16.lib.vc_operand_format() == 1
+    kc.check_gemm(be16, 200, 136, 128, 0, True, lda_pad=64, ldw_pad=16, path="dma")
+    be16.lib.vck_set_gemm_force_8phase(1)
+    try:
+        kc.check_gemm(be16, 70, 264, 192, 1, True, lda_pad=64, path="8phase")
+    finally:
+        be16.lib.vck_set_gemm_force_8phase(0)
+    kc.check_gemm_qkv_fused(be16, 2, 70, 2, 192, bias=True, lda_pad=64)
+    kc.check_gemm_f8(be16, 100, 144, 128, 0, path="8phase")
+    kc.check_rmsnorm(be16, 6, 4096)
+    kc.check_qkv_split_at_offset(be16, 1, 21, 2, 128, 75, False)
+    kc.check_qkv_split_at_offset(be16, 2, 5, 2, 128, 130, True)
 
 
 @pytest.mark.parametrize("M,N,K,epi,norm,G,ks", [

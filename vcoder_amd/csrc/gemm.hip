@@ -16,6 +16,7 @@
 
 #include "vc_device.h"
 #include <algorithm>
+#include <atomic>
 #include <stdexcept>
 
 #include "kernels.h"
@@ -759,6 +760,10 @@ static void launch_gemm_8phase(const GemmArgs& a, hipStream_t s) {
 // test hook (vck_set_gemm_force_8phase): the bf16 8-phase kernel for every size inside one process
 static bool g_force_8phase = false;
 void set_gemm_force_8phase(bool on) { g_force_8phase = on; }
+// which kernel launch_gemm chose, counted on the host (tests pin the dispatch rule to the shapes they mean to cover)
+static std::atomic<unsigned long> g_gemm_dma_launches{0}, g_gemm_8phase_launches{0};   // sessions launch from their own threads
+unsigned long gemm_dma_launches() { return g_gemm_dma_launches.load(std::memory_order_relaxed); }
+unsigned long gemm_8phase_launches() { return g_gemm_8phase_launches.load(std::memory_order_relaxed); }
 
 // The e4m3 form (GemmArgs::f8) and the fused QKV epilogue always take the 8-phase kernel (any size: rows are clamped, stores
 // masked); the other bf16 GEMMs take it from M >= 1024 and N >= 512 on, the 128 x 128 LDS-DMA kernel below that.
@@ -771,6 +776,8 @@ void launch_gemm(const GemmArgs& a, int epilogue, hipStream_t s) {
             a.M != e.B * e.Tp || !e.q || !e.k || !e.vt || !e.rope_cos || !e.rope_sin || (!e.v && !e.v8))
             throw std::runtime_error("gemm: EPI_QKV needs hd 128, D % 256 == 0, N = 3 D, M = B * Tp with Tp = rup(T, 32), q / k / v / vt and the RoPE tables");
     }
+    const bool eight = a.f8 || epilogue == EPI_QKV || g_force_8phase || (a.M >= 1024 && a.N >= 512);
+    (eight ? g_gemm_8phase_launches : g_gemm_dma_launches).fetch_add(1, std::memory_order_relaxed);
     if (a.f8) {
         switch (epilogue) {
             case EPI_QKV: return launch_gemm_8phase<EPI_QKV, true>(a, s);
@@ -781,7 +788,7 @@ void launch_gemm(const GemmArgs& a, int epilogue, hipStream_t s) {
         }
     }
     if (epilogue == EPI_QKV) return launch_gemm_8phase<EPI_QKV, false>(a, s);
-    if (g_force_8phase || (a.M >= 1024 && a.N >= 512)) {
+    if (eight) {
 #define VC_G8(E) return a.kwrap > 0 ? launch_gemm_8phase<E, false, true>(a, s) : launch_gemm_8phase<E, false>(a, s)
         switch (epilogue) {
             case EPI_BF16: VC_G8(EPI_BF16);

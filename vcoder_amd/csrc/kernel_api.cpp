@@ -110,6 +110,9 @@ VCK_EXPORT void vck_rmsnorm(const float* x, const int* row_idx, const float* w, 
     if (row_idx) launch_rmsnorm_rows(x, row_idx, w, y, rows, D, eps, S(stream));
     else launch_rmsnorm(x, w, y, rows, D, eps, S(stream));
 }
+VCK_EXPORT void vck_rmsnorm_ld(const float* x, const float* w, uint16_t* y, int rows, int D, float eps, int ldy, void* stream) {
+    launch_rmsnorm(x, w, y, rows, D, eps, S(stream), ldy);
+}
 VCK_EXPORT void vck_rmsnorm_q8(const float* x, const float* w, uint8_t* q, float* scale, int rows, int D, float eps, void* stream) {
     launch_rmsnorm_q8(x, w, q, scale, rows, D, eps, S(stream));
 }
@@ -286,6 +289,8 @@ VCK_EXPORT void vck_gemv_full(const uint16_t* X, const void* Wp, const float* ws
 VCK_EXPORT void vck_set_gemv_variant(int v) { set_gemv_variant(v); }
 VCK_EXPORT void vck_set_gemm_force_8phase(int on) { set_gemm_force_8phase(on != 0); }
 VCK_EXPORT void vck_set_gemv_wide(int v) { set_gemv_wide(v); }
+VCK_EXPORT unsigned long long vck_gemm_dma_launches() { return gemm_dma_launches(); }
+VCK_EXPORT unsigned long long vck_gemm_8phase_launches() { return gemm_8phase_launches(); }
 VCK_EXPORT unsigned long long vck_gemv_wide_launches() { return gemv_wide_launches(); }
 VCK_EXPORT unsigned long long vck_gemv_wg_launches() { return gemv_wg_launches(); }
 VCK_EXPORT void vck_rmsnorm_split(const float* x, const int* row_idx, const float* w, uint16_t* y, int rows, int D, float eps,

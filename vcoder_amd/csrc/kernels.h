@@ -151,6 +151,8 @@ void launch_gemv(const GemvArgs& a, int epilogue, hipStream_t s);
 // the decode GEMV of precision mode "split": 0 = per-wave rings (two weight passes of 16 rows), -1 / 1 = the workgroup-shared form
 void set_gemv_variant(int v);
 void set_gemm_force_8phase(bool on);   // test hook: the bf16 GEMMs of every size take the 8-phase 256 x 256 kernel
+unsigned long gemm_dma_launches();      // launches launch_gemm sent to the 128 x 128 LDS-DMA kernel so far (tests)
+unsigned long gemm_8phase_launches();   // ... and to the 8-phase 256 x 256 kernel (split-K fix-up launches not counted)
 void set_gemv_wide(int v);       // -1 / 1 = the measured classes (default), 0 = off, 2 = every class (launch_gemv_wide)
 unsigned long gemv_wide_launches();
 bool gemv_wg_enabled();                          // the workgroup-shared form serves the split step's GEMVs
