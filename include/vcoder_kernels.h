@@ -220,6 +220,37 @@ void vck_qkv_split_kv8(const uint16_t* qkv, uint16_t* q, uint16_t* k, uint8_t* k
 void vck_attention_decode_kv8(const uint16_t* qkv, uint8_t* k, uint8_t* v, uint16_t* out, int B, int H, int hd, int kv_stride,
                               const int* pos_rows, int pos_stride, const int* active_rows, const float* rope_cos,
                               const float* rope_sin, float scale, void* stream);
+/* ---- the attention kernels with the arguments the engine sets for padded batches and for a prefill into a cache (tests).
+ * key_mask [B][mask_stride] bytes: key_mask[b * mask_stride + key] == 0 hides that key from every query of sequence b (NULL = no
+ * mask; key 0 must be visible, and for the decode step the row's own position).  Bytes at keys the launch does not reach are
+ * never read.
+ * vck_attention_ex: vck_attention with V^T rows of their own stride (vt_stride columns, a multiple of 64; 0 = kv_stride) — the LLM
+ *   prefill's form: q_stride = S, kv_stride = the cache capacity, vt_stride = S rounded up to 64 — and a key mask.
+ * vck_attention_split_ex: vck_attention_split likewise.
+ * vck_attention_decode_masked: the per-row fused decode attention (vck_attention_decode_rows / _kv32 / _kv24 / _kv8) over the cache
+ *   format kv_format — 0 bf16, 1 fp32, 2 fp24, 3 e4m3; qkv is fp32 and G the output row group for 1 and 2 — with a mask per row.
+ * vck_attention_f32_masked: vck_attention_f32 with a key mask.
+ * vck_attn_probs: output_attentions — probabilities out [B,H,T,Tk'] fp32 (Tk' = Tk, or T when Tk == 0) of T queries at positions
+ *   q_pos0 + t over keys 0 .. q_pos0 + t ([HF] llama eager_attention_forward :191-214 attn_weights); hidden and future keys get 0.
+ *   q: q32 [B,H,q_stride,hd] fp32, or bf16 q_hi (+ q_lo: hi + lo planes); k rows [B,H,kv_stride,hd]: k32 fp32, or bf16 k_hi (+ k_lo),
+ *   or e4m3 bytes k8, or fp24 rows k24 (the first non-NULL of k32, k8, k_hi, k24 is used).  keys <= 4096. */
+void vck_attention_ex(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* out, int B, int H, int T, int hd,
+                      int q_stride, int kv_stride, int vt_stride, int causal, float scale, const uint8_t* key_mask, int mask_stride,
+                      void* stream);
+void vck_attention_split_ex(const uint16_t* q_hi, const uint16_t* q_lo, const uint16_t* k_hi, const uint16_t* k_lo,
+                            const uint16_t* vt_hi, const uint16_t* vt_lo, uint16_t* out, int B, int H, int T, int hd, int q_stride,
+                            int kv_stride, int vt_stride, int causal, float scale, int ldo, int lo_off, const uint8_t* key_mask,
+                            int mask_stride, void* stream);
+void vck_attention_decode_masked(const void* qkv, void* k, void* v, uint16_t* out, int B, int H, int hd, int kv_stride,
+                                 const int* pos_rows, int pos_stride, const int* active_rows, const float* rope_cos,
+                                 const float* rope_sin, float scale, int kv_format, int G, const uint8_t* key_mask, int mask_stride,
+                                 void* stream);
+void vck_attention_f32_masked(const float* q, const float* k, const float* v, float* out, int B, int H, int Tq, int hd, int q_stride,
+                              int kv_stride, int causal, int Tk, const int* pos0_dev, float scale, const uint8_t* key_mask,
+                              int mask_stride, void* stream);
+void vck_attn_probs(const float* q32, const uint16_t* q_hi, const uint16_t* q_lo, const float* k32, const uint16_t* k_hi,
+                    const uint16_t* k_lo, const void* k24, const uint8_t* k8, float* out, int B, int H, int T, int hd, int q_stride,
+                    int kv_stride, float scale, int Tk, int q_pos0, const uint8_t* key_mask, int mask_stride, void* stream);
 /* deterministic synthetic tensors (vcoder_amd/synth.py) and dtype converts */
 void vck_synth_bf16(uint16_t* out, uint64_t n, uint32_t tseed, float offset, float halfwidth, void* stream);
 void vck_synth_f32(float* out, uint64_t n, uint32_t tseed, float offset, float halfwidth, void* stream);

@@ -23,15 +23,30 @@ def _u8(be, a):
     return torch.from_numpy(a).to(be.dev)
 
 
-def check_attention_extend(be, B, H, P, n, kv8, masked=False, seed=0, tail=8):
+def check_attention_extend(be, B, H, P, n, kv8, masked=False, seed=0, tail=8, needle=False, patterns=None, beta=None):
     """n queries per (b, h) at positions P .. P+n-1 over a key-major cache of P + n + `tail` rows (the tail holds values that
-    must not be read: huge in bf16, NaN bytes in e4m3).  Reference: fp64 softmax attention over the values the kernel was given."""
+    must not be read: huge in bf16, NaN bytes in e4m3).  Reference: fp64 softmax attention over the values the kernel was given
+    (kernel_cases.attention_reference), judged by the historical 2^-7 bound and by the signal-scaled bars of kernel_cases.
+    needle: chunk key P + t = beta * q[t - 1] (t >= 1) — query t - 1 would score the key right behind its causal range >= 10 nats
+    above every key it sees; patterns: kernel_cases.MASK_PATTERNS names, row b takes patterns[b % len], mask stride MASK_STRIDE, the
+    hidden keys hold the largest finite magnitudes of the cache format."""
     hd = 128
     rng = np.random.RandomState(seed)
     S = P + n + tail
     q = rng.randn(B, H, n, hd)
     k = rng.randn(B, H, S, hd)
     v = rng.randn(B, H, S, hd)
+    big = kc.POISON_E4M3 if kv8 else kc.POISON
+    prow = np.zeros(hd)
+    prow[0] = big
+    if patterns:
+        q[..., 0] = kc.Q_SHARED
+    if needle:
+        kc._needle_keys(q, k[:, :, :P + n], beta, first=P + 1)
+    if patterns:
+        pkm = kc.key_masks(kc._names_for(B, patterns), [P + n] * B)
+        for b in range(B):
+            k[b][:, :P + n][:, pkm[b, :P + n] == 0], v[b][:, :P + n][:, pkm[b, :P + n] == 0] = prow, big
     qd = be.bf16(q)
     q_used = be.host_f32(qd).reshape(B, H, n, hd).astype(np.float64)
     if kv8:
@@ -53,19 +68,23 @@ def check_attention_extend(be, B, H, P, n, kv8, masked=False, seed=0, tail=8):
         for b in range(B):
             hide = rng.choice(np.arange(1, max(P, 2)), size=max(1, P // 3), replace=False) if P > 1 else []
             km[b, hide] = 0
+    if patterns:
+        masked, km, mstride = True, pkm, kc.MASK_STRIDE
     out = be.zeros((B * n, H * hd), "bf16")
     scale = 1.0 / math.sqrt(hd)
+    hidden = kc.attention_hidden(B, n, Tk, True, P, km)
+    if needle and n > 1:
+        kc._assert_needle(q_used, k_used[:, :, :Tk], scale, hidden, P)
+    if patterns:
+        kc._assert_poison(q_used, k_used[:, :, :Tk], scale, hidden, prow)
     kc._call(be, "vck_attention_extend", qd, kd, vd, out, B, H, n, P, hd, n, S, int(kv8), scale,
              _u8(be, km) if masked else None, mstride)
-    s = np.matmul(q_used, k_used[:, :, :Tk].transpose(0, 1, 3, 2)) * scale
-    keys, qpos = np.arange(Tk)[None, :], P + np.arange(n)[:, None]
-    hidden = (keys > qpos)[None, None] | (km[:, None, None, :Tk] == 0)
-    s = np.where(hidden, -np.inf, s)
-    pr = np.exp(s - s.max(-1, keepdims=True))
-    pr /= pr.sum(-1, keepdims=True)
-    ref = np.matmul(pr, v_used[:, :, :Tk]).transpose(0, 2, 1, 3).reshape(B * n, H * hd)
     got = be.host_f32(out).reshape(B * n, H * hd)
     assert np.isfinite(got).all(), "extend attention: non-finite output (the cache tail was read)"
+    what = f"extend attention B{B} H{H} P{P} n{n} kv8={int(kv8)} masked{int(masked)} needle{int(needle)} mask {patterns} [{be.operands}]"
+    fig, ref = kc.attention_judge(what, got.reshape(B, n, H, hd).transpose(0, 2, 1, 3), q_used, k_used[:, :, :Tk], v_used[:, :, :Tk], scale,
+                                  hidden, "flash", be.operands)
+    ref = ref.transpose(0, 2, 1, 3).reshape(B * n, H * hd)
     err = float(np.abs(got - ref).max())
     assert err < 2 ** -7 * max(1.0, float(np.abs(ref).max())), f"extend attention B{B} H{H} P{P} n{n} kv8={kv8}: abs err {err}"
     return err

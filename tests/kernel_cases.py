@@ -803,13 +803,19 @@ def check_attention(be, B, H, T, hd, causal, seed=0, spike=False):
     out = be.zeros((B * T, H * hd), "bf16")
     scale = 1.0 / math.sqrt(hd)
     vtp = vtp[..., vt_key_pos(Ts)]
-    _call(be, "vck_attention", be.bf16(qp), be.bf16(kp), be.bf16(vtp), out, B, H, T, hd, Ts, Ts, int(causal), scale)
+    qd, kd, vd = be.bf16(qp), be.bf16(kp), be.bf16(vtp)
+    _call(be, "vck_attention", qd, kd, vd, out, B, H, T, hd, Ts, Ts, int(causal), scale)
     ref = cpu_ref.softmax_attention(torch.from_numpy(q), torch.from_numpy(k), torch.from_numpy(v), scale, causal,
                                     cpu_ref.Rounder(True))
     ref = ref.transpose(1, 2).reshape(B * T, H * hd).numpy()
     got = be.host_f32(out)
     err = np.abs(got - ref).max()
     assert err < 2 ** -7 * max(1.0, np.abs(ref).max()), f"attention B{B} H{H} T{T} hd{hd} causal{causal}: abs err {err}"
+    # the shared float64 reference over the values the kernel was given, and the signal-scaled bars (C_MAX / C_RMS below)
+    q_u, k_u = be.host_f32(qd)[:, :, :T], be.host_f32(kd)[:, :, :T]
+    v_u = be.host_f32(vd)[..., np.argsort(vt_key_pos(Ts))][..., :T].transpose(0, 1, 3, 2)
+    attention_judge(f"attention B{B} H{H} T{T} hd{hd} causal{int(causal)} spike{int(spike)} [{be.operands}]",
+                    got.reshape(B, T, H, hd).transpose(0, 2, 1, 3), q_u, k_u, v_u, scale, attention_hidden(B, T, T, causal), "flash", be.operands)
     return err
 
 
@@ -972,6 +978,8 @@ def check_attention_decode_fused(be, B, H, hd, pos, seed=0, per_row=False):
         ref = ref.transpose(1, 2).reshape(D).numpy()
         err = np.abs(got[b] - ref).max()
         assert err < 2 ** -7 * max(1.0, np.abs(ref).max()), f"attention_decode_fused row {b} pos {pb}: abs err {err}"
+        attention_judge(f"attention_decode_fused row {b} of B{B} H{H} hd{hd} pos {pb}", got[b].reshape(1, H, 1, hd), rq, k_all, v_all, scale,
+                        attention_hidden(1, 1, pb + 1, False), "decode", be.operands)
 
 
 RS = dict(ACTIVE=0, FINISHED=1, STEP=2, POS=3, MAXNEW=4, EOS=5, PAD=6, NSTOP=7, SAMPLE=8, INVTEMP=9, TOPK=10, TOPP=11,
@@ -1220,6 +1228,10 @@ def check_attention_f32(be, B, H, T, hd, causal, decode_pos=None, seed=0):
                                         scale, False, cpu_ref.Rounder(False)).transpose(1, 2).reshape(B, H * hd).numpy()
     err = np.abs(be.host_f32(out) - ref).max()
     assert err < 2e-6 * max(1.0, np.abs(ref).max()) + 2e-6, f"attention_f32 abs err {err}"
+    Tq = 1 if decode_pos is not None else T
+    Tk = decode_pos + 1 if decode_pos is not None else T
+    attention_judge(f"attention_f32 B{B} H{H} T{T} hd{hd}", be.host_f32(out).reshape(B, Tq, H, hd).transpose(0, 2, 1, 3), q, k[:, :, :Tk], v[:, :, :Tk],
+                    scale, attention_hidden(B, Tq, Tk, bool(causal) and decode_pos is None), None, tol_rel=2e-6, tol_abs=2e-6)
 
 
 def check_qkv_rope_f32(be, B, T, H, hd, pos0):
@@ -1516,6 +1528,8 @@ def check_qkv_split32_and_attention_split(be, B, H, T, hd, causal, rope=True, se
     ref = ref.transpose(1, 2).reshape(B * T, D).numpy()
     err = np.abs(_split_value(be, out, D) - ref).max()
     assert err < 3e-5 * max(1.0, np.abs(ref).max()), f"attention_split B{B} H{H} T{T} hd{hd} causal{causal}: abs err {err}"
+    attention_judge(f"attention_split B{B} H{H} T{T} hd{hd} causal{int(causal)}", _split_value(be, out, D).reshape(B, T, H, hd).transpose(0, 2, 1, 3),
+                    q.numpy(), k.numpy(), v.numpy(), scale, attention_hidden(B, T, T, causal), None, tol_rel=3e-5)
     return err
 
 
@@ -1569,6 +1583,8 @@ def check_attention_decode_kv32(be, B, H, hd, pos, seed=0):
         ref = ref.transpose(1, 2).reshape(D).numpy()
         err = np.abs(go[orow] + go[orow + G] - ref).max()
         assert err < 3e-5 * max(1.0, np.abs(ref).max()), f"decode attention kv32 row {b}: {err}"
+        attention_judge(f"decode attention kv32 row {b} pos {pb}", (go[orow] + go[orow + G]).reshape(1, H, 1, hd), q[None].numpy(), k_all.numpy(),
+                        v_all.numpy(), scale, attention_hidden(1, 1, pb + 1, False), None, tol_rel=3e-5)
 
 
 # ---- the workgroup-shared-activation decode GEMV of precision mode "split" (gemv_wg_kernel) -------------------------------------
@@ -1883,6 +1899,8 @@ def check_kv24(be, B, H, hd, pos, T_prefill=70, seed=0):
         ref = ref.transpose(1, 2).reshape(D).numpy()
         err = np.abs(go[orow] + go[orow + G] - ref).max()
         assert err < 3e-5 * max(1.0, np.abs(ref).max()), f"decode attention kv24 row {b}: {err}"
+        attention_judge(f"decode attention kv24 row {b} pos {pb}", (go[orow] + go[orow + G]).reshape(1, H, 1, hd), q[None].numpy(), k_all.numpy(),
+                        v_all.numpy(), scale, attention_hidden(1, 1, pb + 1, False), None, tol_rel=3e-5)
 
 
 # ---- e4m3 KV caches of the fp8 weight format -------------------------------------------------------------------------------------
@@ -1960,3 +1978,467 @@ def check_kv8(be, B, H, hd, pos, T_prefill=70, seed=0):
         ref = ref.transpose(1, 2).reshape(D).numpy()
         err = np.abs(got[b] - ref).max()
         assert err < 2 ** -7 * max(1.0, np.abs(ref).max()), f"decode attention kv8 row {b} pos {pb}: abs err {err}"
+        attention_judge(f"decode attention kv8 row {b} of B{B} H{H} hd{hd} pos {pb}", got[b].reshape(1, H, 1, hd), rq, k_all, v_all, scale,
+                        attention_hidden(1, 1, pb + 1, False), "decode", be.operands)
+
+
+# =====================================================================================================================================
+# Attention: ONE float64 reference, a signal-scaled error measure, and inputs that turn a boundary error into an O(1) error
+# =====================================================================================================================================
+U_OUT = 2.0 ** -8      # unit roundoff of the bf16 output (kept for the fp16-operand library, whose operands are finer)
+POISON = 3.0e4         # the largest magnitude used behind a limit: finite in bf16 / fp16 / fp32 / fp24 (0 * inf is NaN in the reference too)
+POISON_E4M3 = 448.0
+Q_SHARED = 3.0         # component 0 of every query of a poisoned case: a poison K row (POISON in component 0) scores
+                       # POISON * Q_SHARED * scale — thousands of nats — for EVERY query
+MASK_STRIDE = 4096     # the engine's mask_stride (max_positions)
+
+# The error bar of one output element: bar = sqrt(sum_k p_k^2 v_k^2) + |ref| — the size of the terms the kernel rounds (a uniform relative
+# perturbation of the numerators moves the output by about the first term, the output rounding by the second).  Two assertions:
+#     max(err / bar) < C_MAX * U_OUT          rms(err) / rms(bar) < C_RMS * U_OUT
+# The constants come from the REFERENCE, not from the kernels: attention_model() is a float64 restatement of the roundings each kernel
+# documents and nothing else —
+#   "flash"  (attention_kernel, attention_extend_kernel): softmax numerators exp(s - rowmax) rounded to the operand format before P.V,
+#            the row sum taken from the unrounded numerators, the normalised output rounded to the output format;
+#   "decode" (attention_decode_fused_kernel, bf16 and e4m3 caches): fp32 throughout, the output rounded —
+# run on the tests' own inputs; the constant is twice the model's largest ratio.  The factor 2 covers what the model leaves out: fp32
+# accumulation order, the hardware exponential, the deferred-maximum rescale (numerators up to e^8 before normalisation).
+# Model ratios in units of U_OUT — max(err / bar), rms(err) / rms(bar) — of attention_model() on the tests' own inputs (numpy on the CPU;
+# every check prints its own next to the kernel's):
+#                                                                        "flash"          "decode"
+#   tests/test_kernels_emu.py, test_extend_emu.py (T 17..330)            1.59   0.301     0.61   0.251
+#   the shapes of tests/test_gpu_kernels.py, 2 heads: T 577..1216        1.77   0.302     0.72   0.291
+#   the shapes of tests/test_gpu_extend.py, 2 heads: P 1215 / 2047       1.79   0.312
+#   the same test files at their full head counts (32 / 40 heads)        2.01   0.310     0.72   0.239
+#   (the maximum is taken over 16..20 times as many elements there: 2.01 at extend H 40, P 2047; flash T 1216: 1.77)
+# The kernels themselves, on the CPU emulator over the 2-head inputs: flash 1.94 / 0.314, extend 1.77 / 0.37 (needle inputs: the
+# deferred maximum keeps numerators up to e^8, which the model does not restate), decode 0.72 / 0.291 (equal to the model).
+# (The fp16-operand library shares these constants: its numerators are finer, except that fp16 flushes numerators below 6e-8, which the
+# model of the needle inputs shows as up to 3.37 u in single elements; the kernel, whose deferred maximum keeps them larger, measured 0.67 u.)
+# On the MI355X at full head counts: flash 1.89 / 0.312, extend 2.15 / 0.318 (bf16 library; 0.24 / 0.04 with fp16 operands),
+# decode 0.72 / 0.239 for bf16 and e4m3 caches (equal to the model to the digits printed).
+ATTN_MODEL_MEASURED = {
+    # kind: (largest model max-ratio, largest model rms-ratio) over all cases above
+    "flash": (2.01, 0.312),
+    "decode": (0.72, 0.291),
+}
+C_MAX = {kind: 2.0 * m for kind, (m, _) in ATTN_MODEL_MEASURED.items()}
+C_RMS = {kind: 2.0 * r for kind, (_, r) in ATTN_MODEL_MEASURED.items()}
+
+
+def _round_fmt(x, operands):
+    """float64 -> the nearest value of the 16-bit format (bf16, or IEEE fp16 for the fp16-operand library), float64"""
+    return _op_decode(_op_bits(np.asarray(x, dtype=np.float32), operands), operands).astype(np.float64)
+
+
+def attention_hidden(B, Tq, Tk, causal, q_pos0=0, key_mask=None):
+    """boolean [B, 1, Tq, Tk]: True where query t (at position q_pos0 + t) must not see the key — its future (causal) or a key the
+    mask hides (key_mask [B, >= Tk] bytes, 0 = hidden)"""
+    keys, qpos = np.arange(Tk)[None, :], q_pos0 + np.arange(Tq)[:, None]
+    h = np.zeros((B, 1, Tq, Tk), bool)
+    if causal:
+        h |= (keys > qpos)[None, None]
+    if key_mask is not None:
+        h |= (np.asarray(key_mask)[:, None, None, :Tk] == 0)
+    return h
+
+
+def attention_reference(q, k, v, scale, hidden):
+    """float64 softmax attention over the values the kernel was given (after operand rounding, e4m3 / fp24 decoding).
+    q [B,H,Tq,hd], k / v [B,H,Tk,hd], hidden boolean [B, 1 or H, Tq, Tk] -> ref [B,H,Tq,hd], p [B,H,Tq,Tk]"""
+    q, k, v = (np.asarray(a, dtype=np.float64) for a in (q, k, v))
+    s = np.matmul(q, k.transpose(0, 1, 3, 2)) * scale
+    s = np.where(hidden, -np.inf, s)
+    p = np.exp(s - s.max(-1, keepdims=True))
+    p /= p.sum(-1, keepdims=True)
+    return np.matmul(p, v), p
+
+
+def attention_model(q, k, v, scale, hidden, kind, operands="bf16"):
+    """float64 model of the kernel's documented roundings only (see C_MAX above)"""
+    q, k, v = (np.asarray(a, dtype=np.float64) for a in (q, k, v))
+    s = np.where(hidden, -np.inf, np.matmul(q, k.transpose(0, 1, 3, 2)) * scale)
+    e = np.exp(s - s.max(-1, keepdims=True))
+    l = e.sum(-1, keepdims=True)
+    if kind == "flash":
+        e = _round_fmt(e, operands)
+    return _round_fmt(np.matmul(e, v) / l, operands)
+
+
+def attention_judge(what, got, q, k, v, scale, hidden, kind, operands="bf16", tol_rel=None, tol_abs=0.0):
+    """got / q [B,H,Tq,hd], k / v [B,H,Tk,hd] (float64-able), hidden [B, 1 or H, Tq, Tk].  kind "flash" / "decode": the two signal-scaled
+    assertions; kind None: the fp32-class kernels — max|err| < tol_rel * max(1, max|ref|) + tol_abs, the tolerance those checks always had.
+    Works through the (b, head-chunk) slices so that a true shape's [Tq, Tk] planes stay small.  -> dict of the figures, ref"""
+    B, H, Tq, hd = q.shape
+    Tk = k.shape[2]
+    with_model = os.environ.get("VC_ATTN_MODEL", "1") != "0"
+    hc = max(1, min(H, (1 << 23) // max(1, Tq * Tk)))
+    ref = np.empty((B, H, Tq, hd))
+    mx = mmx = 0.0
+    se = sb = sm = 0.0
+    for b in range(B):
+        for h0 in range(0, H, hc):
+            sl = (slice(b, b + 1), slice(h0, h0 + hc))
+            hid = hidden[b:b + 1] if hidden.shape[1] == 1 else hidden[sl]
+            r, p = attention_reference(q[sl], k[sl], v[sl], scale, hid)
+            ref[sl] = r
+            if kind is None:
+                continue
+            bar = np.sqrt(np.matmul(p ** 2, np.asarray(v[sl], dtype=np.float64) ** 2)) + np.abs(r)
+            err = np.abs(np.asarray(got[sl], dtype=np.float64) - r)
+            merr = np.abs(attention_model(q[sl], k[sl], v[sl], scale, hid, kind, operands) - r) if with_model else np.zeros_like(r)
+            mx, mmx = max(mx, float((err / bar).max())), max(mmx, float((merr / bar).max()))
+            se, sb, sm = se + float((err ** 2).sum()), sb + float((bar ** 2).sum()), sm + float((merr ** 2).sum())
+    err_abs = float(np.abs(np.asarray(got, dtype=np.float64) - ref).max())
+    fig = {"abs": err_abs, "ref_max": float(np.abs(ref).max())}
+    if kind is None:
+        print(f"{what}: max|err| {err_abs:.3e} (max|ref| {fig['ref_max']:.3g})")
+        assert err_abs < tol_rel * max(1.0, fig["ref_max"]) + tol_abs, f"{what}: abs err {err_abs}"
+        return fig, ref
+    fig.update(max_u=mx / U_OUT, rms_u=math.sqrt(se / sb) / U_OUT, model_max_u=mmx / U_OUT, model_rms_u=math.sqrt(sm / sb) / U_OUT)
+    print(f"{what}: max(err/bar) {fig['max_u']:.2f} u, rms(err)/rms(bar) {fig['rms_u']:.3f} u   [model of the documented roundings: "
+          f"{fig['model_max_u']:.2f} u, {fig['model_rms_u']:.3f} u; bars {C_MAX[kind]:.2f} u, {C_RMS[kind]:.2f} u]   max|err| {err_abs:.3e}")
+    assert np.isfinite(np.asarray(got, dtype=np.float64)).all(), f"{what}: non-finite output (a value behind a limit was read)"
+    assert fig["max_u"] < C_MAX[kind], f"{what}: max(err / bar) = {fig['max_u']:.2f} u, bar {C_MAX[kind]:.2f} u"
+    assert fig["rms_u"] < C_RMS[kind], f"{what}: rms(err) / rms(bar) = {fig['rms_u']:.3f} u, bar {C_RMS[kind]:.2f} u"
+    return fig, ref
+
+
+# ---- key masks -------------------------------------------------------------------------------------------------------------------
+MASK_PATTERNS = ("ones", "pad1", "pad63", "pad64", "pad200", "tile", "straddle", "early", "singles")
+
+
+def mask_pattern(name, T, keep_last=False):
+    """visible[T] (uint8) of one pattern.  Key 0 is always visible; keep_last (decode: T = the row's position + 1) keeps key T - 1
+    visible as well — right padding then ends in front of it.  The patterns: right padding of 1 / 63 / 64 / 200 keys; a hidden run that
+    is exactly the 64-key tile 64..127 ("tile") or straddles two (63..128); keys 1..130 hidden ("early": the early causal queries see
+    key 0 alone); single hidden keys at 1, 63, 64 and the last one."""
+    m = np.ones(T, np.uint8)
+    end = T - 1 if keep_last else T
+    if name.startswith("pad"):
+        n = int(name[3:])
+        assert 1 <= end - n, f"mask pattern {name} does not fit {T} keys"
+        m[end - n:end] = 0
+    elif name in ("tile", "straddle", "early"):
+        lo, hi = {"tile": (64, 128), "straddle": (63, 129), "early": (1, 131)}[name]
+        assert hi < end, f"mask pattern {name} does not fit {T} keys"
+        m[lo:hi] = 0
+    elif name == "singles":
+        for key in (1, 63, 64, end - 1):
+            if 0 < key < end:
+                m[key] = 0
+    else:
+        assert name == "ones"
+    assert m[0] == 1 and (not keep_last or m[T - 1] == 1)
+    return m
+
+
+def key_masks(names, Ts, stride=MASK_STRIDE, keep_last=False):
+    """[B, stride] mask bytes: row b = pattern names[b] over its Ts[b] keys; the bytes behind them are 0 in the even rows and 1 in the
+    odd ones — they must not matter"""
+    km = np.zeros((len(names), stride), np.uint8)
+    for b, (name, T) in enumerate(zip(names, Ts)):
+        km[b, T:] = b & 1
+        km[b, :T] = mask_pattern(name, T, keep_last)
+    return km
+
+
+def _needle_keys(q, k, beta=None, first=1):
+    """the causal needle: key j = beta * q[j - 1] for j >= first .. — query j - 1 would score the key right behind its range far above
+    every key it may see (k [.., Tk, hd] is changed in place from row `first` on; q [.., Tq, hd] supplies rows 0 .. Tk - first - 1).
+    The hidden score is beta |q|^2 / sqrt(hd) ~ beta sqrt(hd), the visible needle-shaped keys score N(0, beta^2): beta 4 at hd 128
+    (about 48 nats against a maximum near 20: the least gap over 32 heads x 1216 queries was 8.2 nats at beta 2.5, so 13 here) and 8 at
+    hd 64, where |q|^2 spreads more;
+    _assert_needle holds every case to >= 10 nats."""
+    if beta is None:
+        beta = 4.0 if q.shape[-1] >= 128 else 8.0
+    n = k.shape[2] - first
+    k[:, :, first:] = beta * q[:, :, :n]
+
+
+def _assert_needle(q, k, scale, hidden, q_pos0, nats=10.0):
+    """precondition, float64: for every query t whose next key q_pos0 + t + 1 exists, that key scores >= `nats` above the best visible"""
+    q, k = np.asarray(q, dtype=np.float64), np.asarray(k, dtype=np.float64)
+    Tq, Tk = q.shape[2], k.shape[2]
+    nq = min(Tq, Tk - q_pos0 - 1)
+    s = np.matmul(q[:, :, :nq], k.transpose(0, 1, 3, 2)) * scale
+    vis = np.where(np.broadcast_to(hidden[:, :, :nq], s.shape), -np.inf, s).max(-1)
+    nxt = np.einsum("bhtd,bhtd->bht", q[:, :, :nq], k[:, :, q_pos0 + 1:q_pos0 + 1 + nq]) * scale
+    gap = float((nxt - vis).min())
+    assert gap >= nats, f"needle precondition: the next key scores only {gap:.1f} nats above the best visible one"
+    return gap
+
+
+def _assert_poison(q, k, scale, hidden, poison_row, nats=20.0):
+    """precondition, float64: a poison K row outscores every visible key of every query by >= `nats`"""
+    q, k = np.asarray(q, dtype=np.float64), np.asarray(k, dtype=np.float64)
+    s = np.matmul(q, k.transpose(0, 1, 3, 2)) * scale
+    vis = np.where(np.broadcast_to(hidden, s.shape), -np.inf, s).max(-1)
+    ps = np.einsum("bhtd,bhtd->bht", q, np.broadcast_to(np.asarray(poison_row, dtype=np.float64), q.shape)) * scale
+    gap = float((ps - vis).min())
+    assert gap >= nats, f"poison precondition: a poison key scores only {gap:.1f} nats above the best visible one"
+    return gap
+
+
+def _names_for(B, patterns):
+    return [patterns[b % len(patterns)] for b in range(B)]
+
+
+def check_attention_ex(be, B, H, T, hd, causal, patterns=None, needle=False, cap_pad=128, split=False, seed=0, beta=None):
+    """The flash kernel as the LLM prefill calls it (vck_attention_ex / vck_attention_split_ex): q_stride = T (the array ends behind
+    query T - 1), kv_stride = a cache capacity T + cap_pad, vt_stride = T rounded up to 64; K rows and V^T columns in [T, stride) hold
+    POISON; patterns (a list of MASK_PATTERNS names, row b takes patterns[b % len]): a key mask of stride MASK_STRIDE whose hidden keys
+    hold POISON too; needle (causal): key j = beta * q[j - 1].  bf16 / fp16 form: both signal-scaled assertions and the historical
+    2^-7 one; split form: its 3e-5."""
+    rng = np.random.RandomState(seed)
+    Ts, cap = (T + 63) // 64 * 64, T + cap_pad
+    scale = 1.0 / math.sqrt(hd)
+    q, k, v = (rng.randn(B, H, T, hd).astype(np.float32) for _ in range(3))
+    q[..., 0] = Q_SHARED
+    if needle:
+        assert causal
+        _needle_keys(q, k, beta)
+    km = key_masks(_names_for(B, patterns), [T] * B) if patterns else None
+    prow = np.zeros(hd, np.float32)
+    prow[0] = POISON
+    if km is not None:
+        for b in range(B):
+            k[b][:, km[b, :T] == 0], v[b][:, km[b, :T] == 0] = prow, POISON
+    kp = np.empty((B, H, cap, hd), np.float32)
+    kp[:, :, :T], kp[:, :, T:] = k, prow
+    vtp = np.full((B, H, hd, Ts), POISON, np.float32)
+    vtp[..., :T] = v.transpose(0, 1, 3, 2)
+    vtp = vtp[..., vt_key_pos(Ts)]
+    D = H * hd
+    what = f"attention{'_split' if split else ''}_ex B{B} H{H} T{T} hd{hd} causal{int(causal)} mask {patterns} needle{int(needle)} [{be.operands}]"
+    kmd = _u8_dev(be, km) if km is not None else None
+    if split:
+        planes = [[be.bf16(p_) for p_ in split_hi_lo(a)] for a in (q, kp, vtp)]
+        (qh, ql), (kh, kl), (vh, vl) = planes
+        used = [be.host_f32(h_).astype(np.float64) + be.host_f32(l_).astype(np.float64) for h_, l_ in planes]
+        ldo = 2 * D + 64
+        out = be.zeros((B * T, ldo), "bf16")
+        be.lib.vck_attention_split_ex(be.ptr(qh), be.ptr(ql), be.ptr(kh), be.ptr(kl), be.ptr(vh), be.ptr(vl), be.ptr(out), B, H, T, hd,
+                                      T, cap, Ts, int(causal), ctypes.c_float(scale), ldo, D, be.ptr(kmd), MASK_STRIDE, None)
+    else:
+        qd, kd, vd = be.bf16(q), be.bf16(kp), be.bf16(vtp)
+        used = [be.host_f32(a).astype(np.float64) for a in (qd, kd, vd)]
+        out = be.zeros((B * T, D), "bf16")
+        be.lib.vck_attention_ex(be.ptr(qd), be.ptr(kd), be.ptr(vd), be.ptr(out), B, H, T, hd, T, cap, Ts, int(causal),
+                                ctypes.c_float(scale), be.ptr(kmd), MASK_STRIDE, None)
+    q_u, k_u = used[0].reshape(B, H, T, hd), used[1].reshape(B, H, cap, hd)[:, :, :T]
+    inv = np.argsort(vt_key_pos(Ts))
+    v_u = used[2].reshape(B, H, hd, Ts)[..., inv][..., :T].transpose(0, 1, 3, 2)
+    hidden = attention_hidden(B, T, T, causal, 0, km)
+    if needle:
+        _assert_needle(q_u, k_u, scale, hidden, 0)
+    _assert_poison(q_u, k_u, scale, hidden, prow)
+    be.sync()
+    if split:
+        got = _split_value(be, out, D)
+    else:
+        got = be.host_f32(out).astype(np.float64)
+    got = got.reshape(B, T, H, hd).transpose(0, 2, 1, 3)
+    if split:
+        return attention_judge(what, got, q_u, k_u, v_u, scale, hidden, None, tol_rel=3e-5)[0]
+    fig, ref = attention_judge(what, got, q_u, k_u, v_u, scale, hidden, "flash", be.operands)
+    assert fig["abs"] < 2 ** -7 * max(1.0, fig["ref_max"]), f"{what}: abs err {fig['abs']}"
+    if patterns and "early" in patterns and causal:   # queries 1 .. 130 of an "early" row see key 0 alone: the output is v[0], rounded once
+        for b in [b_ for b_, n_ in enumerate(_names_for(B, patterns)) if n_ == "early"]:
+            assert np.array_equal(got[b, :, 1:131], np.broadcast_to(_round_fmt(v_u[b, :, :1], be.operands), got[b, :, 1:131].shape)), \
+                f"{what}: a query that sees key 0 alone did not return v[0]"
+    return fig
+
+
+def _rope64(x, cos, sin):
+    """rotate_half RoPE of [.., hd] rows in float64 from the fp32 tables' row (cos / sin [hd / 2])"""
+    half = x.shape[-1] // 2
+    a, b = x[..., :half].astype(np.float64), x[..., half:].astype(np.float64)
+    c, s = cos.astype(np.float64), sin.astype(np.float64)
+    return np.concatenate([a * c - b * s, b * c + a * s], -1)
+
+
+def check_attention_decode_masked(be, fmt, B, H, hd, pos, patterns, seed=0):
+    """vck_attention_decode_masked: the fused decode attention with a position and a key mask per row (mask_stride = MASK_STRIDE), one row
+    inactive, over the cache format fmt (0 bf16, 1 fp32, 2 fp24, 3 e4m3).  Cache rows behind a row's position and rows its mask hides
+    hold the largest finite magnitudes of the format, K aligned with the row's query.  bf16 / e4m3: the signal-scaled assertions
+    (kind "decode") and the historical 2^-7; fp32 / fp24: their 3e-5."""
+    rng = np.random.RandomState(seed)
+    D = H * hd
+    kv32 = fmt in (1, 2)
+    G = (8 if B <= 8 else (16 if B <= 16 else 32)) if kv32 else 0
+    poss = [max(1, pos - 13 * b) for b in range(B)]
+    S = (pos + 1 + 63) // 64 * 64 + 64
+    assert S <= MASK_STRIDE
+    scale = 1.0 / math.sqrt(hd)
+    cos, sin = rope_tables(S, hd)
+    qkv = rng.randn(B, 3 * D).astype(np.float32)
+    if not kv32:
+        qkv = _op_decode(_op_bits(bf16_round(qkv), be.operands), be.operands)
+    x = qkv.reshape(B, 3, H, hd)
+    big = POISON_E4M3 if fmt == 3 else POISON
+    k_old, v_old = rng.randn(B, H, S, hd).astype(np.float32), rng.randn(B, H, S, hd).astype(np.float32)
+    km = key_masks(_names_for(B, patterns), [p_ + 1 for p_ in poss], keep_last=True)
+    rq = np.empty((B, H, hd))
+    for b in range(B):
+        r = _rope64(x[b, 0], cos[poss[b]], sin[poss[b]])
+        rq[b] = r if kv32 else _round_fmt(r, be.operands)    # (the bf16 step rounds q after RoPE)
+        bad = np.ones(S, bool)
+        bad[:poss[b]] = km[b, :poss[b]] == 0
+        bad[poss[b]] = False                                  # the row the step appends
+        k_old[b][:, bad] = (big * np.where(rq[b] >= 0, 1.0, -1.0))[:, None, :]
+        v_old[b][:, bad] = big
+    enc = {0: lambda a: be.bf16(a), 1: lambda a: be.f32(a), 2: lambda a: _u8_dev(be, f24_pack(f24_round(a))),
+           3: lambda a: _u8_dev(be, e4m3_bytes(a))}[fmt]
+    dec = {0: lambda t: be.host_f32(t), 1: lambda t: be.host_f32(t), 2: lambda t: f24_unpack(_u8_host(be, t), hd),
+           3: lambda t: e4m3_from_bytes(_u8_host(be, t))}[fmt]
+    kd, vd = enc(k_old), enc(v_old)
+    k0, v0 = dec(kd).reshape(B, H, S, hd).copy(), dec(vd).reshape(B, H, S, hd).copy()
+    out = be.zeros((((B + G - 1) // G) * 2 * G, D) if kv32 else (B, D), "bf16")
+    qd, cd, sd, kmd = (be.f32(qkv) if kv32 else be.bf16(qkv)), be.f32(cos), be.f32(sin), _u8_dev(be, km)
+    inactive = B - 1 if B > 1 else -1
+    rows = np.zeros((B, 4), np.int32)
+    rows[:, 0], rows[:, 1] = 1, poss
+    if inactive >= 0:
+        rows[inactive, 0] = 0
+    rd = be.i32(rows)
+    be.lib.vck_attention_decode_masked(be.ptr(qd), be.ptr(kd), be.ptr(vd), be.ptr(out), B, H, hd, S, c_p(_addr(rd) + 4), 4, c_p(_addr(rd)),
+                                       be.ptr(cd), be.ptr(sd), ctypes.c_float(scale), fmt, G, be.ptr(kmd), MASK_STRIDE, None)
+    be.sync()
+    gk, gv, go = dec(kd).reshape(B, H, S, hd), dec(vd).reshape(B, H, S, hd), be.host_f32(out).astype(np.float64)
+    figs = []
+    for b in range(B):
+        pb = poss[b]
+        orow = ((b // G) * 2 * G + b % G) if kv32 else b
+        if b == inactive:
+            assert np.array_equal(gk[b], k0[b]) and np.array_equal(gv[b], v0[b]) and not go[orow].any()
+            continue
+        keep = np.ones(S, bool)
+        keep[pb] = False
+        assert np.array_equal(gk[b][:, keep], k0[b][:, keep]) and np.array_equal(gv[b][:, keep], v0[b][:, keep]), "a cache row other than the appended one changed"
+        vn = x[b, 2] if fmt == 1 else (f24_round(x[b, 2]) if fmt == 2 else (e4m3_round(x[b, 2]) if fmt == 3 else x[b, 2]))
+        assert np.array_equal(gv[b, :, pb], vn), "appended V row"
+        rk = _rope64(x[b, 1], cos[pb], sin[pb])
+        ktol = {0: 2 ** -7, 1: 1e-5, 2: 2.0 ** -16, 3: 2 ** -3}[fmt] * np.abs(rk).max()
+        assert np.abs(gk[b, :, pb] - rk).max() <= ktol, "appended K row"
+        hidden = attention_hidden(1, 1, pb + 1, False, 0, km[b:b + 1])
+        assert not hidden[0, 0, 0, 0] and not hidden[0, 0, 0, pb]
+        q_b, k_b, v_b = rq[b][None, :, None, :], gk[b:b + 1, :, :pb + 1], gv[b:b + 1, :, :pb + 1]
+        if hidden.any():
+            _assert_poison(q_b, k_b, scale, hidden, (big * np.where(rq[b] >= 0, 1.0, -1.0))[None, :, None, :])
+        got = (go[orow] + go[orow + G]) if kv32 else go[b]
+        what = f"attention_decode_masked fmt{fmt} row {b} of B{B} H{H} hd{hd} pos {pb} mask {_names_for(B, patterns)[b]} [{be.operands}]"
+        if kv32:
+            figs.append(attention_judge(what, got.reshape(1, H, 1, hd), q_b, k_b, v_b, scale, hidden, None, tol_rel=3e-5)[0])
+        else:
+            fig = attention_judge(what, got.reshape(1, H, 1, hd), q_b, k_b, v_b, scale, hidden, "decode", be.operands)[0]
+            assert fig["abs"] < 2 ** -7 * max(1.0, fig["ref_max"]), f"{what}: abs err {fig['abs']}"
+            figs.append(fig)
+    return figs
+
+
+def check_attention_f32_masked(be, B, H, T, hd, causal, patterns, needle=False, seed=0, beta=None):
+    """vck_attention_f32_masked (the strict path's attention over a padded batch): masked keys hold POISON; tolerance of check_attention_f32.
+    That tolerance (2e-6) is an fp32 figure for unit-normal scores: the kernel's fp32 score carries an error proportional to |s|, which the
+    exponential turns into a relative error of p.  With needle keys (scores up to 50 nats) the MI355X measured 1.7e-5 against a bound of
+    1.2e-5 at H 32 / T 1216 — fp32 arithmetic, not a boundary error — so the tests call this check without the needle; a mask or causal
+    error still meets POISON."""
+    rng = np.random.RandomState(seed)
+    scale = 1.0 / math.sqrt(hd)
+    q, k, v = (rng.randn(B, H, T, hd).astype(np.float32) for _ in range(3))
+    q[..., 0] = Q_SHARED
+    if needle:
+        _needle_keys(q, k, beta)
+    km = key_masks(_names_for(B, patterns), [T] * B)
+    prow = np.zeros(hd, np.float32)
+    prow[0] = POISON
+    for b in range(B):
+        k[b][:, km[b, :T] == 0], v[b][:, km[b, :T] == 0] = prow, POISON
+    hidden = attention_hidden(B, T, T, causal, 0, km)
+    if needle:
+        _assert_needle(q, k, scale, hidden, 0)
+    _assert_poison(q, k, scale, hidden, prow)
+    out = be.zeros((B * T, H * hd), "f32")
+    qd, kd, vd, kmd = be.f32(q), be.f32(k), be.f32(v), _u8_dev(be, km)
+    be.lib.vck_attention_f32_masked(be.ptr(qd), be.ptr(kd), be.ptr(vd), be.ptr(out), B, H, T, hd, T, T, int(causal), T, None,
+                                    ctypes.c_float(scale), be.ptr(kmd), MASK_STRIDE, None)
+    be.sync()
+    got = be.host_f32(out).astype(np.float64).reshape(B, T, H, hd).transpose(0, 2, 1, 3)
+    what = f"attention_f32_masked B{B} H{H} T{T} hd{hd} causal{int(causal)} mask {patterns}"
+    assert np.isfinite(got).all(), f"{what}: non-finite output"
+    fig, ref = attention_judge(what, got, q, k, v, scale, hidden, None, tol_rel=2e-6, tol_abs=2e-6)
+    return fig
+
+
+def check_attn_probs(be, qform, kform, B, H, T, hd, patterns, q_pos0=0, needle=False, seed=0, beta=None):
+    """vck_attn_probs (output_attentions) in the forms the engine uses: qform "f32" / "bf16" / "hilo", kform "f32" / "bf16" / "hilo" /
+    "e4m3" / "fp24"; T queries at positions q_pos0 + t over Tk = q_pos0 + T key columns (q_pos0 = 0: the prefill form, Tk passed as 0),
+    K rows of a cache of stride Tk + 72 whose tail holds POISON, masked keys too.  Against p of attention_reference element by element:
+    |got - p| <= p * (2 ds + 2^-20) + 1e-30, ds = hd * 2^-24 * max_key sum_d |q_d k_d| * scale the worst case of the kernel's fp32 FMA
+    chain over hd products (the softmax moves by at most twice the largest score error; 2^-20 for expf, the sum and the division);
+    hidden and future keys exactly 0; each row sums to 1 within 2^-18 (64-lane tree + Tk / 64 serial adds + the roundings above)."""
+    rng = np.random.RandomState(seed)
+    scale = 1.0 / math.sqrt(hd)
+    Tk, S = q_pos0 + T, q_pos0 + T + 72
+    q, k = rng.randn(B, H, T, hd).astype(np.float32), rng.randn(B, H, S, hd).astype(np.float32)
+    q[..., 0] = Q_SHARED
+    if needle:
+        _needle_keys(q, k[:, :, :Tk], beta, first=q_pos0 + 1)
+    big = POISON_E4M3 if kform == "e4m3" else POISON
+    km = key_masks(_names_for(B, patterns), [Tk] * B)
+    prow = np.zeros(hd, np.float32)
+    prow[0] = big
+    k[:, :, Tk:] = prow
+    for b in range(B):
+        k[b][:, :Tk][:, km[b, :Tk] == 0] = prow
+    ptr = dict(q32=None, q_hi=None, q_lo=None, k32=None, k_hi=None, k_lo=None, k24=None, k8=None)
+    hold = []
+
+    def operand(form, a, side):
+        if form == "f32":
+            d = be.f32(a)
+            ptr[side + "32"] = d
+            return a.astype(np.float64)
+        if form == "bf16":
+            d = be.bf16(a)
+            ptr[side + "_hi"] = d
+            return be.host_f32(d).astype(np.float64).reshape(a.shape)
+        if form == "hilo":
+            hi, lo = split_hi_lo(a)
+            dh, dl = be.bf16(hi), be.bf16(lo)
+            ptr[side + "_hi"], ptr[side + "_lo"] = dh, dl
+            return (be.host_f32(dh).astype(np.float64) + be.host_f32(dl).astype(np.float64)).reshape(a.shape)
+        if form == "e4m3":
+            ptr["k8"] = _u8_dev(be, e4m3_bytes(a))
+            return e4m3_round(a).astype(np.float64)
+        assert form == "fp24"
+        ptr["k24"] = _u8_dev(be, f24_pack(f24_round(a)))
+        return f24_round(a).astype(np.float64)
+
+    q_u, k_u = operand(qform, q, "q"), operand(kform, k, "k")[:, :, :Tk]
+    hidden = attention_hidden(B, T, Tk, True, q_pos0, km)
+    if needle:
+        _assert_needle(q_u, k_u, scale, hidden, q_pos0)
+    _assert_poison(q_u, k_u, scale, hidden, prow)
+    out = be.f32(np.full((B, H, T, Tk), np.nan, np.float32))
+    kmd = _u8_dev(be, km)
+    be.lib.vck_attn_probs(*(be.ptr(ptr[n]) for n in ("q32", "q_hi", "q_lo", "k32", "k_hi", "k_lo", "k24", "k8")), be.ptr(out), B, H, T, hd,
+                          T, S, ctypes.c_float(scale), 0 if q_pos0 == 0 else Tk, q_pos0, be.ptr(kmd), MASK_STRIDE, None)
+    be.sync()
+    got = be.host_f32(out).astype(np.float64).reshape(B, H, T, Tk)
+    what = f"attn_probs q {qform} k {kform} B{B} H{H} T{T} hd{hd} q_pos0 {q_pos0} mask {patterns}"
+    assert np.isfinite(got).all(), f"{what}: non-finite probability"
+    worst = 0.0
+    for b in range(B):
+        for h in range(H):
+            sl = (slice(b, b + 1), slice(h, h + 1))
+            _, p = attention_reference(q_u[sl], k_u[sl], np.zeros_like(k_u[sl]), scale, hidden[b:b + 1])
+            ds = hd * 2.0 ** -24 * scale * np.matmul(np.abs(q_u[sl]), np.abs(k_u[sl]).transpose(0, 1, 3, 2))
+            ds = np.where(hidden[b:b + 1], 0.0, ds).max(-1, keepdims=True)
+            g = got[sl]
+            assert not g[np.broadcast_to(hidden[b:b + 1], g.shape)].any(), f"{what}: a hidden or future key has a non-zero probability (b {b} h {h})"
+            tol = p * (2 * ds + 2.0 ** -20) + 1e-30
+            worst = max(worst, float((np.abs(g - p) / tol).max()))
+            assert (np.abs(g - p) <= tol).all(), f"{what}: probabilities differ (b {b} h {h}): max |got - p| {np.abs(g - p).max():.3e}, {worst:.2f} of the bound"
+            assert np.abs(g.sum(-1) - 1.0).max() < 2.0 ** -18, f"{what}: a row sums to 1 + {np.abs(g.sum(-1) - 1.0).max():.3e}"
+    print(f"{what}: max |got - p| / bound {worst:.3f}")
+    return worst

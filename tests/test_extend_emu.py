@@ -40,6 +40,16 @@ def test_attention_extend_kernel_key_mask(be, P, n, kv8):
     xc.check_attention_extend(be, 2, 2, P, n, kv8=kv8, masked=True, seed=P + n)
 
 
+@pytest.mark.parametrize("P,n", [(100, 17), (139, 65), (200, 130)])
+@pytest.mark.parametrize("kv8", [False, True])
+def test_attention_extend_kernel_needle_and_mask_patterns(be, P, n, kv8):
+    """chunk key P + t = 4 q[t - 1]: a query that sees one key too many is wrong in every element; poisoned hidden keys, a pattern per row"""
+    xc.check_attention_extend(be, 1, 2, P, n, kv8=kv8, needle=True, seed=P + n)
+    xc.check_attention_extend(be, 3, 1, P, n, kv8=kv8, needle=True, patterns=["straddle" if P + n > 130 else "singles", "pad63", "ones"], seed=P + n + 1)
+    if P + n > 200:
+        xc.check_attention_extend(be, 2, 1, P, n, kv8=kv8, needle=True, patterns=["pad200", "early"], seed=P + n + 2)
+
+
 def test_attention_extend_under_another_wave_order():
     """the kernel tests once more with the emulator's waves in another order and the dynamic-LDS race check on (as
     tests/test_emu_orders.py does for the other kernels)"""

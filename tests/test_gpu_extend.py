@@ -30,6 +30,16 @@ def test_attention_extend_key_mask(be):
     xc.check_attention_extend(be, 2, 32, 1215, 40, kv8=True, masked=True, seed=6)
 
 
+@pytest.mark.parametrize("H,P", [(32, 1215), (40, 2047)])
+@pytest.mark.parametrize("n", [33, 257])
+@pytest.mark.parametrize("kv8", [False, True])
+def test_attention_extend_needle(be, H, P, n, kv8):
+    """chunk key P + t = 4 q[t - 1]: one key too many for one query is an O(1) error in every element of its row; the second launch
+    under a key mask per batch row whose hidden keys hold the largest finite values of the cache format"""
+    xc.check_attention_extend(be, 1, H, P, n, kv8=kv8, needle=True, seed=P + n)
+    xc.check_attention_extend(be, 2, H, P, n, kv8=kv8, needle=True, patterns=["early", "pad200"], seed=P + n + 1)
+
+
 @pytest.mark.parametrize("fmt", ["bf16", "w8a16", "fp8"])
 @pytest.mark.parametrize("n", [5, 64, 65])
 def test_engine_extend_against_oracle(fmt, n):

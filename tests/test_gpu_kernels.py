@@ -187,6 +187,49 @@ def test_attention(be, B, H, T, hd, causal, spike):
     kc.check_attention(be, B, H, T, hd, causal, spike=spike)
 
 
+# ---- the attention kernels as the engine calls them (key masks, prefill strides, poison, needles) at the true shapes -----------------
+PAT_A = ["early", "pad200"]
+PAT_B = ["straddle", "ones"]
+
+
+@pytest.mark.parametrize("lib", ["bf16", "fp16"])
+def test_attention_ex_true_shapes(be, be16, lib):
+    b = be if lib == "bf16" else be16
+    kc.check_attention_ex(b, 2, 32, 1216, 128, True, PAT_A, True)                        # 7b prefill, 19 key tiles
+    kc.check_attention_ex(b, 2, 40, 1190, 128, True, ["tile", "pad63"], True, seed=1)   # 13b heads, S off the 64 grid
+    kc.check_attention_ex(b, 2, 32, 1216, 128, True, ["pad64", "singles"], False, seed=2)   # the diffuse bulk under a mask
+    kc.check_attention_ex(b, 2, 40, 1190, 128, True, None, True, seed=3)                # no mask: strides + poison alone, key T inside the last tile
+    kc.check_attention_ex(b, 3, 16, 577, 64, False, None, False, seed=5)                # the ViT form with the prefill's strides
+    kc.check_attention_ex(b, 3, 16, 577, 64, False, ["pad1", "straddle", "ones"], False, seed=4)   # the non-causal masked branch
+
+
+def test_attention_split_ex_true_shapes(be):
+    kc.check_attention_ex(be, 2, 8, 1216, 128, True, PAT_A, True, split=True, seed=5)
+
+
+@pytest.mark.parametrize("fmt", [0, 1, 2, 3])
+def test_attention_decode_masked_true_shapes(be, fmt):
+    kc.check_attention_decode_masked(be, fmt, 8, 32, 128, 1216, ["early", "pad200", "tile", "straddle", "singles", "pad63", "ones", "pad1"], seed=fmt)
+    kc.check_attention_decode_masked(be, fmt, 24, 32 if fmt in (0, 3) else 8, 128, 1300, list(kc.MASK_PATTERNS), seed=10 + fmt)   # the pool
+    kc.check_attention_decode_masked(be, fmt, 2, 4, 128, 4000, ["pad200", "early"], seed=20 + fmt)
+
+
+def test_attention_decode_masked_fp16_operand_library(be16):
+    kc.check_attention_decode_masked(be16, 0, 8, 32, 128, 1216, ["early", "pad200", "tile", "straddle", "singles", "pad63", "ones", "pad1"])
+    kc.check_attention_decode_masked(be16, 3, 8, 32, 128, 1216, ["early", "pad200", "tile", "straddle", "singles", "pad63", "ones", "pad1"], seed=1)
+
+
+def test_attention_f32_masked_and_attn_probs_true_shapes(be):
+    kc.check_attention_f32_masked(be, 2, 32, 1216, 128, True, PAT_A)
+    kc.check_attn_probs(be, "bf16", "bf16", 1, 32, 1216, 128, ["early"], needle=True)
+    kc.check_attn_probs(be, "hilo", "hilo", 1, 32, 1216, 128, ["straddle"], needle=True, seed=1)
+    kc.check_attn_probs(be, "f32", "f32", 2, 4, 1216, 128, ["pad200", "singles"], needle=True, seed=2)
+    for kform in ("bf16", "f32", "fp24", "e4m3"):
+        kc.check_attn_probs(be, "f32", kform, 2, 32, 1, 128, PAT_A, q_pos0=1216, seed=3)
+    for kform in ("bf16", "e4m3"):
+        kc.check_attn_probs(be, "bf16", kform, 2, 32, 33, 128, PAT_B, q_pos0=1215, needle=True, seed=4)
+
+
 def test_fused_decode_kernels(be):
     kc.check_gemv_norm_chain(be, 8, 4096, 12288)
     kc.check_gemv_norm_chain(be, 16, 5120, 1024, seed=1)

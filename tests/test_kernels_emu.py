@@ -147,6 +147,52 @@ def test_attention(be, B, H, T, hd, causal, spike):
     kc.check_attention(be, B, H, T, hd, causal, spike=spike)
 
 
+# ---- the attention kernels as the engine calls them: key masks, the prefill's strides, poison behind every limit, causal needles -------
+# (B, H, T, hd, causal, mask pattern per batch row, needle)
+ATTN_EX_CASES = [(3, 1, 330, 128, True, ["pad200", "early", "ones"], True), (2, 2, 200, 128, True, ["straddle", "pad63"], True),
+                 (4, 2, 150, 64, True, ["tile", "pad64", "singles", "pad1"], True),      # B H % 8 == 0: XCD-grouped order
+                 (2, 1, 70, 64, False, ["pad1", "singles"], False), (1, 2, 257, 128, False, ["straddle"], False),
+                 (1, 1, 192, 128, True, None, True), (1, 2, 129, 128, True, None, False),
+                 (2, 2, 150, 64, False, None, False)]    # no mask, non-causal, T off the 64 grid: key T sits inside the last tile
+
+
+@pytest.mark.parametrize("B,H,T,hd,causal,patterns,needle", ATTN_EX_CASES)
+def test_attention_ex(be, B, H, T, hd, causal, patterns, needle):
+    """vck_attention_ex: q_stride = T, kv_stride = T + 128, vt_stride = T rounded to 64, mask stride 4096"""
+    kc.check_attention_ex(be, B, H, T, hd, causal, patterns, needle, seed=T)
+
+
+def test_attention_ex_fp16_operand_library(be16):
+    kc.check_attention_ex(be16, 3, 1, 330, 128, True, ["pad200", "early", "ones"], True, seed=1)
+    kc.check_attention_ex(be16, 2, 2, 150, 64, False, ["tile", "pad1"], False, seed=2)
+    kc.check_attention(be16, 1, 2, 200, 128, True, spike=True)
+
+
+@pytest.mark.parametrize("fmt", [0, 1, 2, 3])
+def test_attention_decode_masked(be, fmt):
+    """the fused decode attention in its four cache formats with a position and a key mask per row, one row inactive"""
+    kc.check_attention_decode_masked(be, fmt, 5, 2, 128, 329, ["pad200", "early", "straddle", "ones", "pad1"], seed=fmt)
+    kc.check_attention_decode_masked(be, fmt, 4, 1, 64, 140, ["tile", "singles", "pad63", "pad64"], seed=10 + fmt)
+    kc.check_attention_decode_masked(be, fmt, 1, 1, 128, 70, ["pad1"], seed=20 + fmt)
+
+
+def test_attention_decode_masked_fp16_operand_library(be16):
+    kc.check_attention_decode_masked(be16, 0, 3, 1, 128, 200, ["early", "tile", "ones"], seed=1)
+    kc.check_attention_decode_masked(be16, 3, 3, 1, 128, 200, ["straddle", "pad64", "ones"], seed=2)
+
+
+def test_attention_f32_masked_and_attn_probs(be):
+    kc.check_attention_f32_masked(be, 3, 1, 200, 128, True, ["early", "pad63", "ones"])
+    kc.check_attention_f32_masked(be, 2, 2, 70, 64, False, ["singles", "pad1"])
+    kc.check_attn_probs(be, "f32", "f32", 2, 1, 200, 128, ["early", "ones"], needle=True)            # the strict prefill
+    kc.check_attn_probs(be, "bf16", "bf16", 3, 2, 150, 64, ["tile", "pad64", "singles"], needle=True, seed=1)   # the bf16 prefill
+    kc.check_attn_probs(be, "hilo", "hilo", 2, 1, 140, 128, ["straddle", "pad1"], needle=True, seed=2)   # the split prefill
+    for kform in ("bf16", "f32", "fp24", "e4m3"):    # a cached decode step: T = 1 at q_pos0, fp32 q
+        kc.check_attn_probs(be, "f32", kform, 3, 2, 1, 128, ["early", "pad63", "ones"], q_pos0=199, seed=3)
+    for kform in ("bf16", "e4m3"):                   # a continuation: n queries behind P cached keys
+        kc.check_attn_probs(be, "bf16", kform, 2, 1, 37, 128, ["tile", "singles"], q_pos0=150, needle=True, seed=4)
+
+
 def test_splice_greedy_synth(be):
     kc.check_splice(be, 256)
     kc.check_greedy(be, 3, 320)

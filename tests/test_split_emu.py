@@ -40,6 +40,10 @@ def test_split_attention_kernels(be):
     kc.check_qkv_split32_and_attention_split(be, 1, 2, 70, 128, True)
     kc.check_qkv_split32_and_attention_split(be, 2, 1, 130, 64, False, rope=False, seed=1)     # ViT form
     kc.check_qkv_split32_and_attention_split(be, 1, 1, 200, 128, True, seed=2, spike=True)     # late running-max jump
+    # the split prefill's strides (V^T scratch narrower than the cache), a key mask per row, poison behind every limit, the causal needle
+    kc.check_attention_ex(be, 3, 1, 330, 128, True, ["pad200", "early", "ones"], True, split=True, seed=3)
+    kc.check_attention_ex(be, 2, 1, 150, 64, False, ["tile", "pad63"], False, split=True, seed=4)
+    kc.check_attention_ex(be, 1, 2, 192, 128, True, None, True, split=True, seed=5)
     kc.check_attention_decode_kv32(be, 3, 2, 128, 140)
     kc.check_attention_decode_kv32(be, 10, 1, 64, 70, seed=1)                                  # two groups of G = 16? no: one group, G = 16
 

@@ -338,3 +338,50 @@ VCK_EXPORT void vck_attention_decode_kv24(const float* qkv, void* k, void* v, ui
     launch_attention_decode_fused(a, S(stream));
 }
 
+// ---- the attention kernels with the arguments the engine sets for a padded batch (key_mask / mask_stride) and for a prefill into a
+// ---- cache (vt_stride): thin wrappers over the same argument structs (tests; include/vcoder_kernels.h)
+VCK_EXPORT void vck_attention_ex(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* out, int B, int H, int T, int hd,
+                                 int q_stride, int kv_stride, int vt_stride, int causal, float scale, const uint8_t* key_mask,
+                                 int mask_stride, void* stream) {
+    AttnArgs a{q, k, vt, out, B, H, T, hd, q_stride, kv_stride, causal, scale, vt_stride};
+    a.key_mask = key_mask;
+    a.mask_stride = mask_stride;
+    launch_attention(a, S(stream));
+}
+VCK_EXPORT void vck_attention_split_ex(const uint16_t* q_hi, const uint16_t* q_lo, const uint16_t* k_hi, const uint16_t* k_lo,
+                                       const uint16_t* vt_hi, const uint16_t* vt_lo, uint16_t* out, int B, int H, int T, int hd,
+                                       int q_stride, int kv_stride, int vt_stride, int causal, float scale, int ldo, int lo_off,
+                                       const uint8_t* key_mask, int mask_stride, void* stream) {
+    AttnArgs a{q_hi, k_hi, vt_hi, out, B, H, T, hd, q_stride, kv_stride, causal, scale, vt_stride, q_lo, k_lo, vt_lo, ldo, lo_off};
+    a.key_mask = key_mask;
+    a.mask_stride = mask_stride;
+    launch_attention(a, S(stream));
+}
+/* the fused decode attention, per-row form, over any cache format (kv_format: 0 bf16, 1 fp32, 2 fp24, 3 e4m3; G: the output row
+ * groups of the fp32 / fp24 forms) with the rows' key masks */
+VCK_EXPORT void vck_attention_decode_masked(const void* qkv, void* k, void* v, uint16_t* out, int B, int H, int hd, int kv_stride,
+                                            const int* pos_rows, int pos_stride, const int* active_rows, const float* rope_cos,
+                                            const float* rope_sin, float scale, int kv_format, int G, const uint8_t* key_mask,
+                                            int mask_stride, void* stream) {
+    AttnDecodeFusedArgs a{reinterpret_cast<const uint16_t*>(qkv), reinterpret_cast<uint16_t*>(k), reinterpret_cast<uint16_t*>(v), out,
+                          B, H, hd, kv_stride, pos_rows, rope_cos, rope_sin, scale, pos_stride, active_rows, kv_format, G, key_mask,
+                          mask_stride};
+    launch_attention_decode_fused(a, S(stream));
+}
+VCK_EXPORT void vck_attention_f32_masked(const float* q, const float* k, const float* v, float* out, int B, int H, int Tq, int hd,
+                                         int q_stride, int kv_stride, int causal, int Tk, const int* pos0_dev, float scale,
+                                         const uint8_t* key_mask, int mask_stride, void* stream) {
+    AttnF32Args a{q, k, v, out, B, H, Tq, hd, q_stride, kv_stride, causal, Tk, pos0_dev, scale, key_mask, mask_stride};
+    launch_attention_f32(a, S(stream));
+}
+/* output_attentions: q as fp32 (q32) or bf16 hi [+ lo]; k as fp32 (k32), bf16 hi [+ lo], e4m3 rows (k8) or fp24 rows (k24) */
+VCK_EXPORT void vck_attn_probs(const float* q32, const uint16_t* q_hi, const uint16_t* q_lo, const float* k32, const uint16_t* k_hi,
+                               const uint16_t* k_lo, const void* k24, const uint8_t* k8, float* out, int B, int H, int T, int hd,
+                               int q_stride, int kv_stride, float scale, int Tk, int q_pos0, const uint8_t* key_mask,
+                               int mask_stride, void* stream) {
+    AttnProbsArgs a{};
+    a.q32 = q32; a.q_hi = q_hi; a.q_lo = q_lo; a.k32 = k32; a.k_hi = k_hi; a.k_lo = k_lo; a.k24 = k24; a.k8 = k8; a.out = out;
+    a.B = B; a.H = H; a.T = T; a.hd = hd; a.q_stride = q_stride; a.kv_stride = kv_stride; a.scale = scale;
+    a.key_mask = key_mask; a.mask_stride = mask_stride; a.Tk = Tk; a.q_pos0 = q_pos0;
+    launch_attn_probs(a, S(stream));
+}
