@@ -154,7 +154,7 @@ VC_API int vc_model_create_shared(vc_ctx* ctx, vc_model* parent, vc_model** out)
     m->st = ctx->stream;
     m->finalized = true;
     m->owns_weights = false;
-    m->root = parent->root ? parent->root : parent;
+    m->root = root_of(parent);
     m->weight_format = parent->weight_format;
     m->P = parent->P; m->Tv = parent->Tv; m->Kpatch = parent->Kpatch; m->Kpad = parent->Kpad;
     m->hd = parent->hd; m->vhd = parent->vhd; m->npart = parent->npart;
@@ -273,7 +273,7 @@ VC_API int vc_model_set_precision(vc_model* m, int mode) {
     if (mode == 2) {
         // split mode on a checkpoint with weight lo planes: its decode GEMV is the workgroup-shared form only — refuse HERE what
         // would otherwise surface as an exception out of a launch (possibly inside a graph capture) (ADVICE r5)
-        const vc_model* root = m->root ? m->root : m;
+        const vc_model* root = root_of(m);
         // (the e4m3 weight formats re-round the decoder linears and drop their lo planes: only K = hidden matrices keep one then)
         if (!root->lo_of.empty() && (!gemv_wg_enabled() || root->c.hidden % 64 != 0 || (root->weight_format == 0 && root->c.ffn % 64 != 0))) {
             m->ctx->err = std::string("precision mode split on a checkpoint with weight lo planes (fp16 / fp32 values) needs the workgroup-shared "
@@ -321,7 +321,7 @@ VC_API int vc_model_set_fp8_kv(vc_model* m, int on) {
  * already are), at the price of a short last round of tiles per GEMM (~2-4 % of a prefill).  Applies to all sessions of the model. */
 VC_API int vc_model_set_batch_invariant(vc_model* m, int on) {
     if (!m) return VC_ERR_INVALID;
-    (m->root ? m->root : m)->batch_invariant = on != 0;
+    root_of(m)->batch_invariant = on != 0;
     return VC_OK;
 }
 
@@ -332,7 +332,7 @@ VC_API int vc_model_set_batch_invariant(vc_model* m, int on) {
 VC_API int vc_model_set_qkv_fused(vc_model* m, int on) {
     if (!m) return VC_ERR_INVALID;
     if (on < 0 || on > 2) return VC_ERR_INVALID;
-    (m->root ? m->root : m)->qkv_fused = on;
+    root_of(m)->qkv_fused = on;
     return VC_OK;
 }
 
@@ -356,7 +356,7 @@ VC_API int vc_operand_format(void) { return VC_OPERAND_FP16; }
  * bits, exact for fp16), the bf16 fast path with the bf16-rounded weights alone. */
 VC_API int vc_model_inexact_tensors(vc_model* m) {
     if (!m) return VC_ERR_INVALID;
-    const vc_model* r = m->root ? m->root : m;
+    const vc_model* r = root_of(m);
     return (int)r->inexact_regions.size();
 }
 
@@ -743,7 +743,7 @@ void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* n
     if (m->precision == 1) {
         enqueue_decode_step_strict(m, B);
     } else if (m->hidden_out || m->attn_out) {
-        enqueue_decode_step_diag(m, session_view(m), B, m->cur_pos);
+        enqueue_decode_step(m, session_view(m), B, m->cur_pos);
     } else {
         ensure_graph(m, B);
         HIPCHK(hipGraphLaunch(m->graph, m->st));

@@ -5,8 +5,7 @@
 // GEMM helpers
 // vc_model_set_batch_invariant: no split-K remainder round (its slices — and so the order in which a row's k-blocks are summed —
 // depend on the number of output tiles, i.e. on how many rows share the launch)
-inline bool batch_invariant(const vc_model* m) { return (m->root ? m->root : m)->batch_invariant; }
-inline const vc_model* root_of(const vc_model* m) { return m->root ? m->root : m; }
+inline bool batch_invariant(const vc_model* m) { return root_of(m)->batch_invariant; }
 inline bool prefill_fold_on() {
     const char* e = getenv("VC_PREFILL_FOLD");
     return e && atoi(e) != 0;
@@ -29,16 +28,19 @@ static void apply_fold(GemmArgs& a, const NormFold* f) {
     a.xg_lo = f->xg_lo;
     a.npart = f->npart;
 }
+// the fp32 workspace of the GEMM's split-K remainder round: only problems with more than one round of tiles can use it
+static void attach_splitk_ws(vc_model* m, GemmArgs& a) {
+    if (batch_invariant(m) || (long)((a.M + 255) / 256) * ((a.N + 255) / 256) <= 256) return;
+    m->gemm_ws.ensure((size_t)64 << 20);
+    a.ws = m->gemm_ws.as<float>();
+    a.ws_bytes = m->gemm_ws.cap;
+}
 void gemm(vc_model* m, const bf16_t* A, const bf16_t* W, const float* bias, void* out, int M, int N, int K, int ldo,
           int epi, int lda = 0, const NormFold* fold = nullptr, const QkvEpiArgs* qe = nullptr) {
     GemmArgs a{A, W, bias, out, M, N, K, lda > 0 ? lda : K, K, ldo};
     apply_fold(a, fold);
     if (qe) a.qe = *qe;
-    if (!batch_invariant(m) && (long)((M + 255) / 256) * ((N + 255) / 256) > 256) {  // only problems with more than one round of tiles can use it
-        m->gemm_ws.ensure((size_t)64 << 20);
-        a.ws = m->gemm_ws.as<float>();
-        a.ws_bytes = m->gemm_ws.cap;
-    }
+    attach_splitk_ws(m, a);
     launch_gemm(a, epi, m->st);
 }
 // weight format 2 (W8A8 prefill): the token rows of A are quantised to e4m3 with per-row power-of-two scales, then
@@ -49,11 +51,7 @@ void gemm_f8(vc_model* m, const bf16_t* A, const uint8_t* Wq, const float* wscal
     if (A) launch_quant_act_rows(A, K, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, K, m->st);
     GemmArgs a{reinterpret_cast<const bf16_t*>(m->a8.p), reinterpret_cast<const bf16_t*>(Wq), nullptr, out, M, N, K, K, K, ldo};
     if (qe) a.qe = *qe;
-    if (!batch_invariant(m) && (long)((M + 255) / 256) * ((N + 255) / 256) > 256) {
-        m->gemm_ws.ensure((size_t)64 << 20);
-        a.ws = m->gemm_ws.as<float>();
-        a.ws_bytes = m->gemm_ws.cap;
-    }
+    attach_splitk_ws(m, a);
     a.f8 = 1;
     a.a_scale = m->a8_scale.as<float>();
     a.w_scale = wscale;
@@ -72,11 +70,7 @@ void gemm_split(vc_model* m, const bf16_t* A, const bf16_t* W, const float* bias
         a.w_lo_off = (long long)(reinterpret_cast<const char*>(Wl) - reinterpret_cast<const char*>(W));
     }
     apply_fold(a, fold);
-    if (!batch_invariant(m) && (long)((M + 255) / 256) * ((N + 255) / 256) > 256) {
-        m->gemm_ws.ensure((size_t)64 << 20);
-        a.ws = m->gemm_ws.as<float>();
-        a.ws_bytes = m->gemm_ws.cap;
-    }
+    attach_splitk_ws(m, a);
     launch_gemm(a, epi, m->st);
 }
 // row stride of a [hi | lo] operand of width K: padded like XN_PAD (2 K bf16 is a power-of-two stride at K = 4096)
@@ -101,7 +95,7 @@ inline int split_kv_es() {
 // the bytes of the e4m3 weights otherwise); vc_model_set_fp8_kv(m, 0) keeps bf16 rows (root model's setting, before finalize)
 // bytes per KV element of the bf16-step modes (precision 0) of a model
 inline int step_kv_es(const vc_model* m) {
-    const vc_model* r = m->root ? m->root : m;
+    const vc_model* r = root_of(m);
     return (r->weight_format == 2 && r->fp8_kv) ? 1 : 2;
 }
 

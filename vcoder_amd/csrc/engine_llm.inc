@@ -192,21 +192,15 @@ struct KvTarget {
     int capR, capS, row0;
     int es;  // bytes per element: 2 (bf16); precision mode "split": 3 (fp24) or 4 (fp32)
 };
-// layer l of a cache whose elements are `es` bytes (the pointer type is nominal for es == 4)
-bf16_t* kv_layer(bf16_t* base, int es, size_t elems) { return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(base) + elems * es); }
-bf16_t* kcache(const vc_model* m, const KvTarget& t, int l) {
-    return kv_layer(t.kc, t.es, ((size_t)l * t.capR + t.row0) * m->c.heads * t.capS * m->hd);
+// row t.row0 of layer l of a cache whose elements are t.es bytes (the pointer type is nominal for es != 2)
+bf16_t* kv_layer(const vc_model* m, bf16_t* base, const KvTarget& t, int l) {
+    const size_t elems = ((size_t)l * t.capR + t.row0) * m->c.heads * t.capS * m->hd;
+    return reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(base) + elems * t.es);
 }
-bf16_t* vcache(const vc_model* m, const KvTarget& t, int l) {
-    return kv_layer(t.vc, t.es, ((size_t)l * t.capR + t.row0) * m->c.heads * t.capS * m->hd);
-}
+bf16_t* kcache(const vc_model* m, const KvTarget& t, int l) { return kv_layer(m, t.kc, t, l); }
+bf16_t* vcache(const vc_model* m, const KvTarget& t, int l) { return kv_layer(m, t.vc, t, l); }
 KvTarget session_kv(vc_model* m) { return KvTarget{m->kc.as<bf16_t>(), m->vc.as<bf16_t>(), m->capB, m->capS, 0, m->kv_es}; }
-bf16_t* kcache(const LoopView& v, const vc_model* m, int l) {
-    return kv_layer(v.kc, v.es, (size_t)l * v.capR * m->c.heads * v.capS * m->hd);
-}
-bf16_t* vcache(const LoopView& v, const vc_model* m, int l) {
-    return kv_layer(v.vc, v.es, (size_t)l * v.capR * m->c.heads * v.capS * m->hd);
-}
+KvTarget loop_kv(const LoopView& v) { return KvTarget{v.kc, v.vc, v.capR, v.capS, 0, v.es}; }   // all rows of a loop's cache
 
 // The decode loop outran the cache (a host-driven vc_decode_step loop past the reserve of its prefill): re-allocate with
 // room for `need` positions and move the live prefix — K and V rows are contiguous per (layer, sample, head), so each is
@@ -268,10 +262,83 @@ void emit_hidden(vc_model* m, int idx, int B, int S, const float* x_src) {
     HIPCHK(hipMemcpyAsync(m->hidden_out + (size_t)idx * n, src, n * 4, hipMemcpyDeviceToHost, m->st));
 }
 
+// ---- the linears of a decoder layer around its attention, stated once for the prefill and vc_extend ------------------------------
+// Folded RMSNorm of a prefill (VC_PREFILL_FOLD, see run_prefill_layers): the arguments of the GEMMs that produce xg / consume
+// 1/rms, and whether xn already holds bf16(x * g) of the CURRENT x for the norm about to be consumed (rstd: its row scales)
+struct FoldRun {
+    bool on = false;
+    NormFold prod, cons;
+    bool have_xg = false;
+};
+FoldRun fold_run(vc_model* m, bool on, int ld_xg, int xg_lo) {
+    FoldRun fr;
+    fr.on = on;
+    fr.prod = NormFold{nullptr, m->xn.as<bf16_t>(), nullptr, m->p_ssq.as<float>(), ld_xg, xg_lo, m->npart};
+    fr.cons = NormFold{m->p_rstd.as<float>()};
+    return fr;
+}
+// the unfused QKV projection of precision mode 0 over the M rows of m->x: RMSNorm -> GEMM into m->qkv [M, 3D] (fp8 format: the
+// norm writes the e4m3 operand of the GEMM directly).  With `qe` the GEMM runs the fused epilogue instead (EPI_QKV: no [M, 3D]
+// rows; its token rows are the samples padded to Tp).
+void qkv_projection(vc_model* m, const LlmLayer& L, int M, const FoldRun& fr, const QkvEpiArgs* qe = nullptr) {
+    const vc_model_cfg& c = m->c;
+    const int D = c.hidden, Mg = qe ? qe->B * qe->Tp : M, ldo = qe ? 0 : 3 * D, epi = qe ? EPI_QKV : EPI_BF16;
+    void* out = qe ? nullptr : m->qkv.p;
+    if (m->weight_format == 2) {
+        launch_rmsnorm_q8(m->x.as<float>(), L.in_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
+        gemm_f8(m, nullptr, L.qkv_q, L.qkv_s, out, Mg, 3 * D, D, ldo, epi, qe);
+    } else {
+        if (!fr.have_xg) launch_rmsnorm(m->x.as<float>(), L.in_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD);
+        gemm(m, m->xn.as<bf16_t>(), L.qkv_w, nullptr, out, Mg, 3 * D, D, ldo, epi, D + XN_PAD, fr.have_xg ? &fr.cons : nullptr, qe);
+    }
+}
+// The tail of a decoder layer behind its attention: o_proj (+ residual) -> post norm -> gate / up (SwiGLU) -> down (+ residual)
+// over the M rows of m->x, on bf16-valued operands m->attn / m->xn / m->h with row strides ld_attn / ld_xn / ld_h.
+//   mm(A, lda, W, out, N, K, ldo, epi, lo_off, fold): the mode's GEMM wrapper (lo_off: gemm_split's split_out)
+//   norm(w): the mode's RMSNorm pass m->x -> m->xn
+// Folded (fr.on): no norm pass — o_proj and down also write xg for the next GEMM and the rows' sum-of-squares partials, a
+// one-wave-per-row launch turns them into 1/rms; next_in: the norm the layer's output meets next (nullptr: the last layer's
+// output meets the final norm on its gathered rows only).
+struct TailLd { int attn, xn, h, h_lo; };
+template <class Gemm, class Norm>
+void layer_tail_on(vc_model* m, const LlmLayer& L, int M, const TailLd& ld, Gemm&& mm, Norm&& norm, FoldRun& fr, const float* next_in) {
+    const vc_model_cfg& c = m->c;
+    const int D = c.hidden, F = c.ffn;
+    NormFold* prod = fr.on ? &fr.prod : nullptr;
+    auto rstd = [&] { launch_rstd_from_partials(prod->ssq_out, m->npart, D / 16, m->p_rstd.as<float>(), M, D, c.rms_eps, m->st); };
+    if (prod) prod->xg_w = L.post_norm;
+    mm(m->attn.as<bf16_t>(), ld.attn, L.o_w, m->x.p, D, D, D, EPI_RESID_F32, 0, prod);
+    if (prod) rstd();
+    else norm(L.post_norm);
+    mm(m->xn.as<bf16_t>(), ld.xn, L.gu_w, m->h.p, 2 * F, D, ld.h, EPI_SWIGLU, ld.h_lo, prod ? &fr.cons : nullptr);
+    fr.have_xg = prod && next_in;
+    if (prod) prod->xg_w = next_in;
+    mm(m->h.as<bf16_t>(), ld.h, L.down_w, m->x.p, D, F, D, EPI_RESID_F32, 0, fr.have_xg ? prod : nullptr);
+    if (fr.have_xg) rstd();
+}
+// ... of precision mode 0: bf16 weights, or the fp8 format's W8A8 GEMMs (never folded)
+void layer_tail(vc_model* m, const LlmLayer& L, int M, FoldRun& fr, const float* next_in) {
+    const vc_model_cfg& c = m->c;
+    const int D = c.hidden, F = c.ffn;
+    if (m->weight_format == 2) {
+        gemm_f8(m, m->attn.as<bf16_t>(), L.o_q, L.o_s, m->x.p, M, D, D, D, EPI_RESID_F32);
+        launch_rmsnorm_q8(m->x.as<float>(), L.post_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
+        gemm_f8(m, nullptr, L.gu_q, L.gu_s, m->h.p, M, 2 * F, D, F, EPI_SWIGLU);
+        gemm_f8(m, m->h.as<bf16_t>(), L.down_q, L.down_s, m->x.p, M, D, F, D, EPI_RESID_F32);
+        return;
+    }
+    layer_tail_on(
+        m, L, M, TailLd{D, D + XN_PAD, F, 0},
+        [&](const bf16_t* A, int lda, const bf16_t* W, void* out, int N, int K, int ldo, int epi, int, const NormFold* fold) {
+            gemm(m, A, W, nullptr, out, M, N, K, ldo, epi, lda, fold);
+        },
+        [&](const float* w) { launch_rmsnorm(m->x.as<float>(), w, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD); }, fr, next_in);
+}
+
 // decoder layers [l0, l1) of a prefill (l1 < 0: all, or the first layer_limit)
 void run_prefill_layers(vc_model* m, const KvTarget& kv, int B, int S, int l0 = 0, int l1 = -1) {
     const vc_model_cfg& c = m->c;
-    const int D = c.hidden, F = c.ffn, H = c.heads, M = B * S;
+    const int D = c.hidden, H = c.heads, M = B * S;
     const int nl = l1 >= 0 ? l1 : (m->layer_limit > 0 ? std::min(m->layer_limit, c.layers) : c.layers);
     const int Sr = (int)rup(S, 64);
     m->vt_pre.ensure((size_t)B * H * m->hd * Sr * 2, true);
@@ -283,11 +350,7 @@ void run_prefill_layers(vc_model* m, const KvTarget& kv, int B, int S, int l0 = 
     // layer's QKV) scales its accumulator by it: the decode steps' form (DESIGN.md section 2).  Measured on MI355X (7b, B = 8,
     // profiles/r04_d_*): 112.9 ms per prefill against 111.6 with the 63 passes — the residual GEMMs' epilogue (8-byte bf16
     // stores in 32-byte segments, partials) costs more than the 45-us passes it removes — so the passes stay the default.
-    const bool fold = prefill_fold_on() && !f8;
-    float* rstd = m->p_rstd.as<float>();
-    NormFold prod{nullptr, m->xn.as<bf16_t>(), nullptr, m->p_ssq.as<float>(), D + XN_PAD, 0, m->npart};
-    const NormFold cons{rstd};
-    bool have_xg = false;   // xn holds bf16(x * g) of the CURRENT x for the norm about to be consumed, rstd its row scales
+    FoldRun fr = fold_run(m, prefill_fold_on() && !f8, D + XN_PAD, 0);
     // the fused QKV epilogue: hd 128, two heads per 256-row weight tile, a problem the 256 x 256 kernel serves anyway
     const int qf = root_of(m)->qkv_fused;
     const bool qkv_fused = qf && m->hd == 128 && D % 256 == 0 && (qf > 1 || (long)B * rup(S, 32) >= 1024);
@@ -309,21 +372,9 @@ void run_prefill_layers(vc_model* m, const KvTarget& kv, int B, int S, int l0 = 
                           kv8 ? reinterpret_cast<uint8_t*>(kcache(m, kv, l)) : nullptr,
                           kv8 ? reinterpret_cast<uint8_t*>(vcache(m, kv, l)) : nullptr, m->rope_cos, m->rope_sin, B, S, Sp, H, S,
                           kflash_stride, Sr, kv.capS};
-            if (f8) {
-                launch_rmsnorm_q8(m->x.as<float>(), L.in_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
-                gemm_f8(m, nullptr, L.qkv_q, L.qkv_s, nullptr, B * Sp, 3 * D, D, 0, EPI_QKV, &qe);
-            } else {
-                if (!have_xg) launch_rmsnorm(m->x.as<float>(), L.in_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD);
-                gemm(m, m->xn.as<bf16_t>(), L.qkv_w, nullptr, nullptr, B * Sp, 3 * D, D, 0, EPI_QKV, D + XN_PAD, have_xg ? &cons : nullptr, &qe);
-            }
+            qkv_projection(m, L, M, fr, &qe);
         } else {
-            if (f8) {  // RMSNorm writes the e4m3 operand of the QKV GEMM directly
-                launch_rmsnorm_q8(m->x.as<float>(), L.in_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
-                gemm_f8(m, nullptr, L.qkv_q, L.qkv_s, m->qkv.p, M, 3 * D, D, 3 * D, EPI_BF16);
-            } else {
-                if (!have_xg) launch_rmsnorm(m->x.as<float>(), L.in_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD);
-                gemm(m, m->xn.as<bf16_t>(), L.qkv_w, nullptr, m->qkv.p, M, 3 * D, D, 3 * D, EPI_BF16, D + XN_PAD, have_xg ? &cons : nullptr);
-            }
+            qkv_projection(m, L, M, fr);
             QkvSplitArgs qa{m->qkv.as<bf16_t>(), m->q.as<bf16_t>(), kflash, m->vt_pre.as<bf16_t>(), B, S, H, m->hd, S, kflash_stride,
                             nullptr, m->rope_cos, m->rope_sin, kv8 ? nullptr : vcache(m, kv, l), Sr,
                             kv8 ? reinterpret_cast<uint8_t*>(kcache(m, kv, l)) : nullptr,
@@ -332,10 +383,7 @@ void run_prefill_layers(vc_model* m, const KvTarget& kv, int B, int S, int l0 = 
         }
         AttnArgs aa{m->q.as<bf16_t>(), kflash, m->vt_pre.as<bf16_t>(), m->attn.as<bf16_t>(), B, H, S, m->hd, S, kflash_stride, 1,
                     1.0f / sqrtf((float)m->hd), Sr};
-        if (m->has_kmask) {
-            aa.key_mask = m->kmask.as<uint8_t>();
-            aa.mask_stride = c.max_positions;
-        }
+        attach_kmask(m, aa, m->has_kmask);
         launch_attention(aa, m->st);
         if (m->attn_out) {
             AttnProbsArgs pa{};
@@ -345,26 +393,7 @@ void run_prefill_layers(vc_model* m, const KvTarget& kv, int B, int S, int l0 = 
             pa.kv_stride = kflash_stride;
             emit_attentions(m, l, B, S, pa);
         }
-        if (f8) {
-            gemm_f8(m, m->attn.as<bf16_t>(), L.o_q, L.o_s, m->x.p, M, D, D, D, EPI_RESID_F32);
-            launch_rmsnorm_q8(m->x.as<float>(), L.post_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
-            gemm_f8(m, nullptr, L.gu_q, L.gu_s, m->h.p, M, 2 * F, D, F, EPI_SWIGLU);
-            gemm_f8(m, m->h.as<bf16_t>(), L.down_q, L.down_s, m->x.p, M, D, F, D, EPI_RESID_F32);
-        } else if (fold) {
-            prod.xg_w = L.post_norm;
-            gemm(m, m->attn.as<bf16_t>(), L.o_w, nullptr, m->x.p, M, D, D, D, EPI_RESID_F32, 0, &prod);
-            launch_rstd_from_partials(prod.ssq_out, m->npart, D / 16, rstd, M, D, c.rms_eps, m->st);
-            gemm(m, m->xn.as<bf16_t>(), L.gu_w, nullptr, m->h.p, M, 2 * F, D, F, EPI_SWIGLU, D + XN_PAD, &cons);
-            have_xg = l + 1 < nl;   // the last layer's output meets the final norm on its gathered rows only
-            prod.xg_w = have_xg ? m->llm[l + 1].in_norm : nullptr;
-            gemm(m, m->h.as<bf16_t>(), L.down_w, nullptr, m->x.p, M, D, F, D, EPI_RESID_F32, 0, have_xg ? &prod : nullptr);
-            if (have_xg) launch_rstd_from_partials(prod.ssq_out, m->npart, D / 16, rstd, M, D, c.rms_eps, m->st);
-        } else {
-            gemm(m, m->attn.as<bf16_t>(), L.o_w, nullptr, m->x.p, M, D, D, D, EPI_RESID_F32);
-            launch_rmsnorm(m->x.as<float>(), L.post_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD);
-            gemm(m, m->xn.as<bf16_t>(), L.gu_w, nullptr, m->h.p, M, 2 * F, D, F, EPI_SWIGLU, D + XN_PAD);
-            gemm(m, m->h.as<bf16_t>(), L.down_w, nullptr, m->x.p, M, D, F, D, EPI_RESID_F32);
-        }
+        layer_tail(m, L, M, fr, l + 1 < nl ? m->llm[l + 1].in_norm : nullptr);
         emit_hidden(m, l + 1, B, S);
     }
 }
@@ -387,25 +416,22 @@ void run_prefill_layers_split(vc_model* m, const KvTarget& kv, int B, int S, int
     m->h.ensure((size_t)M * ldh * 2);
     bf16_t *qh = m->q.as<bf16_t>(), *kh = m->vt_pre.as<bf16_t>(), *vh = kh + 2 * kplane;
     // folded RMSNorm as in run_prefill_layers (opt-in): the producer writes both planes of xg ([hi | lo], the lo plane D columns right)
-    const bool fold_on = prefill_fold_on();
-    float* rstd = m->p_rstd.as<float>();
-    NormFold prod{nullptr, m->xn.as<bf16_t>(), nullptr, m->p_ssq.as<float>(), ldx, D, m->npart};
-    const NormFold cons{rstd};
-    bool have_xg = false;
+    FoldRun fr = fold_run(m, prefill_fold_on(), ldx, D);
+    auto mm = [&](const bf16_t* A, int lda, const bf16_t* W, void* out, int N, int K, int ldo, int epi, int lo_off, const NormFold* fold) {
+        gemm_split(m, A, W, nullptr, out, M, N, K, ldo, epi, lda, lo_off, fold);
+    };
+    auto norm = [&](const float* w) { launch_rmsnorm_split(m->x.as<float>(), nullptr, w, m->xn.as<bf16_t>(), M, D, c.rms_eps, ldx, D, m->st); };
     for (int l = l0; l < nl; ++l) {
         const LlmLayer& L = m->llm[l];
-        if (!have_xg) launch_rmsnorm_split(m->x.as<float>(), nullptr, L.in_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, ldx, D, m->st);
-        gemm_split(m, m->xn.as<bf16_t>(), L.qkv_w, nullptr, m->s_qkv.p, M, 3 * D, D, 3 * D, EPI_F32, ldx, 0, have_xg ? &cons : nullptr);
+        if (!fr.have_xg) norm(L.in_norm);
+        mm(m->xn.as<bf16_t>(), ldx, L.qkv_w, m->s_qkv.p, 3 * D, D, 3 * D, EPI_F32, 0, fr.have_xg ? &fr.cons : nullptr);
         QkvSplit32Args qa{m->s_qkv.as<float>(), qh, qh + qplane, kh, kh + kplane, vh, vh + kplane,
                           reinterpret_cast<float*>(kcache(m, kv, l)), reinterpret_cast<float*>(vcache(m, kv, l)),
                           B, S, H, m->hd, S, Sr, Sr, kv.capS, m->rope_cos, m->rope_sin, kv.es == 3};
         launch_qkv_split32(qa, m->st);
         AttnArgs aa{qh, kh, vh, m->attn.as<bf16_t>(), B, H, S, m->hd, S, Sr, 1, 1.0f / sqrtf((float)m->hd), Sr,
                     qh + qplane, kh + kplane, vh + kplane, ldx, D};
-        if (m->has_kmask) {
-            aa.key_mask = m->kmask.as<uint8_t>();
-            aa.mask_stride = c.max_positions;
-        }
+        attach_kmask(m, aa, m->has_kmask);
         launch_attention(aa, m->st);
         if (m->attn_out) {
             AttnProbsArgs pa{};
@@ -417,21 +443,7 @@ void run_prefill_layers_split(vc_model* m, const KvTarget& kv, int B, int S, int
             pa.kv_stride = Sr;
             emit_attentions(m, l, B, S, pa);
         }
-        if (fold_on) {
-            prod.xg_w = L.post_norm;
-            gemm_split(m, m->attn.as<bf16_t>(), L.o_w, nullptr, m->x.p, M, D, D, D, EPI_RESID_F32, ldx, 0, &prod);
-            launch_rstd_from_partials(prod.ssq_out, m->npart, D / 16, rstd, M, D, c.rms_eps, m->st);
-            gemm_split(m, m->xn.as<bf16_t>(), L.gu_w, nullptr, m->h.p, M, 2 * F, D, ldh, EPI_SWIGLU, ldx, F, &cons);
-            have_xg = l + 1 < nl;
-            prod.xg_w = have_xg ? m->llm[l + 1].in_norm : nullptr;
-            gemm_split(m, m->h.as<bf16_t>(), L.down_w, nullptr, m->x.p, M, D, F, D, EPI_RESID_F32, ldh, 0, have_xg ? &prod : nullptr);
-            if (have_xg) launch_rstd_from_partials(prod.ssq_out, m->npart, D / 16, rstd, M, D, c.rms_eps, m->st);
-        } else {
-            gemm_split(m, m->attn.as<bf16_t>(), L.o_w, nullptr, m->x.p, M, D, D, D, EPI_RESID_F32, ldx);
-            launch_rmsnorm_split(m->x.as<float>(), nullptr, L.post_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, ldx, D, m->st);
-            gemm_split(m, m->xn.as<bf16_t>(), L.gu_w, nullptr, m->h.p, M, 2 * F, D, ldh, EPI_SWIGLU, ldx, F);
-            gemm_split(m, m->h.as<bf16_t>(), L.down_w, nullptr, m->x.p, M, D, F, D, EPI_RESID_F32, ldh);
-        }
+        layer_tail_on(m, L, M, TailLd{ldx, ldx, ldh, F}, mm, norm, fr, l + 1 < nl ? m->llm[l + 1].in_norm : nullptr);
         emit_hidden(m, l + 1, B, S);
     }
 }
@@ -462,51 +474,57 @@ SelectArgs select_args(vc_model* m, const LoopView& v, const float* logits, int 
     return a;
 }
 
-void enqueue_decode_step(vc_model* m, const LoopView& v, int nrows) {
-    decode_linears(m, v, nrows, [&](int l) {
-        AttnDecodeFusedArgs da{v.qkv_dec, kcache(v, m, l), vcache(v, m, l), v.attn_dec, nrows, m->c.heads, m->hd, v.capS,
-                               v.rows + RS_POS, m->rope_cos, m->rope_sin, 1.0f / sqrtf((float)m->hd), RS_STRIDE,
-                               v.rows + RS_ACTIVE, v.split_G ? (v.es == 3 ? 2 : 1) : (v.es == 1 ? 3 : 0), v.split_G, v.kmask, v.kmask_stride};
-        da.stamp = next_stamp(v);
-        launch_attention_decode_fused(da, v.st);
-    });
+// the fused decode attention of layer l of a step over the first `nrows` rows of a loop
+AttnDecodeFusedArgs decode_attn_args(const vc_model* m, const LoopView& v, int l, int nrows) {
+    const KvTarget kv = loop_kv(v);
+    // AttnDecodeFusedArgs::kv32: the split step over fp24 / fp32 rows, the bf16 step over e4m3 / bf16 rows
+    const int cache_format = v.split_G ? (v.es == 3 ? 2 : 1) : (v.es == 1 ? 3 : 0);
+    AttnDecodeFusedArgs da{v.qkv_dec, kcache(m, kv, l), vcache(m, kv, l), v.attn_dec, nrows, m->c.heads, m->hd, v.capS,
+                           v.rows + RS_POS, m->rope_cos, m->rope_sin, 1.0f / sqrtf((float)m->hd), RS_STRIDE,
+                           v.rows + RS_ACTIVE, cache_format, v.split_G, v.kmask, v.kmask_stride};
+    return da;
+}
+
+// hook_pos >= 0 (the rows' position): the same step run eagerly and unstamped with the output_hidden_states / output_attentions
+// hooks of a cached decode step (vc_request_hidden_states / vc_request_attentions before vc_decode_step): inputs_embeds row, every
+// layer's residual row, the final norm; and per layer the probabilities of the new token's query over the pos + 1 keys, recomputed
+// from the step's own roped q (rounded as the fused kernel rounds it) and the K cache — the fused decode attention keeps only
+// unnormalised scores.
+void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_pos = -1) {
+    const vc_model_cfg& c = m->c;
+    const bool hooks = hook_pos >= 0;
+    LoopView v = view;
+    if (hooks) v.stamps = nullptr;   // next_stamp(v) == nullptr for every launch
+    if (hooks) emit_hidden(m, 0, nrows, 1, v.x_dec);
+    decode_linears(
+        m, v, nrows,
+        [&](int l) {
+            AttnDecodeFusedArgs da = decode_attn_args(m, v, l, nrows);
+            da.stamp = next_stamp(v);
+            launch_attention_decode_fused(da, v.st);
+            if (hooks && m->attn_out) {
+                m->attn_q.ensure((size_t)nrows * c.hidden * 4);
+                launch_rope_q_decode(v.qkv_dec, v.split_G != 0, m->attn_q.as<float>(), nrows, c.heads, m->hd, hook_pos, m->rope_cos,
+                                     m->rope_sin, v.split_G == 0, v.st);
+                const bf16_t* k = da.k;
+                AttnProbsArgs pa{};
+                pa.q32 = m->attn_q.as<float>();
+                if (v.split_G && v.es == 3) pa.k24 = k;
+                else if (v.split_G) pa.k32 = reinterpret_cast<const float*>(k);
+                else if (v.es == 1) pa.k8 = reinterpret_cast<const uint8_t*>(k);   // the fp8 weight format's e4m3 rows
+                else pa.k_hi = k;
+                pa.q_stride = 1;
+                pa.kv_stride = v.capS;
+                emit_attentions(m, l, nrows, 1, pa, hook_pos + 1, hook_pos);
+            }
+        },
+        [&](int l) {
+            if (hooks) emit_hidden(m, l + 1, nrows, 1, v.x_dec);
+        });
     launch_select_embed(select_args(m, v, v.logits, nrows, 3), v.st);                                        // K19/K20+K10
     // in-situ timing: fold the step's slots (5 per layer: qkv, attention, o, gate/up, down; then lm_head) into the span's sums
     if (v.stamps && v.stamp_next && v.prof_acc)
         launch_stamp_accumulate(v.stamps, *v.stamp_next, m->c.layers, v.prof_acc, v.stamp_scratch, v.st);
-}
-
-// The same step run eagerly with the output_hidden_states / output_attentions hooks of a cached decode step
-// (vc_request_hidden_states / vc_request_attentions before vc_decode_step): inputs_embeds row, every layer's residual row, the
-// final norm; and per layer the probabilities of the new token's query over the pos + 1 keys, recomputed from the step's own
-// roped q (rounded as the fused kernel rounds it) and the K cache — the fused decode attention keeps only unnormalised scores.
-void enqueue_decode_step_diag(vc_model* m, const LoopView& v, int nrows, int pos) {
-    const vc_model_cfg& c = m->c;
-    emit_hidden(m, 0, nrows, 1, v.x_dec);
-    decode_linears(
-        m, v, nrows,
-        [&](int l) {
-            AttnDecodeFusedArgs da{v.qkv_dec, kcache(v, m, l), vcache(v, m, l), v.attn_dec, nrows, c.heads, m->hd, v.capS,
-                                   v.rows + RS_POS, m->rope_cos, m->rope_sin, 1.0f / sqrtf((float)m->hd), RS_STRIDE,
-                                   v.rows + RS_ACTIVE, v.split_G ? (v.es == 3 ? 2 : 1) : (v.es == 1 ? 3 : 0), v.split_G, v.kmask, v.kmask_stride};
-            launch_attention_decode_fused(da, v.st);
-            if (m->attn_out) {
-                m->attn_q.ensure((size_t)nrows * c.hidden * 4);
-                launch_rope_q_decode(v.qkv_dec, v.split_G != 0, m->attn_q.as<float>(), nrows, c.heads, m->hd, pos, m->rope_cos, m->rope_sin,
-                                     v.split_G == 0, v.st);
-                AttnProbsArgs pa{};
-                pa.q32 = m->attn_q.as<float>();
-                if (v.split_G && v.es == 3) pa.k24 = kcache(v, m, l);
-                else if (v.split_G) pa.k32 = reinterpret_cast<const float*>(kcache(v, m, l));
-                else if (v.es == 1) pa.k8 = reinterpret_cast<const uint8_t*>(kcache(v, m, l));   // the fp8 weight format's e4m3 rows
-                else pa.k_hi = kcache(v, m, l);
-                pa.q_stride = 1;
-                pa.kv_stride = v.capS;
-                emit_attentions(m, l, nrows, 1, pa, pos + 1, pos);
-            }
-        },
-        [&](int l) { emit_hidden(m, l + 1, nrows, 1, v.x_dec); });
-    launch_select_embed(select_args(m, v, v.logits, nrows, 3), v.st);
 }
 
 // strict mode: the rows of a session advance in lockstep, so row 0's position serves every row of the fp32 kernels
@@ -516,6 +534,26 @@ void enqueue_decode_step_strict(vc_model* m, int B) {
     run_llm_layers_strict(m, m->x_dec.as<float>(), B, 1, v.rows + RS_POS, false);
     logits_strict(m, m->x_dec.as<float>(), nullptr, B);
     launch_select_embed(select_args(m, v, v.logits, B, 3), v.st);
+}
+
+// ---- logits of precision mode 0 from the residual rows x (B sequences of rows_per_seq rows) --------------------------------------
+// final norm of each sequence's last row -> lm_head GEMV -> m->logits [B, V]
+void last_row_logits(vc_model* m, const float* x, int B, int rows_per_seq) {
+    const vc_model_cfg& c = m->c;
+    std::vector<int> idx(B);
+    for (int b = 0; b < B; ++b) idx[b] = b * rows_per_seq + rows_per_seq - 1;
+    HIPCHK(hipMemcpyAsync(m->last_idx.p, idx.data(), B * 4, hipMemcpyHostToDevice, m->st));
+    launch_rmsnorm_rows(x, m->last_idx.as<int>(), m->final_norm, m->xl.as<bf16_t>(), B, c.hidden, c.rms_eps, m->st);
+    LoopView lv{};  // the lm_head GEMV over the last rows only needs a stream
+    lv.st = m->st;
+    gemv(m, lv, m->xl.as<bf16_t>(), m->lm_head_p, nullptr, m->logits.p, B, c.vocab, c.hidden, c.vocab, GEMV_F32);
+    HIPCHK(hipStreamSynchronize(m->st));   // `idx` is host memory
+}
+// final norm -> lm_head GEMM over all M rows -> m->logits_all [M, V] (sized by the caller)
+void all_row_logits(vc_model* m, const float* x, int M) {
+    const vc_model_cfg& c = m->c;
+    launch_rmsnorm(x, m->final_norm, m->xn.as<bf16_t>(), M, c.hidden, c.rms_eps, m->st);
+    gemm(m, m->xn.as<bf16_t>(), m->lm_head, nullptr, m->logits_all.p, M, c.vocab, c.hidden, c.vocab, EPI_F32);
 }
 
 // ---- multi-token continuation of the session's cached rows (vc_extend), precision mode 0 ----------------------------------
@@ -563,10 +601,7 @@ void run_extend(vc_model* m, const int* tok_dev, int B, int n, bool all_rows) {
         launch_qkv_split(qa, m->st);
         AttnExtendArgs ea{m->q.as<bf16_t>(), kcache(m, kv, l), vcache(m, kv, l), m->attn.as<bf16_t>(), B, H, n, P, hd, n, kv.capS,
                           kv8 ? 1 : 0, 1.0f / sqrtf((float)hd), nullptr, 0};
-        if (m->kmask_in_decode) {
-            ea.key_mask = m->kmask.as<uint8_t>();
-            ea.mask_stride = c.max_positions;
-        }
+        attach_kmask(m, ea, m->kmask_in_decode);
         launch_attention_extend(ea, m->st);
         if (m->attn_out) {
             AttnProbsArgs pa{};
@@ -598,42 +633,16 @@ void run_extend(vc_model* m, const int* tok_dev, int B, int n, bool all_rows) {
     }
     launch_embed_tokens(tok_dev, m->embed, x, M, D, m->st);
     emit_hidden(m, 0, B, n, x);
+    FoldRun fr;   // (a continuation never folds its norms)
     for (int l = 0; l < c.layers; ++l) {
         const LlmLayer& L = m->llm[l];
-        if (f8) {
-            launch_rmsnorm_q8(x, L.in_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
-            gemm_f8(m, nullptr, L.qkv_q, L.qkv_s, m->qkv.p, M, 3 * D, D, 3 * D, EPI_BF16);
-        } else {
-            launch_rmsnorm(x, L.in_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD);
-            gemm(m, m->xn.as<bf16_t>(), L.qkv_w, nullptr, m->qkv.p, M, 3 * D, D, 3 * D, EPI_BF16, D + XN_PAD);
-        }
+        qkv_projection(m, L, M, fr);
         attention(l, m->qkv.as<bf16_t>());
-        if (f8) {
-            gemm_f8(m, m->attn.as<bf16_t>(), L.o_q, L.o_s, x, M, D, D, D, EPI_RESID_F32);
-            launch_rmsnorm_q8(x, L.post_norm, m->a8.as<uint8_t>(), m->a8_scale.as<float>(), M, D, c.rms_eps, m->st);
-            gemm_f8(m, nullptr, L.gu_q, L.gu_s, m->h.p, M, 2 * F, D, F, EPI_SWIGLU);
-            gemm_f8(m, m->h.as<bf16_t>(), L.down_q, L.down_s, x, M, D, F, D, EPI_RESID_F32);
-        } else {
-            gemm(m, m->attn.as<bf16_t>(), L.o_w, nullptr, x, M, D, D, D, EPI_RESID_F32);
-            launch_rmsnorm(x, L.post_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st, D + XN_PAD);
-            gemm(m, m->xn.as<bf16_t>(), L.gu_w, nullptr, m->h.p, M, 2 * F, D, F, EPI_SWIGLU, D + XN_PAD);
-            gemm(m, m->h.as<bf16_t>(), L.down_w, nullptr, x, M, D, F, D, EPI_RESID_F32);
-        }
+        layer_tail(m, L, M, fr, nullptr);
         emit_hidden(m, l + 1, B, n, x);
     }
-    if (all_rows) {
-        launch_rmsnorm(x, m->final_norm, m->xn.as<bf16_t>(), M, D, c.rms_eps, m->st);
-        gemm(m, m->xn.as<bf16_t>(), m->lm_head, nullptr, m->logits_all.p, M, c.vocab, D, c.vocab, EPI_F32);
-    } else {   // the last row of every sequence through the lm_head GEMV, as a prefill does
-        std::vector<int> idx(B);
-        for (int b = 0; b < B; ++b) idx[b] = b * n + n - 1;
-        HIPCHK(hipMemcpyAsync(m->last_idx.p, idx.data(), B * 4, hipMemcpyHostToDevice, m->st));
-        launch_rmsnorm_rows(x, m->last_idx.as<int>(), m->final_norm, m->xl.as<bf16_t>(), B, D, c.rms_eps, m->st);
-        LoopView lv{};
-        lv.st = m->st;
-        gemv(m, lv, m->xl.as<bf16_t>(), m->lm_head_p, nullptr, m->logits.p, B, c.vocab, D, c.vocab, GEMV_F32);
-        HIPCHK(hipStreamSynchronize(m->st));   // `idx` is host memory
-    }
+    if (all_rows) all_row_logits(m, x, M);
+    else last_row_logits(m, x, B, n);   // the last row of every sequence through the lm_head GEMV, as a prefill does
 }
 
 hipGraphExec_t capture_step(vc_model* m, const LoopView& v, int nrows) {
@@ -751,20 +760,9 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
         else m->feats.ensure(256);
     } else if (m->plan_only) {
         // the plan needs the feature-row COUNTS of every modality and the depth pixels (is_depth_zero), not the features
-        const int Rp = m->Tv - (c.vit_keep_cls ? 0 : 1);
-        const size_t img_elems = (size_t)3 * c.vit_image * c.vit_image;
-        int first = 0;
-        for (int k = 0; k < 3; ++k) {
-            m->feat_off[k] = first * Rp;
-            m->feat_rows[k] = pix.p[k] ? pix.n[k] * Rp : 0;
-            if (pix.p[k]) first += pix.n[k];
-        }
-        REQUIRE(first > 0, VC_ERR_INVALID, "no images");
-        m->v_pixels.ensure((size_t)first * img_elems * 4);
-        if (depth)
-            HIPCHK(hipMemcpyAsync(m->v_pixels.as<float>() + (size_t)(first - pix.n[VC_MOD_DEPTH]) * img_elems, depth,
-                                  (size_t)pix.n[VC_MOD_DEPTH] * img_elems * 4, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                  m->st));
+        int order[3], first_img[3];
+        stage_pixels(m, pix, on_dev, order, first_img, 1u << VC_MOD_DEPTH);
+        set_feat_rows(m, pix, first_img, m->Tv - (c.vit_keep_cls ? 0 : 1));
     } else if (m->precision == 1) run_vit_and_adapters_strict(m, pix, on_dev);
     else if (m->precision == 2) run_vit_and_adapters_split(m, pix, on_dev);
     else run_vit_and_adapters(m, pix, on_dev);
@@ -882,9 +880,9 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
 void finish_prefill(vc_model* m, const KvTarget& kv, float* logits_all_host) {
     const vc_model_cfg& c = m->c;
     const int B = m->curB, S = m->curS, D = c.hidden;
-    std::vector<int> idx(B);
+    std::vector<int> idx(B);   // strict / split: the last row of every sequence
     for (int b = 0; b < B; ++b) idx[b] = b * S + S - 1;
-    HIPCHK(hipMemcpyAsync(m->last_idx.p, idx.data(), B * 4, hipMemcpyHostToDevice, m->st));
+    if (m->precision) HIPCHK(hipMemcpyAsync(m->last_idx.p, idx.data(), B * 4, hipMemcpyHostToDevice, m->st));
     emit_hidden(m, 0, B, S);   // inputs_embeds
     if (m->precision == 1) {
         run_llm_layers_strict(m, m->x.as<float>(), B, S, nullptr, true);
@@ -902,10 +900,7 @@ void finish_prefill(vc_model* m, const KvTarget& kv, float* logits_all_host) {
         gemv(m, lv, m->xl.as<bf16_t>(), m->lm_head_p, nullptr, m->logits.p, B, c.vocab, D, c.vocab, GEMV_F32);
     } else {
         run_prefill_layers(m, kv, B, S);
-        launch_rmsnorm_rows(m->x.as<float>(), m->last_idx.as<int>(), m->final_norm, m->xl.as<bf16_t>(), B, D, c.rms_eps, m->st);
-        LoopView lv{};  // the lm_head GEMV over the last rows only needs a stream
-        lv.st = m->st;
-        gemv(m, lv, m->xl.as<bf16_t>(), m->lm_head_p, nullptr, m->logits.p, B, c.vocab, D, c.vocab, GEMV_F32);
+        last_row_logits(m, m->x.as<float>(), B, S);
     }
     if (logits_all_host) {  // lm_head over ALL S positions, as the reference's forward returns (:93)
         const size_t Mr = (size_t)B * S;
@@ -920,8 +915,7 @@ void finish_prefill(vc_model* m, const KvTarget& kv, float* logits_all_host) {
             launch_rmsnorm_split(m->x.as<float>(), nullptr, m->final_norm, m->xn.as<bf16_t>(), (int)Mr, D, c.rms_eps, ldx, D, m->st);
             gemm_split(m, m->xn.as<bf16_t>(), m->lm_head, nullptr, m->logits_all.p, (int)Mr, c.vocab, D, c.vocab, EPI_F32, ldx);
         } else {
-            launch_rmsnorm(m->x.as<float>(), m->final_norm, m->xn.as<bf16_t>(), (int)Mr, D, c.rms_eps, m->st);
-            gemm(m, m->xn.as<bf16_t>(), m->lm_head, nullptr, m->logits_all.p, (int)Mr, c.vocab, D, c.vocab, EPI_F32);
+            all_row_logits(m, m->x.as<float>(), (int)Mr);
         }
         HIPCHK(hipMemcpyAsync(logits_all_host, m->logits_all.p, Mr * c.vocab * 4, hipMemcpyDeviceToHost, m->st));
     }

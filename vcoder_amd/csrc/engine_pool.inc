@@ -318,7 +318,7 @@ bool pool_wants_prof(const vc_model* root, bool want_split) {
 }
 
 vc_pool* pool_for(vc_model* m, int need_S, int need_out) {
-    vc_model* root = m->root ? m->root : m;
+    vc_model* root = root_of(m);
     const vc_model_cfg& c = root->c;
     std::unique_lock<std::mutex> create(g_pool_create);
     vc_pool* p = root->pool;

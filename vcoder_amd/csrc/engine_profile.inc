@@ -142,6 +142,9 @@ VC_API int vc_profile_decode_attention(vc_model* m, int B, int ctx, int reps, in
         v.st = m->st;
     }
     REQUIRE(ctx + 1 <= v.capS, VC_ERR_INVALID, "context %d exceeds the cache capacity %d", ctx, v.capS);
+    v.split_G = 0;   // the sweep times the bf16 step's attention as such: no split group, no key mask
+    v.kmask = nullptr;
+    v.kmask_stride = 0;
     std::vector<int> rec((size_t)B * RS_STRIDE, 0);
     double keys = 0;
     for (int b = 0; b < B; ++b) {
@@ -153,10 +156,7 @@ VC_API int vc_profile_decode_attention(vc_model* m, int B, int ctx, int reps, in
     HIPCHK(hipStreamSynchronize(m->st));
     auto sweep = [&]() {
         for (int l = 0; l < c.layers; ++l) {
-            AttnDecodeFusedArgs da{v.qkv_dec, kcache(v, m, l), vcache(v, m, l), v.attn_dec, B, c.heads, m->hd, v.capS,
-                                   v.rows + RS_POS, m->rope_cos, m->rope_sin, 1.0f / sqrtf((float)m->hd), RS_STRIDE,
-                                   v.rows + RS_ACTIVE, v.es == 1 ? 3 : 0};
-            launch_attention_decode_fused(da, m->st);
+            launch_attention_decode_fused(decode_attn_args(m, v, l, B), m->st);
         }
     };
     sweep();  // warm
@@ -179,7 +179,7 @@ VC_API int vc_profile_decode_attention(vc_model* m, int B, int ctx, int reps, in
  * created (zeros if it has none): lets bench.py weight the per-row-count kernel timings by what the timed run executed */
 VC_API int vc_pool_step_counts(vc_model* m, unsigned long long* counts4) {
     if (!m || !counts4) return VC_ERR_INVALID;
-    vc_model* root = m->root ? m->root : m;
+    vc_model* root = root_of(m);
     for (int i = 0; i < 4; ++i) counts4[i] = 0;
     if (root->pool) {
         std::lock_guard<std::mutex> lk(root->pool->mu);
@@ -202,7 +202,7 @@ VC_API int vc_pool_step_counts(vc_model* m, unsigned long long* counts4) {
  * latency for the requests in flight).  Applies to every session of the model. */
 VC_API int vc_pool_set_hold(vc_model* m, int on) {
     if (!m) return VC_ERR_INVALID;
-    vc_model* root = m->root ? m->root : m;
+    vc_model* root = root_of(m);
     root->pool_hold.store(on != 0);
     // the pool may be rebuilt (destroyed and re-created) by pool_for under g_pool_create while this runs on another thread
     std::lock_guard<std::mutex> create_lk(g_pool_create);
@@ -218,13 +218,13 @@ VC_API int vc_pool_set_hold(vc_model* m, int on) {
  * the pool is next (re)built, i.e. while it is idle; a 64-row pool serves the bf16 step only and carries no in-situ timing slots. */
 VC_API int vc_pool_set_rows(vc_model* m, int rows) {
     if (!m || (rows != VC_POOL_ROWS && rows != VC_POOL_ROWS_MAX)) return VC_ERR_INVALID;
-    (m->root ? m->root : m)->pool_rows = rows;
+    root_of(m)->pool_rows = rows;
     return VC_OK;
 }
 
 VC_API int vc_pool_profile(vc_model* m, int on) {
     if (!m) return VC_ERR_INVALID;
-    vc_model* root = m->root ? m->root : m;
+    vc_model* root = root_of(m);
     root->pool_profile = on != 0;
     return VC_OK;
 }
@@ -237,7 +237,7 @@ VC_API int vc_pool_profile_read(vc_model* m, double* exec_us, double* period_us,
     if (!m || !exec_us || !period_us || !launches) return VC_ERR_INVALID;
     GUARD_BEGIN
     USE_DEVICE(m->ctx);
-    vc_model* root = m->root ? m->root : m;
+    vc_model* root = root_of(m);
     const int nspan = VC_POOL_ROWS / 8;
     for (int i = 0; i < nspan * PROF_KINDS; ++i) {
         exec_us[i] = period_us[i] = 0;

@@ -10,29 +10,96 @@ struct PixSet {
     int n[3];           // images in each block
 };
 
-// CLIPVisionTower.forward (clip_encoder.py:39-51) up to hidden_states[select_layer]: leaves the fp32 residual stream of
-// all N images in v_x [N*Tv, Dv]; returns N and the block order
-int run_vit_tower(vc_model* m, const PixSet& in, int pixels_on_device, int order[3], int first_img[3]) {
-    const vc_model_cfg& c = m->c;
-    const int Dv = c.vit_hidden, Fv = c.vit_ffn, H = c.vit_heads, Tv = m->Tv, P = m->P;
+inline bool has_mod(const PixSet& in, int k) { return in.p[k] && in.n[k] > 0; }
+
+// Pixel staging of a tower pass: counts the modalities present (`order`: their blocks in v_pixels, `first_img[k]`: the first
+// image of modality k's block), sizes v_pixels for all N images and copies in the blocks of the modalities in `copy_mask`
+// (bit k; the splice plan alone reads only the depth pixels).  Returns N.
+int stage_pixels(vc_model* m, const PixSet& in, int pixels_on_device, int order[3], int first_img[3], unsigned copy_mask = 7) {
     int nmod = 0, N = 0;
     for (int k = 0; k < 3; ++k) {
         first_img[k] = 0;
-        if (in.p[k] && in.n[k] > 0) {
+        if (has_mod(in, k)) {
             order[nmod++] = k;
             first_img[k] = N;
             N += in.n[k];
         }
     }
     REQUIRE(N > 0, VC_ERR_INVALID, "no images");
-    const size_t img_elems = (size_t)3 * c.vit_image * c.vit_image;
+    const size_t img_elems = (size_t)3 * m->c.vit_image * m->c.vit_image;
     m->v_pixels.ensure((size_t)N * img_elems * 4);
     for (int i = 0; i < nmod; ++i) {
         const int k = order[i];
+        if (!(copy_mask >> k & 1)) continue;
         HIPCHK(hipMemcpyAsync(m->v_pixels.as<float>() + (size_t)first_img[k] * img_elems, in.p[k],
                               (size_t)in.n[k] * img_elems * 4,
                               pixels_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m->st));
     }
+    return N;
+}
+
+// what the splice planner reads of the features: modality k owns rows [feat_off, feat_off + feat_rows) of the feature buffer
+// (R rows per image, blocks in the order of v_pixels)
+void set_feat_rows(vc_model* m, const PixSet& in, const int first_img[3], int R) {
+    for (int k = 0; k < 3; ++k) {
+        m->feat_rows[k] = 0;
+        if (!has_mod(in, k)) continue;
+        m->feat_off[k] = first_img[k] * R;
+        m->feat_rows[k] = in.n[k] * R;
+    }
+}
+
+// The adapters behind the tower (encode_images / encode_seg_images / encode_depth_images, vcoder_ds_llava_arch.py:106-124),
+// stated once for the three precision modes.  A mode describes its buffers (rows in bytes):
+struct AdapterForm {
+    const char* src;    // feature_select'ed tower rows
+    size_t src_row;
+    char* out;          // projected features (what the splice reads)
+    size_t out_row;
+    Buf *mid0, *mid1;   // outputs of the middle layers of a projector, alternating
+    size_t mid_row;
+};
+// and supplies two callables: identity_rows() -> the rows a depth-0 projector copies (in the features' element type, all images),
+// and linear(cur, l, W, b, dst, rows, last): layer l of a projector over `rows` rows (GELU unless last)
+template <class IdentityRows, class Linear>
+void run_adapters(vc_model* m, const PixSet& in, const int first_img[3], const AdapterForm& f, IdentityRows&& identity_rows,
+                  Linear&& linear) {
+    const int R = m->Tv - (m->c.vit_keep_cls ? 0 : 1);  // feature rows per image
+    set_feat_rows(m, in, first_img, R);
+    for (int mod = 0; mod < 3; ++mod) {
+        if (!has_mod(in, mod)) continue;
+        // images -> mm_projector; seg AND depth -> seg_mm_projector (quirk 1, vcoder_ds_llava_arch.py:111-114);
+        // mm2_projector is unreachable (quirk 2, :137,145)
+        const Projector& pj = mod == VC_MOD_IMAGE ? m->mm : m->seg;
+        const int rows = m->feat_rows[mod];
+        const size_t row0 = (size_t)m->feat_off[mod];
+        char* out = f.out + row0 * f.out_row;
+        if (pj.depth == 0) {
+            REQUIRE(m->c.vit_hidden == m->c.hidden, VC_ERR_INVALID, "identity projector needs mm_hidden_size == hidden_size");
+            HIPCHK(hipMemcpyAsync(out, identity_rows() + row0 * f.out_row, (size_t)rows * f.out_row, hipMemcpyDeviceToDevice, m->st));
+            continue;
+        }
+        const void* cur = f.src + row0 * f.src_row;
+        for (int l = 0; l < pj.depth; ++l) {
+            const bool last = l == pj.depth - 1;
+            void* dst = out;
+            if (!last) {
+                Buf* mid = l % 2 == 0 ? f.mid0 : f.mid1;
+                mid->ensure((size_t)rows * f.mid_row);
+                dst = mid->p;
+            }
+            linear(cur, l, pj.w[l], pj.b[l], dst, rows, last);
+            cur = dst;
+        }
+    }
+}
+
+// CLIPVisionTower.forward (clip_encoder.py:39-51) up to hidden_states[select_layer]: leaves the fp32 residual stream of
+// all N images in v_x [N*Tv, Dv]; returns N and the block order
+int run_vit_tower(vc_model* m, const PixSet& in, int pixels_on_device, int order[3], int first_img[3]) {
+    const vc_model_cfg& c = m->c;
+    const int Dv = c.vit_hidden, Fv = c.vit_ffn, H = c.vit_heads, Tv = m->Tv, P = m->P;
+    const int N = stage_pixels(m, in, pixels_on_device, order, first_img);
     const int M = N * Tv, Mp = N * P;
     const int Ts = (int)rup(Tv, 64);
     m->v_cols.ensure((size_t)Mp * m->Kpad * 2);
@@ -73,40 +140,17 @@ int run_vit_tower(vc_model* m, const PixSet& in, int pixels_on_device, int order
 }
 
 void run_vit_and_adapters(vc_model* m, const PixSet& in, int pixels_on_device) {
-    const vc_model_cfg& c = m->c;
-    const int Dv = c.vit_hidden, D = c.hidden;
+    const int Dv = m->c.vit_hidden, D = m->c.hidden;
     int order[3], first_img[3];
     const int N = run_vit_tower(m, in, pixels_on_device, order, first_img);
-    const int R = m->Tv - (c.vit_keep_cls ? 0 : 1);  // feature rows per image
+    const int R = m->Tv - (m->c.vit_keep_cls ? 0 : 1);  // feature rows per image
     m->feats.ensure((size_t)N * R * D * 2);
     m->v_mid.ensure((size_t)N * R * D * 2);
-    for (int k = 0; k < 3; ++k) m->feat_rows[k] = 0;
-    for (int mod = 0; mod < 3; ++mod) {
-        if (!(in.p[mod] && in.n[mod] > 0)) continue;
-        // images -> mm_projector; seg AND depth -> seg_mm_projector (quirk 1, vcoder_ds_llava_arch.py:111-114);
-        // mm2_projector is unreachable (quirk 2, :137,145)
-        const Projector& pj = mod == VC_MOD_IMAGE ? m->mm : m->seg;
-        const int rows = in.n[mod] * R;
-        const bf16_t* src = m->v_sel.as<bf16_t>() + (size_t)first_img[mod] * R * Dv;
-        bf16_t* out = m->feats.as<bf16_t>() + (size_t)first_img[mod] * R * D;
-        m->feat_off[mod] = first_img[mod] * R;
-        m->feat_rows[mod] = rows;
-        if (pj.depth == 0) {
-            REQUIRE(Dv == D, VC_ERR_INVALID, "identity projector needs mm_hidden_size == hidden_size");
-            HIPCHK(hipMemcpyAsync(out, src, (size_t)rows * D * 2, hipMemcpyDeviceToDevice, m->st));
-            continue;
-        }
-        const bf16_t* cur = src;
-        int K = Dv;
-        for (int l = 0; l < pj.depth; ++l) {
-            const bool last = l == pj.depth - 1;
-            if (!last && l % 2 == 1) m->v_h.ensure((size_t)rows * D * 2);
-            bf16_t* dst = last ? out : (l % 2 == 0 ? m->v_mid.as<bf16_t>() : m->v_h.as<bf16_t>());
-            gemm(m, cur, pj.w[l], pj.b[l], dst, rows, D, K, D, last ? EPI_BF16 : EPI_BF16_GELU);
-            cur = dst;
-            K = D;
-        }
-    }
+    const AdapterForm f{m->v_sel.as<char>(), (size_t)Dv * 2, m->feats.as<char>(), (size_t)D * 2, &m->v_mid, &m->v_h, (size_t)D * 2};
+    run_adapters(m, in, first_img, f, [&] { return f.src; },
+                 [&](const void* cur, int l, const bf16_t* W, const float* b, void* dst, int rows, bool last) {
+                     gemm(m, static_cast<const bf16_t*>(cur), W, b, dst, rows, D, l ? D : Dv, D, last ? EPI_BF16 : EPI_BF16_GELU);
+                 });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -117,24 +161,7 @@ void run_vit_and_adapters(vc_model* m, const PixSet& in, int pixels_on_device) {
 int run_vit_tower_split(vc_model* m, const PixSet& in, int pixels_on_device, int order[3], int first_img[3]) {
     const vc_model_cfg& c = m->c;
     const int Dv = c.vit_hidden, Fv = c.vit_ffn, H = c.vit_heads, Tv = m->Tv, P = m->P;
-    int nmod = 0, N = 0;
-    for (int k = 0; k < 3; ++k) {
-        first_img[k] = 0;
-        if (in.p[k] && in.n[k] > 0) {
-            order[nmod++] = k;
-            first_img[k] = N;
-            N += in.n[k];
-        }
-    }
-    REQUIRE(N > 0, VC_ERR_INVALID, "no images");
-    const size_t img_elems = (size_t)3 * c.vit_image * c.vit_image;
-    m->v_pixels.ensure((size_t)N * img_elems * 4);
-    for (int i = 0; i < nmod; ++i) {
-        const int k = order[i];
-        HIPCHK(hipMemcpyAsync(m->v_pixels.as<float>() + (size_t)first_img[k] * img_elems, in.p[k],
-                              (size_t)in.n[k] * img_elems * 4,
-                              pixels_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m->st));
-    }
+    const int N = stage_pixels(m, in, pixels_on_device, order, first_img);
     const int M = N * Tv, Mp = N * P;
     const int Ts = (int)rup(Tv, 64);
     const int ldx = split_ld(Dv), ldh = split_ld(Fv);
@@ -185,38 +212,20 @@ void run_vit_and_adapters_split(vc_model* m, const PixSet& in, int pixels_on_dev
     launch_select_rows_bf16(m->v_x.as<float>(), m->v_sel.as<bf16_t>(), N, m->Tv, skip, Dv, m->st, true);
     m->s_feats.ensure((size_t)N * R * D * 4);
     m->v_mid.ensure((size_t)N * R * ldd * 2);
-    for (int k = 0; k < 3; ++k) m->feat_rows[k] = 0;
-    for (int mod = 0; mod < 3; ++mod) {
-        if (!(in.p[mod] && in.n[mod] > 0)) continue;
-        const Projector& pj = mod == VC_MOD_IMAGE ? m->mm : m->seg;  // quirk 1: depth -> seg_mm_projector
-        const int rows = in.n[mod] * R;
-        float* out = m->s_feats.as<float>() + (size_t)first_img[mod] * R * D;
-        m->feat_off[mod] = first_img[mod] * R;
-        m->feat_rows[mod] = rows;
-        if (pj.depth == 0) {  // identity: the fp32 rows of hidden_states[select_layer]
-            REQUIRE(Dv == D, VC_ERR_INVALID, "identity projector needs mm_hidden_size == hidden_size");
+    const AdapterForm f{m->v_sel.as<char>(), (size_t)ldv * 2, m->s_feats.as<char>(), (size_t)D * 4, &m->v_mid, &m->v_h, (size_t)ldd * 2};
+    run_adapters(
+        m, in, first_img, f,
+        [&] {  // identity: the fp32 rows of hidden_states[select_layer]
             m->s_sel.ensure((size_t)N * R * Dv * 4);
             launch_select_rows_f32(m->v_x.as<float>(), m->s_sel.as<float>(), N, m->Tv, skip, Dv, m->st);
-            HIPCHK(hipMemcpyAsync(out, m->s_sel.as<float>() + (size_t)first_img[mod] * R * Dv, (size_t)rows * D * 4,
-                                  hipMemcpyDeviceToDevice, m->st));
-            continue;
-        }
-        const bf16_t* cur = m->v_sel.as<bf16_t>() + (size_t)first_img[mod] * R * ldv;
-        int K = Dv, lda = ldv;
-        for (int l = 0; l < pj.depth; ++l) {
-            const bool last = l == pj.depth - 1;
-            if (!last && l % 2 == 1) m->v_h.ensure((size_t)rows * ldd * 2);
-            if (last) {
-                gemm_split(m, cur, pj.w[l], pj.b[l], out, rows, D, K, D, EPI_F32, lda);
-            } else {
-                bf16_t* dst = l % 2 == 0 ? m->v_mid.as<bf16_t>() : m->v_h.as<bf16_t>();
-                gemm_split(m, cur, pj.w[l], pj.b[l], dst, rows, D, K, ldd, EPI_BF16_GELU, lda, D);
-                cur = dst;
-                K = D;
-                lda = ldd;
-            }
-        }
-    }
+            return m->s_sel.as<char>();
+        },
+        [&](const void* cur, int l, const bf16_t* W, const float* b, void* dst, int rows, bool last) {
+            const bf16_t* A = static_cast<const bf16_t*>(cur);
+            const int K = l ? D : Dv, lda = l ? ldd : ldv;
+            if (last) gemm_split(m, A, W, b, dst, rows, D, K, D, EPI_F32, lda);
+            else gemm_split(m, A, W, b, dst, rows, D, K, ldd, EPI_BF16_GELU, lda, D);
+        });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -231,24 +240,7 @@ void gemm32(vc_model* m, const float* A, const bf16_t* W, const float* bias, flo
 int run_vit_tower_strict(vc_model* m, const PixSet& in, int pixels_on_device, int order[3], int first_img[3]) {
     const vc_model_cfg& c = m->c;
     const int Dv = c.vit_hidden, Fv = c.vit_ffn, H = c.vit_heads, Tv = m->Tv, P = m->P, D = c.hidden;
-    int nmod = 0, N = 0;
-    for (int k = 0; k < 3; ++k) {
-        first_img[k] = 0;
-        if (in.p[k] && in.n[k] > 0) {
-            order[nmod++] = k;
-            first_img[k] = N;
-            N += in.n[k];
-        }
-    }
-    REQUIRE(N > 0, VC_ERR_INVALID, "no images");
-    const size_t img_elems = (size_t)3 * c.vit_image * c.vit_image;
-    m->v_pixels.ensure((size_t)N * img_elems * 4);
-    for (int i = 0; i < nmod; ++i) {
-        const int k = order[i];
-        HIPCHK(hipMemcpyAsync(m->v_pixels.as<float>() + (size_t)first_img[k] * img_elems, in.p[k],
-                              (size_t)in.n[k] * img_elems * 4,
-                              pixels_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m->st));
-    }
+    const int N = stage_pixels(m, in, pixels_on_device, order, first_img);
     const int M = N * Tv, Mp = N * P;
     m->s_cols.ensure((size_t)Mp * m->Kpatch * 4);
     m->s_patches.ensure((size_t)Mp * Dv * 4);
@@ -296,30 +288,14 @@ void run_vit_and_adapters_strict(vc_model* m, const PixSet& in, int pixels_on_de
     const int R = m->Tv - (c.vit_keep_cls ? 0 : 1);
     m->s_feats.ensure((size_t)N * R * D * 4);
     m->s_mid.ensure((size_t)N * R * D * 4);
-    for (int k = 0; k < 3; ++k) m->feat_rows[k] = 0;
-    for (int mod = 0; mod < 3; ++mod) {
-        if (!(in.p[mod] && in.n[mod] > 0)) continue;
-        const Projector& pj = mod == VC_MOD_IMAGE ? m->mm : m->seg;  // quirk 1: depth -> seg_mm_projector
-        const int rows = in.n[mod] * R;
-        const float* src = m->s_sel.as<float>() + (size_t)first_img[mod] * R * Dv;
-        float* out = m->s_feats.as<float>() + (size_t)first_img[mod] * R * D;
-        m->feat_off[mod] = first_img[mod] * R;
-        m->feat_rows[mod] = rows;
-        if (pj.depth == 0) {
-            REQUIRE(Dv == D, VC_ERR_INVALID, "identity projector needs mm_hidden_size == hidden_size");
-            HIPCHK(hipMemcpyAsync(out, src, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, m->st));
-            continue;
-        }
-        const float* cur = src;
-        int K = Dv;
-        for (int l = 0; l < pj.depth; ++l) {
-            const bool last = l == pj.depth - 1;
-            float* dst = last ? out : (l % 2 == 0 ? m->s_mid.as<float>() : m->s_vh.as<float>());
-            gemm32(m, cur, pj.w[l], pj.b[l], dst, rows, D, K, K, K, D, last ? EPI_F32 : EPI_BF16_GELU);
-            cur = dst;
-            K = D;
-        }
-    }
+    // (s_vh, the tower's MLP buffer, already holds N * Tv rows of max(vit_ffn, hidden) floats)
+    const AdapterForm f{m->s_sel.as<char>(), (size_t)Dv * 4, m->s_feats.as<char>(), (size_t)D * 4, &m->s_mid, &m->s_vh, (size_t)D * 4};
+    run_adapters(m, in, first_img, f, [&] { return f.src; },
+                 [&](const void* cur, int l, const bf16_t* W, const float* b, void* dst, int rows, bool last) {
+                     const int K = l ? D : Dv;
+                     gemm32(m, static_cast<const float*>(cur), W, b, static_cast<float*>(dst), rows, D, K, K, K, D,
+                            last ? EPI_F32 : EPI_BF16_GELU);
+                 });
 }
 
 void ensure_strict(vc_model* m, int B, int Scap) {
@@ -361,10 +337,7 @@ void run_llm_layers_strict(vc_model* m, float* x, int B, int T, const int* pos_d
         launch_qkv_rope_f32(qa, m->st);
         AttnF32Args aa{q, s_kcache(m, l), s_vcache(m, l), at, B, H, T, m->hd, T, m->s_capS, 1, 0, pos_dev,
                        1.0f / sqrtf((float)m->hd)};
-        if (is_prefill ? m->has_kmask : m->kmask_in_decode) {
-            aa.key_mask = m->kmask.as<uint8_t>();
-            aa.mask_stride = c.max_positions;
-        }
+        attach_kmask(m, aa, is_prefill ? m->has_kmask : m->kmask_in_decode);
         launch_attention_f32(aa, m->st);
         const bool step = !is_prefill && x == m->x_dec.as<float>();   // a session's cached decode step (m->cur_pos = its position)
         const bool pre = is_prefill && x == m->x.as<float>();

@@ -1,6 +1,8 @@
 // engine_weights.inc — part of the host engine (textually included by engine.hip inside its anonymous namespace; one translation unit).
 // device allocation helpers, HF key canonicalisation, the loader's 16-bit planes (hi / lo), place_tensor: every checkpoint tensor into its inference layout.
 
+// the model that owns the weights and the model-wide settings (a session created by vc_model_create_shared points at its parent's)
+template <class M> inline M* root_of(M* m) { return m->root ? m->root : m; }
 
 template <class T> T* walloc(vc_model* m, size_t n, bool zero = false) {
     void* p = nullptr;
@@ -69,7 +71,7 @@ std::string canon_key(const std::string& k) {
 
 // the lo plane of a weight (hi-plane pointer as loaded / packed), or nullptr: exact checkpoint, or none kept for it
 const bf16_t* lo_plane(const vc_model* m, const void* hi) {
-    const vc_model* r = m->root ? m->root : m;
+    const vc_model* r = root_of(m);
     auto it = r->lo_of.find(hi);
     return it == r->lo_of.end() ? nullptr : it->second;
 }
@@ -237,6 +239,14 @@ int place_tensor(vc_model* m, const std::string& raw_key, const void* src, int d
     return VC_OK;
 }
 
+// the session's key mask (keys hidden by the caller's attention_mask: [VC_MAX_ROWS][max_positions] bytes, 0 = hidden) onto the
+// arguments of an attention launch, when `on` (a prefill: m->has_kmask; cached rows: m->kmask_in_decode)
+template <class A> void attach_kmask(const vc_model* m, A& a, bool on) {
+    if (!on) return;
+    a.key_mask = m->kmask.as<uint8_t>();
+    a.mask_stride = m->c.max_positions;
+}
+
 // output_hidden_states hook (defined with the prefill layers); x_src: the residual rows to copy (default: the prefill's m->x)
 void emit_hidden(vc_model* m, int idx, int B, int S, const float* x_src = nullptr);
 // output_attentions hook: the probabilities of decoder layer l from its q / k in the precision mode's own form.  S queries
@@ -257,10 +267,7 @@ void emit_attentions(vc_model* m, int l, int B, int S, AttnProbsArgs a, int Tk =
     a.q_pos0 = q_pos0;
     a.hd = m->hd;
     a.scale = 1.0f / sqrtf((float)m->hd);
-    if (Tk > 0 ? m->kmask_in_decode : m->has_kmask) {
-        a.key_mask = m->kmask.as<uint8_t>();
-        a.mask_stride = m->c.max_positions;
-    }
+    attach_kmask(m, a, Tk > 0 ? m->kmask_in_decode : m->has_kmask);
     launch_attn_probs(a, m->st);
     HIPCHK(hipMemcpyAsync(m->attn_out + (size_t)l * n, a.out, n * 4, hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipStreamSynchronize(m->st));   // hidden_tmp is shared with the hidden-state hook
