@@ -215,6 +215,33 @@ int vc_decode_step(vc_model* m, const int32_t* tok, float* logits, int32_t* next
  * calls.  A refused call (bad ids, shape, state) changes nothing. */
 int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logits_all, float* logits_last);
 
+/* Token scores (one-shot), for the NEXT vc_prefill (labels [B, T] aligned with its ids) or vc_extend (labels [B, n] aligned with its
+ * tok): the loss side of the reference's forward(labels=...) (vcoder_ds_llava_llama.py:95-106) without logits leaving the device.
+ * A vc_prefill splices the labels by the plan of its embeddings (vcoder_ds_llava_arch.py:176-293): a text row keeps the label of its
+ * id, feature rows and the right padding of shorter rows carry -100, text the DS variant drops between <image> and <seg> drops its
+ * label too, and whatever stands at a placeholder position of `labels` is ignored.  HF's shift applies: the row in front of position
+ * j scores label j, position 0 of a prefill and label 0 of an extend chunk are never scored.  The final norm and the lm_head run
+ * over the scored rows only, in chunks of 1024 rows, and a kernel reduces every logits row to log p(label).
+ * logprobs (host, cap elements) receives [B, S] resp. [B, n] fp32: log p(label) where the spliced label is not -100, 0 elsewhere;
+ * spliced_labels (host, cap elements, may be NULL) the labels as laid out.  Both must stay valid until that call returns.
+ * Composes with vc_set_attention_mask, vc_set_image_counts, vc_request_hidden_states, vc_request_attentions, logits_all and
+ * logits_last.  Cleared when that call returns, also when it fails; vc_generate* ignores and clears it.
+ * That call refuses, with the session's cache and position unchanged (vc_extend: before anything is enqueued; vc_prefill: behind
+ * its splice plan, before the decoder stack): a spliced label outside {-100} and [0, vocab) that the shift keeps (VC_ERR_INDEX:
+ * torch's "Target ... is out of bounds" is an IndexError; as there, a label the splice drops is never looked at); B / T / n that do
+ * not match the call, or cap smaller than the result (VC_ERR_INVALID).  For the same reason a scored vc_prefill that its plan refuses
+ * on other grounds (an id outside the vocabulary, VC_ERR_UNEQUAL) keeps the loop position too, where an unscored vc_prefill has
+ * already dropped it on entry; both leave the cache rows untouched.  labels == NULL cancels a pending request. */
+int vc_request_token_scores(vc_model* m, const int64_t* labels, int B, int T, float* logprobs /* [B, S] or [B, n] host */,
+                            int64_t* spliced_labels /* same shape, may be NULL */, size_t cap /* elements of each output buffer */);
+
+/* the loop steps back to position P (prefill's S <= P <= current position): cached rows >= P are dead.  Nothing is copied; the
+ * prefill's hidden keys stay hidden; every precision mode.  The token the last step selected on the device is no longer valid:
+ * vc_decode_step(tok = NULL) returns VC_ERR_STATE until a vc_extend or a vc_decode_step with explicit tokens has run.  K candidate
+ * continuations are scored behind one prompt as K x (vc_request_token_scores, vc_extend, vc_rewind).  HF counterpart:
+ * DynamicCache.crop. */
+int vc_rewind(vc_model* m, int P);
+
 /* beam search support: the KV rows of the current vc_prefill / vc_decode_step loop are permuted, row r <- old row src_rows[r] —
  * `past_key_values` reordered by beam_idx after a beam step ([HF] generation/utils.py beam_search; the reference's eval loaders
  * forward num_beams: eval/model_seg_loader.py:129-139) */

@@ -117,6 +117,10 @@ int vck_row_state_stride(void);
 /* test hook of the sampler: u[i] = the uniform in (0,1) the Gumbel-max draw derives from 32-bit hash h[i] (strictly
  * inside the interval for EVERY h, so the Gumbel term -log(-log(u)) written to gumbel[i] is finite) */
 void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, void* stream);
+/* scoring: logprob[r] = logits[r, target[r]] - logsumexp(logits[r, 0:V]) over `rows` fp32 rows of stride ldl floats (ldl >= V; V and
+ * the row starts need no alignment; columns V..ldl are never read).  -inf entries are legal while one entry of the row is finite; a
+ * -inf target gives -inf.  target[r] in [0, V). */
+void vck_token_logprob(const float* logits, int ldl, const int* target, float* logprob, int rows, int V, void* stream);
 void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w, uint16_t* xg, int B,
                           int D, int npart, void* stream);
 void vck_advance(int* step_dev, int* pos_dev, int* ctx_dev, void* stream);

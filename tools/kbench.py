@@ -576,6 +576,74 @@ def bench_extend_attn():
                       f"{byts / us / 1e3 / 8000:.2f} of 8 TB/s", flush=True)
 
 
+def bench_token_logprob():
+    """token_logprob_kernel over [rows, 32000] fp32 logits: time and the fraction of the 8 TB/s HBM peak its one pass over the rows is;
+    beside it the greedy row scan of select_embed_kernel (argmax, one workgroup of 1024 threads per row) over the same buffer"""
+    V = 32000
+    stride = int(lib.vck_row_state_stride())
+    for rows in (128, 1024):
+        lg = [torch.randn(rows, V, device=dev) * 3 for _ in range(4)]   # 4 x 131 MB at 1024 rows: past the 256 MB MALL in rotation
+        tgt = torch.randint(0, V, (rows,), dtype=torch.int32, device=dev)
+        out = torch.zeros(rows, device=dev)
+        it = [0]
+
+        def f():
+            it[0] += 1
+            lib.vck_token_logprob(P(lg[it[0] % 4]), V, P(tgt), P(out), rows, V, None)
+        us = timeit(f, iters=40)
+        gbs = rows * V * 4 / us / 1e3
+        print(f"token_logprob rows {rows:4d} V {V}: {us:7.1f} us  {gbs:7.1f} GB/s = {gbs / 8000:.2f} of 8 TB/s", flush=True)
+        rs = torch.zeros((rows, stride), dtype=torch.int32, device=dev)
+        rs[:, 0] = 1    # RS_ACTIVE
+        rs[:, 5] = -1   # RS_EOS: none
+        rs[:, 14] = torch.arange(rows, dtype=torch.int32, device=dev)   # RS_OUT_OFF
+        nxt = torch.zeros(rows, dtype=torch.int32, device=dev)
+        ids = torch.zeros(rows, dtype=torch.int32, device=dev)
+
+        def g():
+            it[0] += 1
+            lib.vck_select_embed(P(lg[it[0] % 4]), V, P(rs), P(nxt), P(ids), None, None, None, None, None, 4096, 16, V, rows, 0, None)
+        us = timeit(g, iters=40)
+        gbs = rows * V * 4 / us / 1e3
+        print(f"argmax scan   rows {rows:4d} V {V}: {us:7.1f} us  {gbs:7.1f} GB/s = {gbs / 8000:.2f} of 8 TB/s", flush=True)
+
+
+def bench_score_head():
+    """The score path's chunk at 7b dims (D 4096, V 32000): gathered final RMSNorm + lm_head + token_logprob over M scored rows (16 .. 1024), the
+    lm_head as ceil(M / 32) passes of the weight-streaming GEMV (packed weights) against one GEMM — the crossover behind
+    SCORE_GEMV_ROWS (engine_llm.inc) at the lm_head's shape."""
+    D, V = 4096, 32000
+    x = torch.randn(8 * 1216, D, device=dev)
+    gw = torch.rand(D, device=dev) + 0.5
+    Ws = [bf16(V, D, scale=0.02) for _ in range(2)]
+    Wp = [torch.zeros_like(w) for w in Ws]
+    for w, wp in zip(Ws, Wp):
+        lib.vck_pack_weight(P(w), P(wp), V, D, None)
+    ws = torch.zeros(16 << 20, device=dev)
+    for M in (16, 32, 64, 128, 160, 1024):
+        idx = torch.randperm(8 * 1216, device=dev)[:M].to(torch.int32)
+        tgt = torch.randint(0, V, (M,), dtype=torch.int32, device=dev)
+        xn = torch.zeros((M + 32, D), dtype=torch.bfloat16, device=dev)
+        lg = torch.zeros((M + 32, V), device=dev)
+        out = torch.zeros(M, device=dev)
+        it = [0]
+
+        def run(gemv):
+            it[0] += 1
+            lib.vck_rmsnorm(P(x), P(idx), P(gw), P(xn), M, D, C.c_float(1e-5), None)
+            if gemv:
+                for m0 in range(0, M, 32):
+                    lib.vck_gemv_ex(P(xn[m0:]), P(Wp[it[0] % 2]), None, P(lg[m0:]), None, None, None, None, 16, C.c_float(1e-5),
+                                    None, None, 0, min(32, M - m0), V, D, V, 1, None)
+            else:
+                lib.vck_gemm_ws(P(xn), P(Ws[it[0] % 2]), None, P(lg), M, V, D, D, D, V, 3, P(ws), C.c_size_t(64 << 20), None)
+            lib.vck_token_logprob(P(lg), V, P(tgt), P(out), M, V, None)
+        uv = timeit(lambda: run(True), iters=20)
+        ug = timeit(lambda: run(False), iters=20)
+        print(f"score_head M{M:5d}: norm + GEMV x{(M + 31) // 32:2d} + logprob {uv:8.1f} us | norm + GEMM + logprob {ug:8.1f} us -> "
+              f"{'GEMV' if uv < ug else 'GEMM'}", flush=True)
+
+
 def bench_attn():
     for (B, H, T, hd, causal, name) in [(8, 32, 1216, 128, 1, "llm prefill"), (24, 16, 577, 64, 0, "vit")]:
         Ts = (T + 63) // 64 * 64
@@ -613,6 +681,7 @@ if __name__ == "__main__":
              "gemv13": bench_gemv13, "gemv_pair": bench_gemv_pair, "gemv_rows": bench_gemv_rows, "dattn_rows": bench_dattn_rows,
              "gemm_f8": bench_gemm_f8, "gemv_rows8": bench_gemv_rows8, "gemv_wide": bench_gemv_wide, "gemm_chunk": bench_gemm_chunk,
              "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,
-             "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn}
+             "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn, "token_logprob": bench_token_logprob,
+             "score_head": bench_score_head}
     for w in what:
         table[w]()

@@ -34,6 +34,7 @@ using namespace vc;
 static const int IMAGE_TOKEN_INDEX = -200;  // vcoder_llava/constants.py:5
 static const int SEG_TOKEN_INDEX = -300;    // constants.py:8
 static const int DEPTH_TOKEN_INDEX = -400;  // constants.py:11
+static const int IGNORE_INDEX = -100;       // constants.py:4
 static const int VC_MAX_ROWS = 16;          // sequences one prefill / one session loop handles
 // The prefill's RMSNorm output rows are padded by 64 elements: with both GEMM operands at a row stride of exactly 2^13
 // bytes (K = 4096 bf16) the 9728 x 12288 QKV GEMM of the 7b model ran 19 % slower (915 vs 770 us; address aliasing
@@ -185,6 +186,17 @@ struct vc_model {
     float* attn_out = nullptr;
     size_t attn_cap = 0;
     Buf attn_q;                   // roped q of a decode step with output_attentions
+    // token scores of the NEXT vc_prefill / vc_extend (vc_request_token_scores; one-shot): the caller's labels [B, T] (a copy), the host
+    // buffers the call fills (cap elements each), and — while that call runs — score_on
+    std::vector<int64_t> score_labels;
+    int score_B = 0, score_T = 0;
+    float* score_out = nullptr;
+    int64_t* score_labels_out = nullptr;
+    size_t score_cap = 0;
+    bool score_on = false;
+    std::vector<int64_t> spliced_labels;   // [B, S] of the prefill being scored (IGNORE_INDEX on feature rows and right padding)
+    Buf sc_idx, sc_lp, sc_xn, sc_logits;   // scored rows: indices | targets, log-probs, normed rows and logits of one chunk
+    bool tok_stale = false;       // vc_rewind ran: the token the last step selected on the device no longer continues the sequence
     bool plan_only = false;       // do_prefill stops behind the splice plan (vc_plan_spliced_len): no tower pass, no state change
     int reserve_new = 64;         // KV slots a vc_prefill keeps free behind the prompt (vc_model_reserve_decode)
     int layer_limit = 0;          // > 0: a prefill evaluates only the first layer_limit decoder layers (vc_model_set_layer_limit)
@@ -230,6 +242,15 @@ namespace {
 #include "engine_llm.inc"
 }  // namespace
 
+static void clear_score_request(vc_model* m) {
+    m->score_labels.clear();
+    m->score_B = m->score_T = 0;
+    m->score_out = nullptr;
+    m->score_labels_out = nullptr;
+    m->score_cap = 0;
+    m->score_on = false;
+}
+
 // the one-shot requests of the NEXT prefill / generate call (vc_set_image_counts, vc_set_attention_mask,
 // vc_request_hidden_states) never outlive that call — also not when it fails half-way (a stale mask would be applied to,
 // and a stale host pointer written by, some later call)
@@ -242,6 +263,7 @@ struct OneShotReset {
         m->hidden_cap = 0;
         m->attn_out = nullptr;
         m->attn_cap = 0;
+        clear_score_request(m);
     }
 };
 

@@ -188,7 +188,7 @@ VC_API void vc_model_destroy(vc_model* m) {
                    &m->s_vq, &m->s_vk, &m->s_vv, &m->s_vattn, &m->s_vh, &m->s_sel, &m->s_mid, &m->s_feats, &m->s_xn, &m->s_qkv,
                    &m->s_q, &m->s_attn, &m->s_h, &m->s_kc, &m->s_vc, &m->s_xl, &m->pp_src, &m->pp_sq, &m->pp_tmp, &m->pp_out,
                    &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre,
-                   &m->ext_tok})
+                   &m->ext_tok, &m->sc_idx, &m->sc_lp, &m->sc_xn, &m->sc_logits})
         b->release();
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
@@ -578,6 +578,28 @@ VC_API int vc_clear_attention_mask(vc_model* m) {
     return VC_OK;
 }
 
+/* Token scores of the NEXT vc_prefill (labels [B, T] aligned with its ids) or vc_extend (labels [B, n] aligned with its tok), one-shot:
+ * that call fills logprobs (host, [B, S] resp. [B, n]) with log p(label) of every labelled position and 0 elsewhere, and
+ * spliced_labels (may be NULL) with the labels as the splice laid them out.  The labels are copied here; the output buffers must stay
+ * valid until that call returns.  See include/vcoder_hip.h. */
+VC_API int vc_request_token_scores(vc_model* m, const int64_t* labels, int B, int T, float* logprobs, int64_t* spliced_labels,
+                                   size_t cap) {
+    if (!m) return VC_ERR_INVALID;
+    clear_score_request(m);
+    if (!labels) return VC_OK;   // NULL cancels a pending request
+    if (!logprobs || B < 1 || T < 1) {
+        m->ctx->err = "vc_request_token_scores needs labels [B, T] and a logprobs buffer";
+        return VC_ERR_INVALID;
+    }
+    m->score_labels.assign(labels, labels + (size_t)B * T);
+    m->score_B = B;
+    m->score_T = T;
+    m->score_out = logprobs;
+    m->score_labels_out = spliced_labels;
+    m->score_cap = cap;
+    return VC_OK;
+}
+
 /* KV-cache slots the next vc_prefill keeps free behind the prompt for vc_decode_step (default 64; clamped to
  * max_position_embeddings).  A decode loop that outruns the reserve still works — the cache grows, at the cost of a copy. */
 VC_API int vc_model_reserve_decode(vc_model* m, int max_new_tokens) {
@@ -593,7 +615,15 @@ VC_API int vc_prefill(vc_model* m, const int64_t* ids, int B, int T, const float
     OneShotReset one_shot{m};
     GUARD_BEGIN
     USE_DEVICE(m->ctx);
-    m->cur_pos = -1;
+    if (!m->score_labels.empty()) {
+        // vc_request_token_scores: a scored prefill is refused while the session's cache and position are still what they were — the
+        // shape here, the label range and the capacity behind the splice plan in do_prefill, which drops the position only then
+        REQUIRE(ids && m->score_B == B && m->score_T == T, VC_ERR_INVALID, "labels are [%d, %d], input_ids [%d, %d]", m->score_B,
+                m->score_T, B, T);
+        m->score_on = true;
+    } else {
+        m->cur_pos = -1;
+    }
     do_prefill(m, ids, B, T, img, seg, depth, pixels_on_device, has_attention_mask, -std::max(m->reserve_new, 1), true, S_out);
     ensure_out_ids(m, B, 1);
     finish_prefill(m, session_kv(m), logits_all);
@@ -719,9 +749,30 @@ VC_API int vc_reorder_cache(vc_model* m, const int32_t* src_rows, int B) {
     GUARD_END(m->ctx)
 }
 
+/* The session's loop steps back to position P: cached rows >= P are dead, nothing is copied.  See include/vcoder_hip.h. */
+VC_API int vc_rewind(vc_model* m, int P) {
+    if (!m) return VC_ERR_INVALID;
+    GUARD_BEGIN
+    USE_DEVICE(m->ctx);
+    REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_rewind before vc_prefill");
+    REQUIRE(P >= m->curS && P <= m->cur_pos, VC_ERR_INVALID, "vc_rewind to %d: the prompt ends at %d, the loop stands at %d", P,
+            m->curS, m->cur_pos);
+    if (P != m->cur_pos) {
+        const std::vector<int> pos(m->curB, P);   // RS_POS of every row (the hidden-key mask of the prefill stays in force)
+        HIPCHK(hipMemcpy2DAsync(m->rows.as<int>() + RS_POS, (size_t)RS_STRIDE * 4, pos.data(), 4, 4, m->curB, hipMemcpyHostToDevice,
+                                m->st));
+        HIPCHK(hipStreamSynchronize(m->st));
+        m->cur_pos = P;
+        m->tok_stale = true;
+    }
+    GUARD_END(m->ctx)
+}
+
 // one cached step of the session's loop (vc_decode_step; vc_extend in precision modes "strict" / "split")
 void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* next_tok) {
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_decode_step before vc_prefill");
+    REQUIRE(tok || !m->tok_stale, VC_ERR_STATE,
+            "vc_decode_step(tok = NULL) after vc_rewind: the token selected on the device belongs to the rows that were dropped");
     if (m->cur_pos + 1 > m->capS) grow_kv(m, m->cur_pos + 1);
     const int B = m->curB;
     if (tok) {
@@ -749,6 +800,7 @@ void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* n
         HIPCHK(hipGraphLaunch(m->graph, m->st));
     }
     m->cur_pos += 1;
+    m->tok_stale = false;
     if (logits) HIPCHK(hipMemcpyAsync(logits, m->logits.p, (size_t)B * m->c.vocab * 4, hipMemcpyDeviceToHost, m->st));
     if (next_tok) HIPCHK(hipMemcpyAsync(next_tok, m->next_tok.p, B * 4, hipMemcpyDeviceToHost, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
@@ -775,6 +827,7 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
             m->hidden_out = nullptr;
             m->attn_out = nullptr;
             m->hidden_cap = m->attn_cap = 0;
+            clear_score_request(m);
         }
     } requests{m};
     GUARD_BEGIN
@@ -792,6 +845,17 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
     REQUIRE(!attn_req || P + n <= 4096, VC_ERR_INVALID, "output_attentions: at most 4096 positions");
     REQUIRE(!hidden_req || hidden_cap >= (size_t)(L + 1) * B * n * c.hidden, VC_ERR_INVALID, "hidden-state buffer too small");
     REQUIRE(!attn_req || attn_cap >= (size_t)L * B * c.heads * n * (P + n), VC_ERR_INVALID, "attention buffer too small");
+    const bool scored = !m->score_labels.empty();   // vc_request_token_scores: labels [B, n] aligned with tok
+    const int64_t* labels = m->score_labels.data();
+    if (scored) {
+        REQUIRE(m->score_B == B && m->score_T == n, VC_ERR_INVALID, "labels are [%d, %d], the tokens [%d, %d]", m->score_B, m->score_T,
+                B, n);
+        REQUIRE(m->score_cap >= (size_t)B * n, VC_ERR_INVALID, "token-score buffers hold %zu elements, the call yields [%d, %d]",
+                m->score_cap, B, n);
+        for (size_t i = 0; i < (size_t)B * n; ++i)
+            REQUIRE(labels[i] == IGNORE_INDEX || (labels[i] >= 0 && labels[i] < V), VC_ERR_INDEX, "Target %lld is out of bounds.",
+                    (long long)labels[i]);
+    }
     if (m->precision != 0) {
         // "strict" / "split": n cached steps of the session's loop (the same launches as n vc_decode_step calls); the per-step
         // diagnostics are gathered into the [.., B, n, ..] layouts of the call
@@ -799,6 +863,16 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
         std::vector<int32_t> col(B);
         std::vector<float> step_lg((size_t)B * V), hs, at;
         if (attn_req) std::fill(attn_req, attn_req + (size_t)L * B * H * n * (P + n), 0.f);
+        // scores: step t's logits [B, V] against label t + 1 (unlabelled rows against token 0, dropped below); one copy at the end
+        std::vector<int> tgt((size_t)std::max(n - 1, 1) * B, 0);
+        if (scored && n > 1) {
+            for (int t = 0; t + 1 < n; ++t)
+                for (int b = 0; b < B; ++b)
+                    if (labels[(size_t)b * n + t + 1] != IGNORE_INDEX) tgt[(size_t)t * B + b] = (int)labels[(size_t)b * n + t + 1];
+            m->sc_idx.ensure(tgt.size() * 4);
+            m->sc_lp.ensure(tgt.size() * 4);
+            HIPCHK(hipMemcpyAsync(m->sc_idx.p, tgt.data(), tgt.size() * 4, hipMemcpyHostToDevice, m->st));
+        }
         for (int t = 0; t < n; ++t) {
             for (int b = 0; b < B; ++b) col[b] = tok[(size_t)b * n + t];
             if (hidden_req) {
@@ -812,6 +886,9 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
                 m->attn_cap = at.size();
             }
             decode_step_impl(m, col.data(), step_lg.data(), nullptr);
+            if (scored && t + 1 < n)
+                launch_token_logprob(m->logits.as<float>(), V, m->sc_idx.as<int>() + (size_t)t * B, m->sc_lp.as<float>() + (size_t)t * B, B,
+                                     V, m->st);
             if (logits_all)
                 for (int b = 0; b < B; ++b) memcpy(logits_all + ((size_t)b * n + t) * V, step_lg.data() + (size_t)b * V, (size_t)V * 4);
             if (hidden_req)
@@ -822,6 +899,18 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
                     memcpy(attn_req + (e * n + t) * (P + n), at.data() + e * (P + t + 1), (size_t)(P + t + 1) * 4);
         }
         if (logits_last) memcpy(logits_last, step_lg.data(), step_lg.size() * 4);
+        if (scored) {
+            std::fill(m->score_out, m->score_out + (size_t)B * n, 0.f);
+            if (n > 1) {
+                std::vector<float> lp((size_t)(n - 1) * B);
+                HIPCHK(hipMemcpyAsync(lp.data(), m->sc_lp.p, lp.size() * 4, hipMemcpyDeviceToHost, m->st));
+                HIPCHK(hipStreamSynchronize(m->st));
+                for (int t = 0; t + 1 < n; ++t)
+                    for (int b = 0; b < B; ++b)
+                        if (labels[(size_t)b * n + t + 1] != IGNORE_INDEX) m->score_out[(size_t)b * n + t + 1] = lp[(size_t)t * B + b];
+            }
+            if (m->score_labels_out) std::copy(labels, labels + (size_t)B * n, m->score_labels_out);
+        }
         return VC_OK;
     }
     if (P + n > m->capS) grow_kv(m, P + n);
@@ -833,6 +922,11 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
     HIPCHK(hipMemcpyAsync(m->ext_tok.p, tok, (size_t)B * n * 4, hipMemcpyHostToDevice, m->st));
     const bool all_rows = logits_all != nullptr || B * n <= EXTEND_GEMV_ROWS;
     run_extend(m, m->ext_tok.as<int>(), B, n, logits_all != nullptr);
+    if (scored) {   // (the lm_head ran over every row: score them in place; otherwise the labelled rows through the score path)
+        if (all_rows) score_logits_rows(m, m->logits_all.as<float>(), labels, B, n, m->score_out);
+        else score_labelled_rows(m, m->x.as<float>(), labels, B, n, m->score_out);
+        if (m->score_labels_out) std::copy(labels, labels + (size_t)B * n, m->score_labels_out);
+    }
     if (all_rows)   // each sequence's last row -> the loop's logits rows (what a decode step leaves there)
         HIPCHK(hipMemcpy2DAsync(m->logits.p, (size_t)V * 4, m->logits_all.as<float>() + (size_t)(n - 1) * V, (size_t)n * V * 4,
                                 (size_t)V * 4, B, hipMemcpyDeviceToDevice, m->st));
@@ -845,6 +939,7 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
     const LoopView v = session_view(m);
     launch_select_embed(select_args(m, v, v.logits, B, 0), m->st);
     m->cur_pos = P + n;
+    m->tok_stale = false;
     if (logits_all)
         HIPCHK(hipMemcpyAsync(logits_all, m->logits_all.p, (size_t)B * n * V * 4, hipMemcpyDeviceToHost, m->st));
     if (logits_last) HIPCHK(hipMemcpyAsync(logits_last, m->logits.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, m->st));

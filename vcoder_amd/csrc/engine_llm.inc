@@ -5,15 +5,22 @@
 // splice planner (host).  One (kind, src) pair per destination row of inputs_embeds.
 struct RowSrc { int kind, src; };
 
+// `labels` [B, T] (nullptr: none announced): lab_out[b] receives one label per destination row, by the plan the embeddings follow
+// — a text row carries the label of its id, a feature row IGNORE_INDEX, text the DS variant drops between <image> and <seg> drops
+// its label with it, and whatever stands at a placeholder position of `labels` is never read (vcoder_ds_llava_arch.py:176, 203-204,
+// 213-216, 225-228, 239-241, 254-257, 269-270; a row without placeholders passes its labels through, :181-208).
 void plan_rows(vc_model* m, const int64_t* ids, int B, int T, bool has_seg, const std::vector<bool>* depth_zero,
-               int R, std::vector<std::vector<RowSrc>>& out) {
+               int R, std::vector<std::vector<RowSrc>>& out, const int64_t* labels = nullptr,
+               std::vector<std::vector<int64_t>>* lab_out = nullptr) {
     const int variant = m->c.variant;
     int img_i = 0, seg_i = 0, dep_i = 0;
+    std::vector<int64_t>* lab = nullptr;   // the labels of the row being planned
     auto text = [&](std::vector<RowSrc>& rows, const int64_t* p, int n) {
         for (int i = 0; i < n; ++i) {
             REQUIRE(p[i] >= 0 && p[i] < m->c.vocab, VC_ERR_INDEX,
                     "index out of range in self (id %lld reached the embedding lookup)", (long long)p[i]);
             rows.push_back({0, (int)p[i]});
+            if (lab) lab->push_back(labels[(p - ids) + i]);
         }
     };
     // features[idx] of the reference: the block of sample idx — R rows per image, all images of the sample flattened
@@ -23,7 +30,10 @@ void plan_rows(vc_model* m, const int64_t* ids, int B, int T, bool has_seg, cons
         const int nblocks = first.empty() ? m->feat_rows[mod] / R : (int)first.size() - 1;
         REQUIRE(idx < nblocks, VC_ERR_INDEX, "index %d is out of bounds for dimension 0 with size %d", idx, nblocks);
         const int i0 = first.empty() ? idx : first[idx], i1 = first.empty() ? idx + 1 : first[idx + 1];
-        for (int r = i0 * R; emit && r < i1 * R; ++r) rows.push_back({1, m->feat_off[mod] + r});
+        for (int r = i0 * R; emit && r < i1 * R; ++r) {
+            rows.push_back({1, m->feat_off[mod] + r});
+            if (lab) lab->push_back(IGNORE_INDEX);
+        }
     };
     auto find = [](const int64_t* p, int n, int tok) {
         for (int i = 0; i < n; ++i)
@@ -31,10 +41,12 @@ void plan_rows(vc_model* m, const int64_t* ids, int B, int T, bool has_seg, cons
         return -1;
     };
     out.assign(B, {});
+    if (labels && lab_out) lab_out->assign(B, {});
     for (int b = 0; b < B; ++b) {
         const int64_t* cur = ids + (size_t)b * T;
         int n = T;
         std::vector<RowSrc>& rows = out[b];
+        lab = labels && lab_out ? &(*lab_out)[b] : nullptr;
         int n_img = 0, n_seg = 0;
         for (int i = 0; i < T; ++i) {
             n_img += cur[i] == IMAGE_TOKEN_INDEX;
@@ -790,17 +802,21 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
     }
     if (m->ev[1]) HIPCHK(hipEventRecord(m->ev[1], m->st));
     std::vector<std::vector<RowSrc>> rows;
+    const int64_t* labels = m->score_on ? m->score_labels.data() : nullptr;   // announced by vc_request_token_scores, checked by vc_prefill
+    std::vector<std::vector<int64_t>> row_labels;
     if (text_only) {
         rows.assign(B, {});
+        if (labels) row_labels.assign(B, {});
         for (int b = 0; b < B; ++b)
             for (int t = 0; t < T; ++t) {
                 const int64_t id = ids[(size_t)b * T + t];
                 REQUIRE(id >= 0 && id < c.vocab, VC_ERR_INDEX, "index out of range in self (id %lld reached the embedding lookup)",
                         (long long)id);
                 rows[b].push_back({0, (int)id});
+                if (labels) row_labels[b].push_back(labels[(size_t)b * T + t]);
             }
     } else {
-        plan_rows(m, ids, B, T, seg != nullptr, depth ? &dz : nullptr, R, rows);
+        plan_rows(m, ids, B, T, seg != nullptr, depth ? &dz : nullptr, R, rows, labels, &row_labels);
     }
     size_t S = 0;
     bool unequal = false;
@@ -811,6 +827,20 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
     // quirk 6: unequal spliced lengths with an attention_mask and no labels die at vcoder_ds_llava_arch.py:295-297
     REQUIRE(!(unequal && has_mask), VC_ERR_UNEQUAL, "local variable '_new_labels' referenced before assignment");
     REQUIRE(S >= 1, VC_ERR_INVALID, "empty sequence");
+    if (labels) {   // [B, S]: shorter rows are right-padded with IGNORE_INDEX (:287-293)
+        m->spliced_labels.assign((size_t)B * S, IGNORE_INDEX);
+        for (int b = 0; b < B; ++b) std::copy(row_labels[b].begin(), row_labels[b].end(), m->spliced_labels.begin() + (size_t)b * S);
+        // what CrossEntropyLoss sees: the spliced labels behind the shift (a label the splice dropped, or at position 0, is never read).
+        // Nothing of the session's cache or position has been touched yet: a refused call leaves the previous loop usable.
+        for (int b = 0; b < B; ++b)
+            for (size_t s = 1; s < S; ++s) {
+                const int64_t l = m->spliced_labels[(size_t)b * S + s];
+                REQUIRE(l == IGNORE_INDEX || (l >= 0 && l < c.vocab), VC_ERR_INDEX, "Target %lld is out of bounds.", (long long)l);
+            }
+        REQUIRE(m->score_cap >= (size_t)B * S, VC_ERR_INVALID,
+                "token-score buffers hold %zu elements, the call yields [%d, %zu]", m->score_cap, B, S);
+        if (own_kv) m->cur_pos = -1;
+    }
     if (m->plan_only) {
         if (S_out) *S_out = (int)S;
         return;
@@ -876,6 +906,103 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
     if (S_out) *S_out = (int)S;
 }
 
+// ---- token scores (vc_request_token_scores): log p(label) of the labelled positions, without logits leaving the device ------------
+// Shift rule of [HF] LlamaForCausalLM.forward / the reference (vcoder_ds_llava_llama.py:95-106): labels[..., 1:] against
+// logits[..., :-1, :] — the row in front of position j scores label j, position 0 is never scored.
+// The rows of one launch sequence: the logits workspace is SCORE_CHUNK_ROWS x V floats however many rows carry a label
+// (131 MB at V = 32000).
+constexpr int SCORE_CHUNK_ROWS = 1024;
+// log p(tgt[i]) from residual row row_idx[i] of x [., D]: per chunk the final RMSNorm gathered by row index, the lm_head over the
+// chunk only, token_logprob_kernel over its logits — in the session's precision mode.  A bf16-mode chunk of up to SCORE_GEMV_ROWS rows
+// takes ONE pass of the packed lm_head's GEMV as last_row_logits does, more rows the GEMM: at the lm_head's shape (N 32000, K 4096)
+// every further GEMV pass streams the 262 MB weight again (+45 us) while the GEMM stays near 105 us up to 160 rows, so the
+// layer linears' EXTEND_GEMV_ROWS = 128 does not hold here (tools/kbench.py score_head, DESIGN.md 4.4c: 16 rows 68 | 102 us,
+// 32 rows 75 | 106, 64 rows 122 | 106, 128 rows 212 | 108).  The results land in m->sc_lp [row_idx.size()] on the device, in order;
+// nothing is synchronised.
+constexpr int SCORE_GEMV_ROWS = VC_GEMV_MAX_M;
+void score_rows(vc_model* m, const float* x, const std::vector<int>& row_idx, const std::vector<int>& tgt) {
+    const vc_model_cfg& c = m->c;
+    const int D = c.hidden, V = c.vocab, n = (int)row_idx.size();
+    if (n == 0) return;
+    const int chunk_cap = (int)rup(std::min(n, SCORE_CHUNK_ROWS), 32);   // (a GEMV pass holds 32 token slots)
+    const int ldx = split_ld(D);
+    m->sc_idx.ensure((size_t)2 * n * 4);
+    m->sc_lp.ensure((size_t)n * 4);
+    m->sc_xn.ensure((size_t)chunk_cap * std::max((size_t)D * 4, (size_t)ldx * 2), true);
+    m->sc_logits.ensure((size_t)chunk_cap * V * 4, true);
+    int* idx_dev = m->sc_idx.as<int>();
+    int* tgt_dev = idx_dev + n;
+    HIPCHK(hipMemcpyAsync(idx_dev, row_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, m->st));
+    HIPCHK(hipMemcpyAsync(tgt_dev, tgt.data(), (size_t)n * 4, hipMemcpyHostToDevice, m->st));
+    float* lg = m->sc_logits.as<float>();
+    for (int r0 = 0; r0 < n; r0 += SCORE_CHUNK_ROWS) {
+        const int nr = std::min(SCORE_CHUNK_ROWS, n - r0);
+        if (m->precision == 1) {
+            launch_rmsnorm_f32(x, idx_dev + r0, m->final_norm, m->sc_xn.as<float>(), nr, D, c.rms_eps, m->st);
+            gemm32(m, m->sc_xn.as<float>(), m->lm_head, nullptr, lg, nr, V, D, D, D, V, EPI_F32);
+        } else if (m->precision == 2) {
+            launch_rmsnorm_split(x, idx_dev + r0, m->final_norm, m->sc_xn.as<bf16_t>(), nr, D, c.rms_eps, ldx, D, m->st);
+            gemm_split(m, m->sc_xn.as<bf16_t>(), m->lm_head, nullptr, lg, nr, V, D, V, EPI_F32, ldx);
+        } else {
+            launch_rmsnorm_rows(x, idx_dev + r0, m->final_norm, m->sc_xn.as<bf16_t>(), nr, D, c.rms_eps, m->st);
+            if (nr <= SCORE_GEMV_ROWS) {
+                LoopView lv{};   // the lm_head GEMV needs a stream only
+                lv.st = m->st;
+                gemv(m, lv, m->sc_xn.as<bf16_t>(), m->lm_head_p, nullptr, lg, nr, V, D, V, GEMV_F32);
+            } else {
+                gemm(m, m->sc_xn.as<bf16_t>(), m->lm_head, nullptr, lg, nr, V, D, V, EPI_F32);
+            }
+        }
+        launch_token_logprob(lg, V, tgt_dev + r0, m->sc_lp.as<float>() + r0, nr, V, m->st);
+    }
+}
+// the labelled positions of `labels` [B, n] (n rows per sequence in x): row b n + j - 1 scores label j >= 1.  The caller's buffer
+// receives [B, n] floats, 0 where nothing is scored.  One device-to-host copy of the scored entries; synchronises the stream.
+void score_labelled_rows(vc_model* m, const float* x, const int64_t* labels, int B, int n, float* out) {
+    std::vector<int> row_idx, tgt;
+    for (int b = 0; b < B; ++b)
+        for (int j = 1; j < n; ++j) {
+            const int64_t l = labels[(size_t)b * n + j];
+            if (l == IGNORE_INDEX) continue;
+            REQUIRE(l >= 0 && l < m->c.vocab, VC_ERR_INDEX, "Target %lld is out of bounds.", (long long)l);
+            row_idx.push_back(b * n + j - 1);
+            tgt.push_back((int)l);
+        }
+    std::fill(out, out + (size_t)B * n, 0.f);
+    if (row_idx.empty()) return;
+    score_rows(m, x, row_idx, tgt);
+    std::vector<float> lp(row_idx.size());
+    HIPCHK(hipMemcpyAsync(lp.data(), m->sc_lp.p, lp.size() * 4, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipStreamSynchronize(m->st));
+    for (size_t i = 0; i < lp.size(); ++i) out[row_idx[i] + 1] = lp[i];
+}
+// logits rows [B * n, V] already on the device (a continuation whose lm_head ran over every row): every row is scored in place —
+// row b n + j - 1 against label j, unlabelled rows against token 0 and dropped on the host
+void score_logits_rows(vc_model* m, const float* logits, const int64_t* labels, int B, int n, float* out) {
+    const int M = B * n;
+    std::vector<int> tgt(M, 0);
+    bool any = false;
+    for (int b = 0; b < B; ++b)
+        for (int j = 1; j < n; ++j) {
+            const int64_t l = labels[(size_t)b * n + j];
+            if (l == IGNORE_INDEX) continue;
+            tgt[b * n + j - 1] = (int)l;
+            any = true;
+        }
+    std::fill(out, out + (size_t)M, 0.f);
+    if (!any) return;
+    m->sc_idx.ensure((size_t)M * 4);
+    m->sc_lp.ensure((size_t)M * 4);
+    HIPCHK(hipMemcpyAsync(m->sc_idx.p, tgt.data(), (size_t)M * 4, hipMemcpyHostToDevice, m->st));
+    launch_token_logprob(logits, m->c.vocab, m->sc_idx.as<int>(), m->sc_lp.as<float>(), M, m->c.vocab, m->st);
+    std::vector<float> lp(M);
+    HIPCHK(hipMemcpyAsync(lp.data(), m->sc_lp.p, (size_t)M * 4, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipStreamSynchronize(m->st));
+    for (int b = 0; b < B; ++b)
+        for (int j = 1; j < n; ++j)
+            if (labels[(size_t)b * n + j] != IGNORE_INDEX) out[b * n + j] = lp[b * n + j - 1];
+}
+
 // decoder stack over the spliced batch + last-row logits (m->logits [B,V]); keys / values go to `kv`
 void finish_prefill(vc_model* m, const KvTarget& kv, float* logits_all_host) {
     const vc_model_cfg& c = m->c;
@@ -919,6 +1046,10 @@ void finish_prefill(vc_model* m, const KvTarget& kv, float* logits_all_host) {
         }
         HIPCHK(hipMemcpyAsync(logits_all_host, m->logits_all.p, Mr * c.vocab * 4, hipMemcpyDeviceToHost, m->st));
     }
+    if (m->score_on) {   // vc_request_token_scores: the labelled rows only, whatever else was asked for
+        score_labelled_rows(m, m->x.as<float>(), m->spliced_labels.data(), B, S, m->score_out);
+        if (m->score_labels_out) std::copy(m->spliced_labels.begin(), m->spliced_labels.end(), m->score_labels_out);
+    }
     HIPCHK(hipStreamSynchronize(m->st));  // `idx` is host memory
     m->hidden_out = nullptr;               // one-shot
     m->attn_out = nullptr;
@@ -933,5 +1064,6 @@ void arm_session_rows(vc_model* m, const GenParams& g, const int* tail) {
     HIPCHK(hipMemcpyAsync(m->rows.p, rec.data(), rec.size() * 4, hipMemcpyHostToDevice, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
     m->cur_pos = S;
+    m->tok_stale = false;
 }
 

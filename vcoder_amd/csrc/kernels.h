@@ -391,6 +391,9 @@ void launch_stamp_accumulate(unsigned* stamps, int n, int layers, unsigned long 
 void launch_embed_tokens_ssq(const int* tok, const bf16_t* embed, float* x, float* ssq, const float* xg_w, bf16_t* xg, int B, int D, int npart,
                              hipStream_t s, int xg_G = 0, const bf16_t* embed_lo = nullptr);
 void launch_advance(int* step_dev, int* pos_dev, int* ctx_dev, hipStream_t s);
+// scoring: logprob[r] = logits[r, target[r]] - logsumexp(logits[r, 0:V]) for `rows` rows of stride ldl floats (ldl >= V; any V, any
+// alignment), one workgroup per row, fp32 throughout (select.hip)
+void launch_token_logprob(const float* logits, int ldl, const int* target, float* logprob, int rows, int V, hipStream_t s);
 // test hook: u[i] = the sampler's uniform for hash value h[i], gumbel[i] = -log(-log(u[i]))
 void launch_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, hipStream_t s);
 

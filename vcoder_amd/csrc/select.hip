@@ -399,6 +399,70 @@ void launch_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, hip
     VC_LAUNCH(uniform_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, s, h, u, gumbel, n);
 }
 
+// ---- log-probability of one target token per logits row (scoring: forward(labels=), score()) -----------------------------------
+//   logprob[r] = logits[r, target[r]] - logsumexp(logits[r, 0:V])       [HF] llama/modeling_llama.py: CrossEntropyLoss over the
+//   shifted logits, per position and without the mean (the caller owns the reduction)
+// One pass over the row: every lane keeps a running (max, sum of exp(v - max)) pair, the pairs merge through the wave (6 xor steps),
+// then across the workgroup's waves through LDS, as the row kernels of norm.hip reduce.  The maximum is subtracted, so rows whose
+// |logit| lies far above 88 stay finite; -inf entries (a filtered distribution) add nothing as long as one entry is finite, and a -inf
+// target gives -inf.  All arithmetic fp32 (expf / logf, not the fast forms: the result is compared at the 1e-6 level).
+// One workgroup per row: the callers score tens to a few thousand rows, and the 128 KB a row of V = 32000 reads takes microseconds —
+// splitting a row over workgroups would buy nothing at these sizes.
+// 16-byte loads where the row start allows (base and ldl multiples of 4 floats), with a scalar head up to the first aligned column
+// and a scalar tail; nothing beyond column V - 1 of a row is read.
+VC_DEV void lse_add(float& m, float& s, float v) {
+    if (v > m) {   // (-inf never enters: m starts at -inf and v > m fails; NaN neither — a NaN logit is the caller's bug)
+        s = s * expf(m - v) + 1.0f;   // m == -inf: s is 0 and expf(-inf) is 0
+        m = v;
+    } else if (v > -INFINITY) {
+        s += expf(v - m);
+    }
+}
+VC_DEV void lse_merge(float& m, float& s, float om, float os) {
+    const float nm = fmaxf(m, om);
+    if (nm > -INFINITY) s = s * expf(m - nm) + os * expf(om - nm);
+    m = nm;
+}
+constexpr int LOGPROB_THREADS = 256;
+__global__ __launch_bounds__(LOGPROB_THREADS) void token_logprob_kernel(const float* __restrict__ logits, int ldl,
+                                                                         const int* __restrict__ target,
+                                                                         float* __restrict__ logprob, int V) {
+    __shared__ float red_m[LOGPROB_THREADS / 64], red_s[LOGPROB_THREADS / 64];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* lg = logits + (size_t)r * ldl;
+    // columns [0, head) and [body_end, V) go one float at a time, [head, body_end) in aligned float4s
+    const int mis = (int)((reinterpret_cast<uintptr_t>(lg) >> 2) & 3);
+    const int head = min(V, (4 - mis) & 3);
+    const int body_end = head + ((V - head) & ~3);
+    float mx = -INFINITY, sm = 0.f;
+    if (tid < head) lse_add(mx, sm, lg[tid]);
+    for (int i = head + tid * 4; i < body_end; i += LOGPROB_THREADS * 4) {
+        const f32x4 v = ld16f(lg + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lse_add(mx, sm, v[e]);
+    }
+    if (body_end + tid < V) lse_add(mx, sm, lg[body_end + tid]);
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        const float om = shfl_xor(mx, k), os = shfl_xor(sm, k);
+        lse_merge(mx, sm, om, os);
+    }
+    if (lane == 0) { red_m[wave] = mx; red_s[wave] = sm; }
+    __syncthreads();
+    if (tid == 0) {
+        mx = red_m[0];
+        sm = red_s[0];
+#pragma unroll
+        for (int w = 1; w < LOGPROB_THREADS / 64; ++w) lse_merge(mx, sm, red_m[w], red_s[w]);   // fixed order: bit-reproducible
+        const float t = lg[target[r]];
+        logprob[r] = t > -INFINITY ? (t - mx) - logf(sm) : -INFINITY;
+    }
+}
+void launch_token_logprob(const float* logits, int ldl, const int* target, float* logprob, int rows, int V, hipStream_t s) {
+    if (rows <= 0) return;
+    VC_LAUNCH(token_logprob_kernel, dim3((unsigned)rows), dim3(LOGPROB_THREADS), 0, s, logits, ldl, target, logprob, V);
+}
+
 // embedding + sum-of-squares partials for tokens supplied by the host (vc_decode_step with explicit tokens)
 __global__ __launch_bounds__(256) void embed_tokens_ssq_kernel(const int* tok, const bf16_t* embed, float* x, float* ssq,
                                                                const float* xg_w, bf16_t* xg, int B, int D, int npart, int G,

@@ -337,8 +337,11 @@ class HipEngine:
 
     def prefill(self, input_ids, images, segs=None, depths=None, has_attention_mask: bool = False,
                 all_logits: bool = False, reserve: Optional[int] = None, attention_mask=None, hidden_states: bool = False,
-                attentions: bool = False):
-        """-> (logits_last [B,V], logits_all [B,S,V] or None, S).  reserve: decode_step calls the caller intends to make
+                attentions: bool = False, labels=None):
+        """-> (logits_last [B,V], logits_all [B,S,V] or None, S).  labels [B,T] (aligned with input_ids, -100 = not scored):
+        last_token_logprobs [B,S] receives log p(label) of every labelled position of the spliced sequence (0 elsewhere; HF's
+        shift: the row in front of a position scores it) and last_spliced_labels [B,S] the labels as the splice laid them out —
+        the lm_head runs over the scored rows only and no logits leave the device for it.  reserve: decode_step calls the caller intends to make
         (sizes the KV cache up front; a longer loop still works — the cache grows).  attention_mask [B,T]: padded batches —
         hidden positions are hidden as keys in this prefill and in the decode_step loop behind it (clear_attention_mask() ends
         that)."""
@@ -356,11 +359,16 @@ class HipEngine:
         last = np.empty((B, V), dtype=np.float32)
         S = C.c_int(0)
         self.last_hidden_states = self.last_attentions = None
+        self.last_token_logprobs = self.last_spliced_labels = None
         hid = att = None
         rows = self.cfg.num_patches + (1 if self.cfg.mm_vision_select_feature == "cls_patch" else 0)
         worst = T + rows * self._max_feature_blocks(ids)
         full = np.empty((B * worst * V,), dtype=np.float32) if all_logits else None
+        lab = self._labels(labels, B, T)
+        lp = sl = None
         try:
+            if lab is not None:
+                lp, sl = self._request_scores(lab, B * worst)
             if attentions:      # [L, B, H, S, S]
                 att = np.empty((self.cfg.num_hidden_layers, B, self.cfg.num_attention_heads, S_att, S_att), dtype=np.float32)
                 self._check(self.lib.vc_request_attentions(self._model, att.ctypes.data_as(C.c_void_p), C.c_size_t(att.size)))
@@ -376,14 +384,47 @@ class HipEngine:
             self.lib.vc_request_attentions(self._model, None, C.c_size_t(0))
             self.lib.vc_request_hidden_states(self._model, None, C.c_size_t(0))
             self.lib.vc_clear_attention_mask(self._model)
+            self._cancel_scores()
             raise
         self.last_S = self._step_pos = S.value
         self._cur_batch = B
         self._keep_hidden(hid, B, S.value)
+        if lab is not None:
+            self.last_token_logprobs = lp[: B * S.value].reshape(B, S.value).copy()
+            self.last_spliced_labels = sl[: B * S.value].reshape(B, S.value).copy()
         self.last_attentions = att
         return last, (full[: B * S.value * V].reshape(B, S.value, V).copy() if all_logits else None), S.value
 
     last_attentions = None
+    last_token_logprobs = None    # [B, S] / [B, n] float32 of the last prefill / extend with labels
+    last_spliced_labels = None    # int64, same shape
+
+    @staticmethod
+    def _labels(labels, B: int, n: int):
+        if labels is None:
+            return None
+        lab = np.ascontiguousarray(labels.detach().cpu().numpy() if _is_torch(labels) else np.asarray(labels), dtype=np.int64)
+        if lab.shape != (B, n):
+            raise ValueError(f"labels must be [{B},{n}], got {tuple(lab.shape)}")
+        return lab
+
+    def _request_scores(self, lab: np.ndarray, cap: int):
+        """announces labels for the next prefill / extend (one-shot); -> the host buffers that call fills"""
+        lp = np.zeros((cap,), dtype=np.float32)
+        sl = np.full((cap,), -100, dtype=np.int64)
+        self._check(self.lib.vc_request_token_scores(self._model, lab.ctypes.data_as(C.c_void_p), int(lab.shape[0]), int(lab.shape[1]),
+                                                     lp.ctypes.data_as(C.c_void_p), sl.ctypes.data_as(C.c_void_p), C.c_size_t(cap)))
+        return lp, sl
+
+    def _cancel_scores(self):
+        self.lib.vc_request_token_scores(self._model, None, 0, 0, None, None, C.c_size_t(0))   # NULL labels: cancel
+
+    def rewind(self, position: int):
+        """The loop steps back to `position` (the prompt's spliced length <= position <= the current position): the cached rows
+        behind it are dead, nothing is copied.  decode_step(tokens=None) is refused until an extend or a decode_step with explicit
+        tokens has run.  K candidate continuations are scored behind one prompt as K x (extend(labels=), rewind)."""
+        self._check(self.lib.vc_rewind(self._model, int(position)))
+        self._step_pos = int(position)
 
     def _keep_hidden(self, hid, B, S):
         """hidden states of the last prefill(hidden_states=True): [(L + 1), B, S, D] (the device packs them for the true S)"""
@@ -441,21 +482,27 @@ class HipEngine:
         self.last_hidden_states, self.last_attentions = hid, att
         return lg, nxt
 
-    def extend(self, tokens, all_logits: bool = True, hidden_states: bool = False, attentions: bool = False):
+    def extend(self, tokens, all_logits: bool = True, hidden_states: bool = False, attentions: bool = False, labels=None):
         """Multi-token continuation of the current loop: tokens [B, n] at positions P .. P+n-1 (P = the position the next
         decode_step would take), causal inside the chunk over every cached key.  -> (logits_last [B, V], logits_all [B, n, V] or
         None).  hidden_states / attentions: [(L + 1), B, n, D] / [L, B, H, n, P + n] in last_hidden_states / last_attentions.
-        decode_step continues at P + n."""
+        decode_step continues at P + n.  labels [B, n] (aligned with tokens): last_token_logprobs [B, n] = log p(label) of the
+        labelled positions 1 .. n-1 (label 0 has no row of this chunk in front of it), last_spliced_labels = the labels."""
         B = self._cur_batch
         tk = np.ascontiguousarray(tokens.detach().cpu().numpy() if _is_torch(tokens) else np.asarray(tokens), dtype=np.int32)
         if tk.ndim != 2 or tk.shape[0] != B or tk.shape[1] < 1:
             raise ValueError(f"expected tokens [{B}, n]")
         n, V, P = int(tk.shape[1]), self.cfg.vocab_size, self._step_pos
         self.last_hidden_states = self.last_attentions = None
+        self.last_token_logprobs = self.last_spliced_labels = None
         last = np.empty((B, V), dtype=np.float32)
         full = np.empty((B, n, V), dtype=np.float32) if all_logits else None
         hid = att = None
+        lab = self._labels(labels, B, n)
+        lp = sl = None
         try:
+            if lab is not None:
+                lp, sl = self._request_scores(lab, B * n)
             if hidden_states:
                 hid = np.empty((self.cfg.num_hidden_layers + 1, B, n, self.cfg.hidden_size), dtype=np.float32)
                 self._check(self.lib.vc_request_hidden_states(self._model, hid.ctypes.data_as(C.c_void_p), C.c_size_t(hid.size)))
@@ -467,9 +514,12 @@ class HipEngine:
         except BaseException:
             self.lib.vc_request_attentions(self._model, None, C.c_size_t(0))
             self.lib.vc_request_hidden_states(self._model, None, C.c_size_t(0))
+            self._cancel_scores()
             raise
         self._step_pos += n
         self.last_hidden_states, self.last_attentions = hid, att
+        if lab is not None:
+            self.last_token_logprobs, self.last_spliced_labels = lp.reshape(B, n), sl.reshape(B, n)
         return last, full
 
     _step_pos = 0   # position of the token the next decode_step processes (prefill: S)

@@ -57,6 +57,42 @@ class KVCacheHandle:
     def __len__(self):
         return self._model.config.num_hidden_layers
 
+    def crop(self, length: int):
+        """HF DynamicCache.crop: the cache steps back to `length` positions (the prompt's spliced length <= length <= the current
+        length; nothing is copied).  A forward over this handle with one id or with several ids continues from there — how K
+        candidate answers are scored behind one prefilled prompt."""
+        if self.generation != self._model._generation:
+            raise RuntimeError("past_key_values does not belong to the engine's current KV cache")
+        self._model.engine.rewind(int(length))
+        self.length = int(length)
+
+
+class TokenScores(dict):
+    """What score() returns: token_logprobs [B, S] (log p(label) where labels != -100 and a row stands in front, 0 elsewhere), labels
+    [B, S] as the splice laid them out, sequence_logprob [B] (row sums), loss (mean of -logprob over the scored entries, nan when
+    there are none) and past_key_values."""
+
+    def __init__(self, **kw):
+        super().__init__(**kw)
+        self.__dict__ = self
+
+
+def _labels_in_range(labels, vocab: int) -> bool:
+    lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
+    return not bool(((lab != -100) & ((lab < 0) | (lab >= vocab))).any())
+
+
+def _score_outputs(engine):
+    """(token_logprobs, labels, loss) of the engine's last labelled prefill / extend as torch tensors"""
+    import torch
+
+    lp = torch.from_numpy(np.ascontiguousarray(engine.last_token_logprobs))
+    sl = torch.from_numpy(np.ascontiguousarray(engine.last_spliced_labels))
+    scored = sl != -100
+    scored[:, 0] = False   # HF's shift: nothing stands in front of position 0
+    loss = -lp[scored].mean() if bool(scored.any()) else torch.tensor(float("nan"), dtype=torch.float32)
+    return lp, sl, loss.to(torch.float32)
+
 
 class _InnerModel:
     """What `get_model()` returns: the plugin modules of VCoder[DS]LlavaMetaModel (vcoder_ds_llava_arch.py:30-49)."""
@@ -216,10 +252,30 @@ class _HipCausalLMBase:
     def forward(self, input_ids=None, attention_mask=None, past_key_values=None, inputs_embeds=None, labels=None,
                 use_cache=None, output_attentions=None, output_hidden_states=None, images=None, segs=None, depths=None,
                 return_dict=None):
+        """labels [B, T] (aligned with input_ids, -100 = ignored): `loss` is the reference's (vcoder_ds_llava_llama.py:95-106) — the
+        labels are spliced like the embeddings, shifted by one, and the mean of -log p(label) over the labelled positions comes
+        back as a float32 scalar (nan when nothing is labelled), first in the tuple with return_dict=False (:108-110).  It is
+        computed on the device from the labelled rows alone (HipEngine.prefill(labels=)); no gradient exists."""
+        return self._forward(input_ids, attention_mask, past_key_values, labels, use_cache, output_attentions, output_hidden_states,
+                             images, segs, depths, return_dict, want_logits=True)
+
+    def score(self, input_ids, labels, images=None, segs=None, depths=None, past_key_values=None, attention_mask=None):
+        """log p(label) per token without logits leaving the device: same dispatch as forward (prefill with images, text-only
+        prefill, continuation of `past_key_values`), no all-row logits.  -> TokenScores.  Candidate answers behind one prompt:
+        prefill once, then per candidate score(candidate_ids, candidate_ids, past_key_values=pkv) and pkv.crop(prompt_length)."""
+        if labels is None:
+            raise ValueError("score() needs labels")
+        return self._forward(input_ids, attention_mask, past_key_values, labels, None, None, None, images, segs, depths, None,
+                             want_logits=False)
+
+    def _forward(self, input_ids, attention_mask, past_key_values, labels, use_cache, output_attentions, output_hidden_states,
+                 images, segs, depths, return_dict, want_logits):
         import torch
 
         if labels is not None:
-            raise NotImplementedError("training loss is outside the inference hot path (SURVEY.md §8: train/* out of scope)")
+            lab_shape = tuple(labels.shape) if hasattr(labels, "shape") else np.asarray(labels).shape
+            if input_ids is not None and lab_shape != tuple(input_ids.shape):
+                raise ValueError(f"labels must have the shape of input_ids {tuple(input_ids.shape)}, got {lab_shape}")
         # The reference OVERWRITES a caller's inputs_embeds with what prepare_inputs_labels_for_multimodal returns
         # (vcoder_ds_llava_llama.py:79: the spliced embeddings, or None) — the argument is dead; without input_ids the call
         # then dies in LlamaModel ("You must specify exactly one of input_ids or inputs_embeds").  Same here.
@@ -239,10 +295,19 @@ class _HipCausalLMBase:
             if images is not None or attention_mask is None:
                 self.engine.clear_attention_mask()
             # output_hidden_states / output_attentions of a cached step: [B, 1, D] per entry, [B, H, 1, past + 1] per layer
+            if labels is not None:   # before the step: a refused call leaves the cache as it was
+                lab1 = np.asarray(labels.detach().cpu().numpy() if hasattr(labels, "detach") else labels, dtype=np.int64)
+                if lab1.shape != (B, 1):
+                    raise ValueError(f"labels must be [{B},1], got {tuple(lab1.shape)}")
+                if not _labels_in_range(lab1, self.config.vocab_size):
+                    raise IndexError("Target is out of bounds.")
             lg, _ = self.engine.decode_step(tok, hidden_states=bool(output_hidden_states), attentions=bool(output_attentions))
             past_key_values.length += 1
             logits = torch.from_numpy(lg).unsqueeze(1)
             pkv = past_key_values
+            if labels is not None:   # one new position: the shift leaves nothing to score (torch's mean over an empty set)
+                self.engine.last_token_logprobs = np.zeros((B, 1), dtype=np.float32)
+                self.engine.last_spliced_labels = lab1
         elif past_key_values is not None:
             # multi-token continuation of the cache: with images=None, prepare_inputs_labels_for_multimodal returns early
             # (vcoder_ds_llava_arch.py:129-133) and LlamaModel runs the n new ids at positions past .. past+n-1, causal inside
@@ -259,6 +324,8 @@ class _HipCausalLMBase:
                 raise ValueError(f"input_ids has {B} rows, past_key_values {past_key_values.batch}")
             if ((tok < 0) | (tok >= self.config.vocab_size)).any():
                 raise IndexError("index out of range in self")
+            if labels is not None and not _labels_in_range(labels, self.config.vocab_size):
+                raise IndexError("Target is out of bounds.")   # torch's CrossEntropyLoss
             if past_key_values.length + n > self.config.max_position_embeddings // 64 * 64:   # vc_extend's own limit
                 raise RuntimeError(f"KV cache full: position {past_key_values.length + n} exceeds max_position_embeddings="
                                    f"{self.config.max_position_embeddings}")
@@ -272,10 +339,10 @@ class _HipCausalLMBase:
                                               "is outside the VCoder hot path")
             else:
                 self.engine.clear_attention_mask()
-            _, full = self.engine.extend(tok, all_logits=True, hidden_states=bool(output_hidden_states),
-                                         attentions=bool(output_attentions))
+            _, full = self.engine.extend(tok, all_logits=want_logits, hidden_states=bool(output_hidden_states),
+                                         attentions=bool(output_attentions), labels=labels)
             past_key_values.length += n
-            logits = torch.from_numpy(full)
+            logits = torch.from_numpy(full) if want_logits else None
             pkv = past_key_values
         else:
             # images None: prepare_inputs_labels_for_multimodal returns early (vcoder_ds_llava_arch.py:129-133) and the
@@ -286,12 +353,18 @@ class _HipCausalLMBase:
                                           "VCoder hot path")
             _, full, S = self.engine.prefill(ids, images, (segs if self.variant != "llava" else None) if images is not None else None,
                                              (depths if self.variant == "vcoder_ds" else None) if images is not None else None,
-                                             all_logits=True, reserve=self._decode_reserve,
+                                             all_logits=want_logits, reserve=self._decode_reserve,
                                              attention_mask=attention_mask if images is not None else None,
-                                             hidden_states=bool(output_hidden_states), attentions=bool(output_attentions))
+                                             hidden_states=bool(output_hidden_states), attentions=bool(output_attentions),
+                                             labels=labels)
             self._generation += 1
-            logits = torch.from_numpy(full)
+            logits = torch.from_numpy(full) if want_logits else None
             pkv = KVCacheHandle(self, self._generation, S, B)
+        loss = None
+        if labels is not None:
+            lp, sl, loss = _score_outputs(self.engine)
+            if not want_logits:
+                return TokenScores(token_logprobs=lp, labels=sl, sequence_logprob=lp.sum(dim=1), loss=loss, past_key_values=pkv)
         if hasattr(ids, "device") and getattr(ids, "is_cuda", False):
             logits = logits.to(ids.device)
         hs = None
@@ -301,10 +374,11 @@ class _HipCausalLMBase:
         at = None
         if output_attentions and self.engine.last_attentions is not None:
             at = tuple(torch.from_numpy(a) for a in self.engine.last_attentions)     # L tensors [B, H, S, S]
-        out = CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=pkv if use_cache is not False else None,
+        out = CausalLMOutputWithPast(loss=loss, logits=logits, past_key_values=pkv if use_cache is not False else None,
                                      hidden_states=hs, attentions=at)
         if return_dict is False:
-            return (out.logits,) + ((out.past_key_values,) if out.past_key_values is not None else ())
+            return ((loss,) if loss is not None else ()) + (out.logits,) + \
+                ((out.past_key_values,) if out.past_key_values is not None else ())
         return out
 
     __call__ = forward
