@@ -195,6 +195,13 @@ unsigned long long vck_gemm_8phase_launches(void);
 void vck_set_gemv_wide(int v);
 unsigned long long vck_gemv_wide_launches(void);
 unsigned long long vck_gemv_wg_launches(void);   /* launches the workgroup-shared form has served (tests) */
+/* the geometry the decode GEMV launcher chooses for a call (vck_gemv_full's arguments; of the optional buffers only their presence:
+ * fp8 = W8A16 weights, has_sk = the split-K buffers with the given capacities, has_wlo = a weight lo plane) under the current
+ * vck_set_gemv_variant / vck_set_gemv_wide values, without launching.  Returns 0 and out = {form (0 ring, 1 wide, 2 workgroup-shared),
+ * waves, tiles per workgroup (per wave in form 2), ring slots, 8-row activation pieces, chunk lines (form 2), fp8, wlo, K-slices,
+ * workgroups}, or -1 where the launcher refuses the call (tests: tests/golden/gemv_plan.npz pins the table) */
+int vck_gemv_plan(int M, int N, int K, int epi, int fp8, int split_rows, int ksplit, int has_sk, unsigned long long sk_scratch_floats,
+                  int sk_counters_n, int has_wlo, int out[10]);
 void vck_rmsnorm_split(const float* x, const int* row_idx, const float* w, uint16_t* y, int rows, int D, float eps, int ldy,
                        uint64_t lo_off, void* stream);
 void vck_layernorm_split(const float* x, const float* w, const float* b, uint16_t* y, int rows, int D, float eps, int ldy,

@@ -1090,11 +1090,12 @@ def check_uniform_extremes(be):
     assert u[9] == np.float32(1.0 - 2.0 ** -24) and u[0] == np.float32(2.0 ** -24)
 
 
-def check_gemv_rows_agree_across_variants(be, N, K, epi, norm=True, ksplit=0, seed=0, fp8=False):
+def check_gemv_rows_agree_across_variants(be, N, K, epi, norm=True, ksplit=0, seed=0, fp8=False, M=29, buffers=False):
     """The decode pool's promise: a row gets bit-for-bit the same result from a 32-row pass (two MFMA row groups) as from a
-    16-row pass — rows 0..15 and 16..31 of an M = 29 launch against two launches of 16 and 13 rows."""
+    16-row pass — rows 0..15 and 16..31 of an M = 29 launch against two launches of 16 and 13 rows.  M: the rows of the large pass
+    (17..32); buffers: the split-K buffers are given with ksplit = 0, as the engine gives them (the launcher then cuts the matrices of
+    257..512 tiles into its own 3 K-slices)."""
     rng = np.random.RandomState(seed)
-    M = 29
     npart = (K // 16 + 15) // 16 * 16
     X = bf16_round(rng.randn(32, K))
     W = bf16_round(rng.randn(N, K) * 0.05)
@@ -1114,8 +1115,8 @@ def check_gemv_rows_agree_across_variants(be, N, K, epi, norm=True, ksplit=0, se
     r0 = rng.randn(32, No).astype(np.float32)
     mk = lambda: (be.f32(r0.copy()) if epi == 2 else be.zeros((32, No), esz))
     sk = None
-    if ksplit:
-        sk = (be.zeros((ksplit * (N // 16) * 2 * 256,), "f32"), be.zeros((N // 16 * 2,), "i32"))
+    if ksplit or buffers:
+        sk = (be.zeros((max(ksplit, 3) * (N // 16) * 2 * 256,), "f32"), be.zeros((N // 16 * 2,), "i32"))
     Xd = be.bf16(X)
     big = mk()
     _gemv_ex(be, Xd, Wp, wsc, big, ssqd, None, None, None, npart, M, N, K, No, epi, sk=sk, ksplit=ksplit)
@@ -1131,7 +1132,7 @@ def check_gemv_rows_agree_across_variants(be, N, K, epi, norm=True, ksplit=0, se
     same = np.array_equal   # the K partition is the same for both row counts
     assert same(b[:16], l[:16]), "rows 0..15 differ between the 32-row and the 16-row pass"
     if epi != 2:   # (the in-place residual form adds into whatever rows the buffer holds: only rows 0..15 line up)
-        assert same(b[16:M], be.host_f32(hi)[: M - 16]), "rows 16..28 differ between the 32-row and the 16-row pass"
+        assert same(b[16:M], be.host_f32(hi)[: M - 16]), f"rows 16..{M - 1} differ between the {M}-row and the {M - 16}-row pass"
     ref = X[:M].astype(np.float64) @ W.T.astype(np.float64)
     if norm:
         ref = ref / np.sqrt(ssq[:M, : K // 16].sum(-1, keepdims=True) / K + 1e-5)
@@ -1141,7 +1142,25 @@ def check_gemv_rows_agree_across_variants(be, N, K, epi, norm=True, ksplit=0, se
     if epi == 2:
         ref = ref + r0[:M]
     e = rel_err(b[:M], ref)
-    assert e < (2 ** -8 if epi in (0, 3) else 2e-5), f"gemv M=29 N{N} K{K} epi{epi}: rel err {e}"
+    assert e < (2 ** -8 if epi in (0, 3) else 2e-5), f"gemv M={M} N{N} K{K} epi{epi}: rel err {e}"
+
+
+# Cells of the decode GEMV's geometry tables (decode.hip kRingClasses / kRingSplitK / kWideClasses) that no case above reaches,
+# each at the lowest tile count of its class, the smallest K that gives every K-slice a k-tile, and the lowest row count of its
+# column (1 / 9 / 17 / 25 rows = 1..4 activation pieces).  (M, N, K, epi) for check_gemv and (..., norm) for check_gemv_fp8:
+GEMV_TABLE_CASES = [(1, 16 * 257, 32, 1), (17, 16 * 257, 32, 0), (25, 16 * 257, 32, 2)]          # 257..512 tiles without split-K buffers
+GEMV_FP8_TABLE_CASES = [
+    (17, 16, 64, 1, False),                                                                      # <= 256 tiles, 3 pieces: 4-slot ring
+    (1, 16 * 257, 64, 1, False), (17, 16 * 257, 64, 2, False),                                   # 257..512 tiles without buffers
+    (9, 16 * 513, 64, 0, False), (17, 16 * 513, 64, 3, False), (25, 16 * 513, 64, 0, False),     # pairs where the wide form is < 218 workgroups
+    (17, 16 * 1536, 64, 1, False), (25, 16 * 1536, 64, 2, False),                                # >= 1536 tiles: 4 tiles per workgroup
+    (17, 16 * 654, 64, 0, False), (17, 16 * 869, 64, 0, False),                                  # wide, 3 pieces: NT 3, 4 (218 workgroups)
+    (17, 16 * 1303, 64, 3, False), (17, 16 * 1537, 64, 3, False)]                                #                 NT 6, 7
+# (N, K, epi, norm, ksplit, fp8, M, buffers) for check_gemv_rows_agree_across_variants: the split-K cells (the M-row pass, and its 16-
+# and (M - 16)-row passes): an explicit ksplit on <= 256 tiles, the launcher's own 3 slices on 257 tiles
+GEMV_SPLITK_TABLE_CASES = [(32, 256, 0, True, 2, False, 21, False), (32, 256, 1, True, 2, True, 21, False), (32, 256, 3, True, 2, True, 29, False),
+                           (16 * 257, 192, 2, False, 0, False, 21, True), (16 * 257, 192, 2, False, 0, False, 29, True),
+                           (16 * 257, 192, 2, False, 0, True, 21, True), (16 * 257, 192, 2, False, 0, True, 29, True)]
 
 
 def check_sampling(be, V, temperature, top_k, top_p, draws=2048, seed0=1234):
@@ -1680,6 +1699,20 @@ def _wg_run(be, c, M, G, ksplit=0, row0=0, wlo=False):
     return val, raw, extra
 
 
+GEMV_FORM_RING, GEMV_FORM_WIDE, GEMV_FORM_WG = 0, 1, 2
+GEMV_PLAN_FIELDS = ("form", "waves", "nt", "r", "xp", "cl", "fp8", "wlo", "ksplit", "workgroups")
+
+
+def gemv_plan(be, M, N, K, epi, fp8=False, G=0, ksplit=0, sk=None, wlo=False):
+    """vck_gemv_plan: what the decode GEMV launcher would launch for this call under the current knobs (sk = (scratch floats,
+    counters) capacities of the split-K buffers, (0, 0) = the default capacity, None = no buffers) -> dict of GEMV_PLAN_FIELDS, or
+    None where the launcher refuses the call"""
+    out = (ctypes.c_int * 10)()
+    rc = be.lib.vck_gemv_plan(M, N, K, epi, int(fp8), G, ksplit, int(sk is not None), ctypes.c_ulonglong(sk[0] if sk else 0),
+                              ctypes.c_int(sk[1] if sk else 0), int(wlo), out)
+    return dict(zip(GEMV_PLAN_FIELDS, out)) if rc == 0 else None
+
+
 def check_gemv_wg(be, M, N, K, epi, norm=True, G=8, ksplit=0, seed=0):
     """gemv_wg_kernel (the GEMV of precision mode "split": hi / lo rows, one weight pass) against the float64 product: every
     epilogue, RMSNorm folding on both sides, explicit K-slices with the cross-workgroup hand-off"""
@@ -1692,6 +1725,8 @@ def check_gemv_wg(be, M, N, K, epi, norm=True, G=8, ksplit=0, seed=0):
         c = _wg_case(be, rng, M, N, K, epi, norm, G)
         val, raw, extra = _wg_run(be, c, M, G, ksplit)
         assert be.lib.vck_gemv_wg_launches() == n0 + 1, "the call was not served by gemv_wg_kernel"
+        plan = gemv_plan(be, M, N, K, epi, G=G, ksplit=ksplit, sk=c["sk"][2:])
+        assert plan is not None and plan["form"] == GEMV_FORM_WG, f"gemv_wg M{M} N{N} K{K} epi{epi} G{G} ks{ksplit}: planned as {plan}"
         e = rel_err(val, c["ref"])
         tol = 3e-5 if G else (2 ** -8 if epi in (0, 3) else 2e-5)
         assert e < tol, f"gemv_wg M{M} N{N} K{K} epi{epi} G{G} ks{ksplit}: rel err {e}"
@@ -1760,11 +1795,15 @@ def check_gemv_wide(be, N, K, epi, rows, norm=True, seed=0):
         worst = 0.0
         for M in rows:
             be.lib.vck_set_gemv_wide(0)
+            plan0 = gemv_plan(be, M, N, K, epi)
             _, raw0, ex0 = _wg_run_plain(be, c, M)
             be.lib.vck_set_gemv_wide(2)
+            plan1 = gemv_plan(be, M, N, K, epi)
             n0 = be.lib.vck_gemv_wide_launches()
             val, raw1, ex1 = _wg_run_plain(be, c, M)
             assert be.lib.vck_gemv_wide_launches() == n0 + 1, f"M{M} N{N} epi{epi}: not served by the wide geometry"
+            assert plan0["form"] == GEMV_FORM_RING and plan1["form"] == GEMV_FORM_WIDE and plan1["nt"] == (N // 16 + 255) // 256, \
+                f"M{M} N{N} epi{epi}: planned as {plan0} (wide off) / {plan1} (every class)"
             assert np.array_equal(raw0, raw1), f"M{M} N{N} K{K} epi{epi}: the wide geometry changed the bits"
             e = rel_err(val, c["ref"][:M])
             assert e < (2 ** -8 if epi in (0, 3) else 2e-5), f"gemv wide M{M} N{N} K{K} epi{epi}: rel err {e}"

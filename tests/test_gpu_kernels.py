@@ -119,14 +119,15 @@ def test_gemm_qkv_fused_epilogue(be, B, T, H, K, ws, f8, kv8):
 
 @pytest.mark.parametrize("M,N,K,epi", [(8, 12288, 4096, 0), (8, 4096, 4096, 2), (8, 22016, 4096, 3),
                                        (8, 4096, 11008, 2), (8, 32000, 4096, 1), (16, 15360, 5120, 0), (1, 320, 256, 1),
-                                       (3, 48, 288, 1)])
+                                       (3, 48, 288, 1)] + kc.GEMV_TABLE_CASES)
 def test_gemv(be, M, N, K, epi):
     kc.check_gemv(be, M, N, K, epi)
 
 
 @pytest.mark.parametrize("M,N,K,epi,norm", [(8, 12288, 4096, 0, True), (8, 4096, 4096, 2, False), (8, 22016, 4096, 3, True),
                                             (8, 4096, 11008, 2, False), (16, 15360, 5120, 0, True),
-                                            (16, 5120, 13824, 2, False), (3, 48, 320, 1, False), (5, 32, 320, 1, True)])
+                                            (16, 5120, 13824, 2, False), (3, 48, 320, 1, False), (5, 32, 320, 1, True)]
+                         + kc.GEMV_FP8_TABLE_CASES)
 def test_gemv_fp8(be, M, N, K, epi, norm):
     kc.check_gemv_fp8(be, M, N, K, epi, norm)
 
@@ -144,6 +145,13 @@ def test_gemm_f8(be, M, N, K, epi, ws):
                                       (3, 48, 320, 3)])
 def test_gemv_splitk(be, M, N, K, ks):
     kc.check_gemv_splitk(be, M, N, K, ks)
+
+
+@pytest.mark.parametrize("N,K,epi,norm,ks,fp8,M,buffers", kc.GEMV_SPLITK_TABLE_CASES)
+def test_gemv_splitk_geometries_17_to_32_rows(be, N, K, epi, norm, ks, fp8, M, buffers):
+    """the split-K cells of the geometry table at 17..24 and 25..32 rows (and the <= 8- / <= 16-row cells of their sub-passes), bf16
+    and W8A16: the same bits per row from every pass, within the float64 bar"""
+    kc.check_gemv_rows_agree_across_variants(be, N, K, epi, norm, ks, fp8=fp8, M=M, buffers=buffers)
 
 
 @pytest.mark.parametrize("M,N,K,epi,bias", [(9728, 4096, 4096, 4, False), (9728, 12288, 4096, 0, False),
@@ -391,7 +399,8 @@ def test_weight_lo_plane_kernels(be):
     kc.check_gemm_split_wlo(be, 9728, 12288, 4096, 3, seed=5, ws_mb=64)   # B = 8 prefill rows: split-K remainder round over the three segments
     kc.check_gemm_f32_wlo(be, 70, 512, 1024, 3)
     for (M, N, K, epi, G, ks) in [(8, 12288, 4096, 1, 8, 0), (16, 22016, 4096, 3, 16, 0), (32, 4096, 11008, 2, 32, 0),
-                                  (29, 32000, 4096, 1, 32, 0), (24, 4096, 4096, 2, 24, 0)]:
+                                  (29, 32000, 4096, 1, 32, 0), (24, 4096, 4096, 2, 24, 0),
+                                  (17, 22016, 128, 3, 24, 0), (25, 22016, 128, 3, 32, 0)]:   # six waves with the lo plane, 3 / 4 pieces
         kc.check_gemv_split_wlo(be, M, N, K, epi, G, ks)
 
 

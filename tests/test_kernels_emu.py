@@ -55,14 +55,14 @@ def test_gemm_splitk_remainder_round(be):
 
 
 @pytest.mark.parametrize("M,N,K,epi", [(8, 64, 256, 0), (3, 32, 1024, 1), (16, 48, 288, 2), (8, 64, 256, 3),
-                                       (1, 16, 32, 1)])
+                                       (1, 16, 32, 1)] + kc.GEMV_TABLE_CASES)
 def test_gemv(be, M, N, K, epi):
     kc.check_gemv(be, M, N, K, epi)
 
 
 @pytest.mark.parametrize("M,N,K,epi,norm", [(8, 64, 256, 0, False), (3, 32, 1024, 1, False), (16, 48, 320, 2, False),
                                             (8, 64, 256, 3, False), (1, 16, 64, 1, False), (8, 64, 512, 0, True),
-                                            (16, 32, 5120, 3, True), (5, 32, 320, 1, True)])
+                                            (16, 32, 5120, 3, True), (5, 32, 320, 1, True)] + kc.GEMV_FP8_TABLE_CASES)
 def test_gemv_fp8(be, M, N, K, epi, norm):
     kc.check_gemv_fp8(be, M, N, K, epi, norm)
 
@@ -96,6 +96,13 @@ def test_gemv_32_rows_w8a16(be, N, K, epi, norm):
     since round 6 (3 / 4 / 6 / 7 tiles per workgroup, ragged last workgroup included), whose finishing stage gives every wave
     several (tile, row group) units — against the pair geometry that serves the same rows in 8- and 16-row passes"""
     kc.check_gemv_rows_agree_across_variants(be, N, K, epi, norm, fp8=True)
+
+
+@pytest.mark.parametrize("N,K,epi,norm,ks,fp8,M,buffers", kc.GEMV_SPLITK_TABLE_CASES)
+def test_gemv_splitk_geometries_17_to_32_rows(be, N, K, epi, norm, ks, fp8, M, buffers):
+    """the split-K cells of the geometry table at 17..24 and 25..32 rows (and the <= 8- / <= 16-row cells of their sub-passes), bf16
+    and W8A16: the same bits per row from every pass, within the float64 bar"""
+    kc.check_gemv_rows_agree_across_variants(be, N, K, epi, norm, ks, fp8=fp8, M=M, buffers=buffers)
 
 
 def test_gemv_chain_24_rows(be):
@@ -324,6 +331,36 @@ def test_gemv_wg(be, M, N, K, epi, norm, G, ks):
 def test_gemv_wide_geometry(be, N, K, epi, norm, rows):
     """the one-workgroup-per-CU geometries (3 / 4 / 6 / 7 tiles per workgroup) give the pair geometry's bits"""
     kc.check_gemv_wide(be, N, K, epi, rows, norm)
+
+
+def test_gemv_plan_matches_recorded(be):
+    """The decode GEMV's launch geometry — which kernel instance, how many K-slices and workgroups, or a refusal — for every call of
+    tests/golden/gemv_plan.npz is what the launcher chose when the rows were recorded.  Every geometry computes the same bits, so no
+    numerical test sees a threshold, ring depth or table cell of decode.hip's gemv_plan move: this one does.  The rows: every
+    tile-count class boundary x 1 / 8 / 9 / 16 / 17 / 24 / 25 / 32 rows x bf16 and W8A16 weights x the (K, epilogue) pairs of the 7b
+    and 13b matrices, with and without the split-K buffers; the split step (G = 8 / 16 / 32, with and without a weight lo plane) at
+    the 7b and 13b shapes; every non-default vck_set_gemv_variant / vck_set_gemv_wide value at the 7b shapes.  A deliberate geometry
+    change regenerates the rows it touches (the `plans` row of each affected call, from vck_gemv_plan) in the same commit and cites
+    the measurement that justifies it, next to the table cell it changes."""
+    import os
+    import numpy as np
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemv_plan.npz"))
+    calls, plans = g["calls"], g["plans"]
+    assert list(g["plan_columns"][1:]) == list(kc.GEMV_PLAN_FIELDS) and len(calls) == len(plans) > 5000
+    wrong = []
+    try:
+        for call, want in zip(calls.tolist(), plans.tolist()):
+            M, N, K, epi, fp8, G, ks, has_sk, sk_floats, sk_n, wlo, variant, wide = call
+            be.lib.vck_set_gemv_variant(variant)
+            be.lib.vck_set_gemv_wide(wide)
+            got = kc.gemv_plan(be, M, N, K, epi, fp8=fp8, G=G, ksplit=ks, sk=(sk_floats, sk_n) if has_sk else None, wlo=wlo)
+            refused, want = want[0] != 0, dict(zip(kc.GEMV_PLAN_FIELDS, want[1:]))
+            if (got is None) != refused or (got is not None and got != want):
+                wrong.append((dict(zip(g["call_columns"].tolist(), call)), "refused" if refused else want, got))
+    finally:
+        be.lib.vck_set_gemv_variant(-1)
+        be.lib.vck_set_gemv_wide(-1)
+    assert not wrong, f"{len(wrong)} of {len(calls)} calls plan differently from the recording; the first (call, recorded, now): {wrong[:3]}"
 
 
 @pytest.mark.parametrize("N,K,epi,norm,rows,ks", [(16 * 13, 576, 0, False, (5, 16, 19, 32), 0), (16 * 13, 576, 2, False, (8, 29), 2),

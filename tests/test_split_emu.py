@@ -125,7 +125,8 @@ def test_weight_lo_plane_kernels(be):
     kc.check_gemm_split_wlo(be, 1024, 16640 - 8, 64, 3, seed=9, ws_mb=4)         # split-K remainder round over the three segments
     kc.check_gemm_f32_wlo(be, 33, 96, 100, 3)
     for (M, N, K, epi, G, ks) in [(5, 64, 256, 1, 8, 0), (13, 48, 320, 2, 16, 0), (29, 96, 576, 3, 32, 0), (32, 64, 1024, 1, 32, 4),
-                                  (21, 80, 384, 0, 24, 2)]:
+                                  (21, 80, 384, 0, 24, 2),
+                                  (17, 22016, 128, 3, 24, 0), (25, 22016, 128, 3, 32, 0)]:   # six waves with the lo plane, 3 / 4 pieces
         kc.check_gemv_split_wlo(be, M, N, K, epi, G, ks)
 
 

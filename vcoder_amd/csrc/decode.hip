@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include <atomic>
+#include <climits>
 #include <stdexcept>
 #include <string>
 
@@ -629,163 +630,12 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_wg_kernel(GemvArgs p) {
     stamp_end(p.stamp, blockIdx.x);
 }
 
-template <class K>
-static void allow_big_lds(K kernel, size_t bytes) {
-#ifndef VC_EMU
-    if (bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-#endif
-}
-
-template <int WAVES, int NT, int R, bool FP8, int XP>
-static void launch_gemv_dma_x(const GemvArgs& a, int epi, hipStream_t s) {
-    const dim3 grid(((a.N / 16 + NT - 1) / NT) * (a.ksplit > 1 ? a.ksplit : 1)), block(WAVES * 64);
-    constexpr size_t shmem = (size_t)WAVES * R * ((FP8 ? 1 : 2) * NT + XP) * 1024;
-    // + the kernel's static ss_part[WAVES][16 * MG] floats
-    static_assert(shmem + WAVES * 16 * ((XP + 1) / 2) * 4 <= 160 * 1024, "ring exceeds the LDS of a CU");
-#define VC_GEMV_DMA(E)                                                                                                  \
-    do {                                                                                                                \
-        static bool once = false;                                                                                       \
-        if (!once) {                                                                                                    \
-            allow_big_lds(gemv_dma_kernel<WAVES, NT, R, E, FP8, XP>, shmem);                                            \
-            once = true;                                                                                                \
-        }                                                                                                               \
-        VC_LAUNCH((gemv_dma_kernel<WAVES, NT, R, E, FP8, XP>), grid, block, shmem, s, a);                               \
-    } while (0)
-    switch (epi) {
-        case GEMV_BF16: VC_GEMV_DMA(GEMV_BF16); break;
-        case GEMV_F32: VC_GEMV_DMA(GEMV_F32); break;
-        case GEMV_RESID_F32: VC_GEMV_DMA(GEMV_RESID_F32); break;
-        default: VC_GEMV_DMA(GEMV_SWIGLU); break;
-    }
-#undef VC_GEMV_DMA
-}
+// ---- host side: what to launch (gemv_plan) and the launch itself (launch_gemv) -----------------------------------------------------
+// Every geometry gives a row the same bits (the K partition of a matrix never depends on the row count or the form), so nothing
+// below shows in a numerical test: tests/golden/gemv_plan.npz pins the choice (test_gemv_plan_matches_recorded).
 
 // rows of the activation operand X: M, or split_rows + M in precision mode "split" (hi rows, then lo rows)
 static int x_rows(const GemvArgs& a) { return a.split_rows ? a.split_rows + a.M : a.M; }
-
-// X rows <= 16: one MFMA row group, one (<= 8 rows) or two 8-row activation pieces per slot
-template <int WAVES, int NT, int R, bool FP8>
-static void launch_gemv_dma(const GemvArgs& a, int epi, hipStream_t s) {
-    if (x_rows(a) <= 8) launch_gemv_dma_x<WAVES, NT, R, FP8, 1>(a, epi, s);
-    else launch_gemv_dma_x<WAVES, NT, R, FP8, 2>(a, epi, s);
-}
-// X rows in 17..32: two row groups, three or four pieces
-template <int WAVES, int NT, int R, bool FP8>
-static void launch_gemv_dma2(const GemvArgs& a, int epi, hipStream_t s) {
-    if (x_rows(a) <= 24) launch_gemv_dma_x<WAVES, NT, R, FP8, 3>(a, epi, s);
-    else launch_gemv_dma_x<WAVES, NT, R, FP8, 4>(a, epi, s);
-}
-
-// K-slices of the 257..512-tile class (13b o_proj / down: 320 tiles neither fill the chip one-per-CU nor balance two-per-CU):
-// with the split-K buffers, pairs of tiles x 3 K-slices = 480 workgroups, all resident (2/CU), activation fragments shared by
-// the pair (measured M = 16: down 43.0 -> 30.2 us, o_proj 20.1 -> 14.9; for <= 256 tiles every split loses: 8.5 -> 10 us).
-// An explicit a.ksplit is honoured.
-constexpr int KS_MID = 3;
-
-// M in 17..32 (the decode pool): two row groups per weight pass.  The K partition (waves per workgroup, K-slices) of every
-// tile-count class equals the 16-row launcher's below, so a row's result does not depend on which variant served it; only
-// the tiles per workgroup and the ring depth are re-balanced for the larger slots (LDS: all workgroups resident).
-template <bool FP8>
-static void launch_gemv_m32(const GemvArgs& a, int epilogue, hipStream_t s) {
-    const int tiles = a.N / 16;
-    if (a.ksplit > 1 || (a.sk_scratch && a.sk_counters && a.ksplit == 0 && tiles > 256 && tiles <= 512)) {
-        GemvArgs b = a;
-        if (b.ksplit <= 1) b.ksplit = KS_MID;
-        if (a.ksplit > 1 && tiles <= 256) launch_gemv_dma2<4, 1, 2, FP8>(b, epilogue, s);
-        else launch_gemv_dma2<4, 2, 2, FP8>(b, epilogue, s);
-        return;
-    }
-    if (tiles <= 256) {
-        // W8A16 slots are 4 KiB (3 pieces) / 5 KiB (4 pieces): a 4-slot ring of the latter would need all 160 KiB + ss_part
-        if constexpr (FP8) {
-            if (x_rows(a) <= 24) {
-                launch_gemv_dma_x<8, 1, 4, true, 3>(a, epilogue, s);
-                return;
-            }
-        }
-        launch_gemv_dma2<8, 1, 3, FP8>(a, epilogue, s);
-    } else if (tiles <= 512) launch_gemv_dma2<4, 1, 3, FP8>(a, epilogue, s);
-    else {
-        // W8A16, the widest matrices (13b gate/up: 1728 tiles): 4 tiles per workgroup halve the activation bytes per weight
-        // byte — the bound of this kernel at 17..32 rows, DESIGN.md section 9.2 — same K partition (4 waves).  Measured at 32
-        // rows: 45.2 -> 35.3 us; with 1376 tiles (7b gate/up) the 344 single-resident workgroups balance badly over 256 CUs
-        // and it loses (26.2 -> 27.9 us), hence the threshold.
-        if constexpr (FP8) {
-            if (tiles >= 1536) {
-                launch_gemv_dma2<4, 4, 2, true>(a, epilogue, s);
-                return;
-            }
-        }
-        // 513..768 tiles as pairs too (2 workgroups/CU, the pair shares the activation pieces; 28.3 vs 33.9 us at M = 24 for
-        // one tile per workgroup)
-        launch_gemv_dma2<4, 2, 2, FP8>(a, epilogue, s);
-    }
-}
-
-template <bool FP8>
-static void launch_gemv_f(const GemvArgs& a, int epilogue, hipStream_t s) {
-    const int tiles = a.N / 16;
-    if (x_rows(a) > 16) {  // the decode pool's 17..32 rows (split mode, ring form: 9..16 rows + their lo parts)
-        launch_gemv_m32<FP8>(a, epilogue, s);
-        return;
-    }
-    // Geometry by tile count, so that (where possible) every workgroup of the launch is resident at once — a tail of
-    // late workgroups cannot keep enough bytes in flight to use the HBM (13b o_proj/down: 320 tiles at one
-    // 128-KiB workgroup per CU ran a 64-workgroup second round at a third of the rate):
-    //   <= 256 tiles: 8 waves, deep ring (1 workgroup/CU);  <= 512: 4 waves, 5-slot ring (2 workgroups/CU);
-    //   <= 768: 4 waves x 1 tile (3/CU);  wider: 4 waves x 2 tiles (pairs share the activation fragments:
-    //   gate/up 30.0 vs 33.1 us, lm_head 40.6 vs 45.5; 4 tiles per workgroup measured slower: W8A16 gate/up 23.2 vs
-    //   19.7 us).  bf16 slots hold a k-tile pair, W8A16 slots one super-tile.
-    if (a.ksplit > 1 || (a.sk_scratch && a.sk_counters && a.ksplit == 0 && tiles > 256 && tiles <= 512)) {
-        GemvArgs b = a;
-        if (b.ksplit <= 1) b.ksplit = KS_MID;
-        if (a.ksplit > 1 && tiles <= 256) launch_gemv_dma<4, 1, 3, FP8>(b, epilogue, s);
-        else launch_gemv_dma<4, 2, 3, FP8>(b, epilogue, s);
-        return;
-    }
-    if (tiles <= 256) launch_gemv_dma<8, 1, FP8 ? 5 : 4, FP8>(a, epilogue, s);
-    else if (tiles <= 512) launch_gemv_dma<4, 1, 5, FP8>(a, epilogue, s);
-    else if (tiles <= 768 && !FP8) launch_gemv_dma<4, 1, 3, FP8>(a, epilogue, s);  // W8A16: always pairs (X is 2x W)
-    else launch_gemv_dma<4, 2, 3, FP8>(a, epilogue, s);
-}
-
-// ---- launcher of the workgroup-shared form (precision mode "split" only) -----------------------------------------------------
-// K-slices per tile group: a function of the MATRIX alone (so that every row count sums in the same order).  Measured on MI355X at
-// the 7b shapes, 8 and 32 rows (profiles/r04_b_kbench_gemv_wg.txt): one tile per wave beats tile pairs everywhere (twice the
-// workgroups), and every extra K-slice costs (the cross-workgroup hand-off) — so only as many slices as it takes to put >= 256
-// workgroups on the chip: qkv (768 tiles) 2, o / down (256) 4, gate-up / lm_head 1.
-static int wg_kslices(int ntiles, int K) {
-    const int groups = (ntiles + 3) / 4, lines = K / 64;
-    int ks = groups >= 256 ? 1 : groups >= 128 ? 2 : 4;
-    while (ks > 1 && lines / ks < 8) --ks;
-    return ks;
-}
-
-template <int XP, int CL, int R, bool WL, int WAVES = 4>
-static void launch_gemv_wg_e(const GemvArgs& a, int epi, hipStream_t s) {
-    constexpr int NTW = 1, KH = 2;
-    const int groups = (a.N / 16 + WAVES * NTW - 1) / (WAVES * NTW);
-    const dim3 grid((unsigned)(groups * (a.ksplit > 1 ? a.ksplit : 1))), block(WAVES * 64);
-    constexpr size_t shmem = (size_t)(2 * CL * XP * KH + WAVES * R * 2 * NTW * (WL ? 2 : 1)) * 1024;
-    static_assert(shmem + WAVES * 16 * ((XP + 1) / 2) * 4 <= 160 * 1024, "exceeds the LDS of a CU");
-#define VC_GEMV_WG(E)                                                                                                   \
-    do {                                                                                                                \
-        static bool once = false;                                                                                       \
-        if (!once) {                                                                                                    \
-            allow_big_lds(gemv_wg_kernel<NTW, XP, KH, CL, R, E, WL, WAVES>, shmem);                                     \
-            once = true;                                                                                                \
-        }                                                                                                               \
-        VC_LAUNCH((gemv_wg_kernel<NTW, XP, KH, CL, R, E, WL, WAVES>), grid, block, shmem, s, a);                        \
-    } while (0)
-    switch (epi) {
-        case GEMV_BF16: VC_GEMV_WG(GEMV_BF16); break;
-        case GEMV_F32: VC_GEMV_WG(GEMV_F32); break;
-        case GEMV_RESID_F32: VC_GEMV_WG(GEMV_RESID_F32); break;
-        default: VC_GEMV_WG(GEMV_SWIGLU); break;
-    }
-#undef VC_GEMV_WG
-}
 
 static int g_gemv_variant = -1;
 static std::atomic<unsigned long> g_gemv_wg_launches{0};   // sessions launch from their own threads
@@ -806,67 +656,104 @@ static bool gemv_wg_applies(const GemvArgs& a) {
     return a.split_rows >= a.M && a.split_rows <= 32 && a.split_rows % 8 == 0;
 }
 
+static int g_gemv_wide = -1;
+static std::atomic<unsigned long> g_gemv_wide_launches{0};   // sessions launch from their own threads
+void set_gemv_wide(int v) { g_gemv_wide = v; }
+unsigned long gemv_wide_launches() { return g_gemv_wide_launches.load(std::memory_order_relaxed); }
+
+// ---- the workgroup-shared form (precision mode "split" only) ----------------------------------------------------------------
+// K-slices per tile group: a function of the MATRIX alone (so that every row count sums in the same order).  Measured on MI355X at
+// the 7b shapes, 8 and 32 rows (profiles/r04_b_kbench_gemv_wg.txt): one tile per wave beats tile pairs everywhere (twice the
+// workgroups), and every extra K-slice costs (the cross-workgroup hand-off) — so only as many slices as it takes to put >= 256
+// workgroups on the chip: qkv (768 tiles) 2, o / down (256) 4, gate-up / lm_head 1.
+static int wg_kslices(int ntiles, int K) {
+    const int groups = (ntiles + 3) / 4, lines = K / 64;
+    int ks = groups >= 256 ? 1 : groups >= 128 ? 2 : 4;
+    while (ks > 1 && lines / ks < 8) --ks;
+    return ks;
+}
+
 // Waves (= tiles) per workgroup: 4, or 6 where that lowers the tile count of the BUSIEST CU — round 6: with four tiles per workgroup
 // 7b gate / up is 344 workgroups (88 CUs hold two, 168 one: the launch lasts 8 tiles on a CU for 5.4 on average) and qkv 192 x 2
 // K-slices = 384 (half the CUs hold two); with six they are 230 and 256 workgroups, one per CU.  A function of the matrix alone
 // (the K-slices are wg_kslices's, whatever the choice: the sums keep their order; only the rstd partials are added per wave).
 // set_gemv_variant(2) keeps 4 everywhere (A/B), 3 takes 6 everywhere (tests).
-static int wg_waves(int ntiles, int ks) {
-    if (g_gemv_variant == 2) return 4;
-    if (g_gemv_variant == 3) return 6;   // (tests: the six-wave geometry on matrices too small to choose it)
+static int wg_waves(int ntiles, int ks, int variant_knob) {
+    if (variant_knob == 2) return 4;
+    if (variant_knob == 3) return 6;   // (tests: the six-wave geometry on matrices too small to choose it)
     auto busiest = [&](int w) { return (((ntiles + w - 1) / w) * ks + 255) / 256 * w; };   // tiles (x 1 / ks of K) of the busiest CU
     return busiest(6) < busiest(4) ? 6 : 4;
 }
 
-static void launch_gemv_wg(const GemvArgs& a0, int epi, hipStream_t s) {
-    GemvArgs a = a0;
+static GemvPlan plan_wg(const GemvArgs& a, int variant_knob) {
     const int ntiles = a.N / 16;
     int ks = a.ksplit > 1 ? a.ksplit : wg_kslices(ntiles, a.K);   // an explicit request (tests) is honoured
     const size_t cap = a.sk_scratch_floats ? a.sk_scratch_floats : (size_t)4 * 512 * 2 * 256;
     const int ncnt = a.sk_counters_n ? a.sk_counters_n : 512 * 2;
     // the split-K buffers bound the slices (a geometry decision of the matrix: the buffers are sized once per model)
     while (ks > 1 && (!a.sk_scratch || !a.sk_counters || (size_t)ks * ntiles * 2 * 256 > cap || ntiles * 2 > ncnt)) --ks;
-    a.ksplit = ks;
-    g_gemv_wg_launches.fetch_add(1, std::memory_order_relaxed);
+    GemvPlan p{};
+    p.form = GEMV_FORM_WG;
+    p.waves = wg_waves(ntiles, ks, variant_knob);
+    p.nt = 1;   // tiles per wave
+    p.xp = (a.M + 7) / 8;
+    p.wlo = a.Wp_lo != nullptr;
+    p.ksplit = ks;
     // chunk length / ring depth by the activation pieces per line, so that two workgroups fit a CU (<= 72 KiB each); with the
     // weight's lo plane (an inexact checkpoint) the slots are twice as large: one workgroup per CU (80 - 96 KiB)
-    const int xp = (a.M + 7) / 8;
-    if (wg_waves(ntiles, ks) == 6) {
+    p.cl = p.xp <= 2 ? 4 : 2;
+    p.r = 4;
+    if (p.waves == 6) {
         // six tiles per workgroup where that spreads the launch evenly (7b qkv: 128 groups x 2 K-slices = 256 workgroups; gate / up:
         // 230; 13b o / down: 54 x 4 = 216): ONE workgroup per CU, so the ring can be deeper (R = 6; 4 with the lo plane's blocks)
-        if (a.Wp_lo != nullptr) {
-            switch (xp) {
-                case 1: launch_gemv_wg_e<1, 3, 4, true, 6>(a, epi, s); break;
-                case 2: launch_gemv_wg_e<2, 3, 4, true, 6>(a, epi, s); break;
-                case 3: launch_gemv_wg_e<3, 2, 4, true, 6>(a, epi, s); break;
-                default: launch_gemv_wg_e<4, 3, 4, true, 6>(a, epi, s); break;
-            }
-            return;
-        }
-        switch (xp) {
-            case 1: launch_gemv_wg_e<1, 3, 6, false, 6>(a, epi, s); break;
-            case 2: launch_gemv_wg_e<2, 3, 6, false, 6>(a, epi, s); break;
-            case 3: launch_gemv_wg_e<3, 2, 6, false, 6>(a, epi, s); break;
-            default: launch_gemv_wg_e<4, 3, 6, false, 6>(a, epi, s); break;
-        }
-        return;
+        p.cl = p.xp == 3 ? 2 : 3;
+        p.r = p.wlo ? 4 : 6;
     }
-    if (a.Wp_lo != nullptr) {
-        switch (xp) {
-            case 1: launch_gemv_wg_e<1, 4, 4, true>(a, epi, s); break;
-            case 2: launch_gemv_wg_e<2, 4, 4, true>(a, epi, s); break;
-            case 3: launch_gemv_wg_e<3, 2, 4, true>(a, epi, s); break;
-            default: launch_gemv_wg_e<4, 2, 4, true>(a, epi, s); break;
-        }
-        return;
-    }
-    switch (xp) {
-        case 1: launch_gemv_wg_e<1, 4, 4, false>(a, epi, s); break;
-        case 2: launch_gemv_wg_e<2, 4, 4, false>(a, epi, s); break;
-        case 3: launch_gemv_wg_e<3, 2, 4, false>(a, epi, s); break;
-        default: launch_gemv_wg_e<4, 2, 4, false>(a, epi, s); break;
-    }
+    return p;
 }
+
+// ---- the ring kernel's geometry by tile count and row group -----------------------------------------------------------------
+// (waves, tiles per workgroup, ring slots) so that (where possible) every workgroup of the launch is resident at once — a tail of
+// late workgroups cannot keep enough bytes in flight to use the HBM (13b o_proj/down: 320 tiles at one 128-KiB workgroup per CU
+// ran a 64-workgroup second round at a third of the rate).  bf16 slots hold a k-tile pair, W8A16 slots one super-tile.
+// The 17..32-row columns (the decode pool; split mode on this kernel: 9..16 rows + their lo parts) serve two row groups per weight
+// pass.  The K partition (waves per workgroup, K-slices) of every class is the same in all four columns, so a row's result does
+// not depend on which served it; only the tiles per workgroup and the ring depth are re-balanced for the larger slots (LDS: all
+// workgroups resident).
+struct RingGeo {
+    int waves, nt, r;
+};
+struct RingClass {
+    int max_tiles;
+    RingGeo geo[2][2];   // [17..32 rows of X][W8A16]
+};
+static const RingClass kRingClasses[] = {
+    // tiles    <= 16 rows: bf16, W8A16     17..32 rows: bf16, W8A16
+    // 8 waves, deep ring (1 workgroup/CU)
+    {256, {{{8, 1, 4}, {8, 1, 5}}, {{8, 1, 3}, {8, 1, 3}}}},
+    // 4 waves, 5-slot ring (2 workgroups/CU)
+    {512, {{{4, 1, 5}, {4, 1, 5}}, {{4, 1, 3}, {4, 1, 3}}}},
+    // <= 16 rows: 4 waves x 1 tile (3/CU); W8A16: always pairs (X is 2x W).  17..32 rows as pairs too (2 workgroups/CU, the pair
+    // shares the activation pieces; 28.3 vs 33.9 us at M = 24 for one tile per workgroup)
+    {768, {{{4, 1, 3}, {4, 2, 3}}, {{4, 2, 2}, {4, 2, 2}}}},
+    // wider: 4 waves x 2 tiles (pairs share the activation fragments: gate/up 30.0 vs 33.1 us, lm_head 40.6 vs 45.5; 4 tiles per
+    // workgroup measured slower at <= 16 rows: W8A16 gate/up 23.2 vs 19.7 us)
+    {1535, {{{4, 2, 3}, {4, 2, 3}}, {{4, 2, 2}, {4, 2, 2}}}},
+    // W8A16 at 17..32 rows, the widest matrices (13b gate/up: 1728 tiles): 4 tiles per workgroup halve the activation bytes per
+    // weight byte — the bound of this kernel at 17..32 rows, DESIGN.md section 9.2 — same K partition (4 waves).  Measured at 32
+    // rows: 45.2 -> 35.3 us; with 1376 tiles (7b gate/up) the 344 single-resident workgroups balance badly over 256 CUs and it
+    // loses (26.2 -> 27.9 us), hence the threshold.
+    {INT_MAX, {{{4, 2, 3}, {4, 2, 3}}, {{4, 2, 2}, {4, 4, 2}}}},
+};
+// K-slices of the 257..512-tile class (13b o_proj / down: 320 tiles neither fill the chip one-per-CU nor balance two-per-CU):
+// with the split-K buffers, pairs of tiles x 3 K-slices = 480 workgroups, all resident (2/CU), activation fragments shared by
+// the pair (measured M = 16: down 43.0 -> 30.2 us, o_proj 20.1 -> 14.9; for <= 256 tiles every split loses: 8.5 -> 10 us).
+// An explicit a.ksplit is honoured: single tiles up to 256 tiles, pairs above.
+constexpr int KS_MID = 3;
+static const RingClass kRingSplitK[] = {
+    {256, {{{4, 1, 3}, {4, 1, 3}}, {{4, 1, 2}, {4, 1, 2}}}},
+    {INT_MAX, {{{4, 2, 3}, {4, 2, 3}}, {{4, 2, 2}, {4, 2, 2}}}},
+};
 
 // ---- "wide" geometry of the ring kernel (set_gemv_wide: -1 / 1 = the measured classes below, 0 = off, 2 = every class) ----------
 // ONE deep-ringed workgroup per CU, all 256 CUs holding exactly one, beats every geometry with more, unevenly spread workgroups
@@ -875,29 +762,12 @@ static void launch_gemv_wg(const GemvArgs& a0, int epi, hipStream_t s) {
 // more than 512 tiles: NT = ceil(tiles / 256) tiles per 4-wave workgroup (>= 218 workgroups, i.e. >= 85 % of the CUs), the ring as
 // deep as 160 KiB allow.  The K partition stays 4 waves without K-slices, so the bits are those of the default geometry (checked on
 // the device for every class and row count).  Measured on MI355X (profiles/r05_a_kbench_gemv_wide.txt, us, default -> wide at
-// 8 / 16 / 24 / 32 rows), which is what the default table below encodes:
+// 8 / 16 / 24 / 32 rows), which is what the bf16 column and its "from 9 rows on" rule in gemv_plan encode:
 //   NT 3: 7b qkv (768 tiles -> 256 workgroups)      18.7 -> 18.2 | 20.2 -> 18.7 | 23.4 -> 20.3 | 25.0 -> 20.2   => always
 //   NT 4: 13b qkv (960 -> 240)                      26.0 -> 26.5 | 27.7 -> 26.7 | 30.5 -> 28.6 | 32.6 -> 29.2   => from 9 rows on
 //   NT 6: 7b gate/up (1376 -> 230)                  30.6 -> 30.9 | 31.4 -> 30.9 | 33.0 -> 33.0 | 36.7 -> 33.4   => from 9 rows on
 //   NT 7: 13b gate/up (1728 -> 247)                 47.1 -> 46.9 | 50.4 -> 46.8 | 56.5 -> 48.9 | 61.4 -> 49.5   => always
-// (NT 8, lm_head 2000 -> 250, lost at every row count — 41.9 -> 47.5 us at 8 rows — and was removed.)
-static int g_gemv_wide = -1;
-static std::atomic<unsigned long> g_gemv_wide_launches{0};   // sessions launch from their own threads
-void set_gemv_wide(int v) { g_gemv_wide = v; }
-unsigned long gemv_wide_launches() { return g_gemv_wide_launches.load(std::memory_order_relaxed); }
-template <int NT, int R, int XP, int EPI>
-static void launch_gemv_wide1(const GemvArgs& a, hipStream_t s) {
-    constexpr int WAVES = 4;
-    const dim3 grid((a.N / 16 + NT - 1) / NT), block(WAVES * 64);
-    constexpr size_t shmem = (size_t)WAVES * R * (2 * NT + XP) * 1024;
-    static_assert(shmem + WAVES * 16 * ((XP + 1) / 2) * 4 <= 160 * 1024, "ring exceeds the LDS of a CU");
-    static bool once = false;
-    if (!once) {
-        allow_big_lds(gemv_dma_kernel<WAVES, NT, R, EPI, false, XP>, shmem);
-        once = true;
-    }
-    VC_LAUNCH((gemv_dma_kernel<WAVES, NT, R, EPI, false, XP>), grid, block, shmem, s, a);
-}
+// (NT 8, lm_head 2000 -> 250, lost at every row count — 41.9 -> 47.5 us at 8 rows — and was removed; NT 5 was never built.)
 // W8A16 (round 6): the same idea for the e4m3 weights at the pool's 17..32 rows.  A slot there is NT KiB of weights + 3-4 KiB of
 // activation pieces, so the pair geometry (NT = 2, a 2-slot ring, 2-3 workgroups per CU) keeps ~30 KiB of weights in flight per CU
 // — qkv 3.2, gate / up 4.1 TB/s at 13b (profiles/r06_ad_kernel_stats_13b_fp8.md); ceil(tiles / 256) tiles per workgroup put one
@@ -905,86 +775,170 @@ static void launch_gemv_wide1(const GemvArgs& a, hipStream_t s) {
 // NT / 2 times less often.  Four waves, no K-slices: the pair geometry's K partition, the same bits.  From 9 rows on (measured at 12 /
 // 16 / 24 / 32 rows, profiles/r06_af_kbench_gemv_rows8.txt: 13b gate / up 31.7 -> 27.0 us at 16 rows, 33.2 -> 29.8 at 32; 13b qkv 17.4
 // -> 16.6 and 23.9 -> 19.9; the one loss is 13b qkv at 12 rows, 16.4 -> 16.7); 8 rows and below keep pairs (slots of NT + 1 KiB).
-template <int NT, int R, int XP, int EPI>
-static void launch_gemv_wide8_1(const GemvArgs& a, hipStream_t s) {
-    constexpr int WAVES = 4;
-    const dim3 grid((a.N / 16 + NT - 1) / NT), block(WAVES * 64);
-    constexpr size_t shmem = (size_t)WAVES * R * (NT + XP) * 1024;
-    static_assert(shmem + WAVES * 16 * ((XP + 1) / 2) * 4 <= 160 * 1024, "ring exceeds the LDS of a CU");
-    static bool once = false;
-    if (!once) {
-        allow_big_lds(gemv_dma_kernel<WAVES, NT, R, EPI, true, XP>, shmem);
-        once = true;
-    }
-    VC_LAUNCH((gemv_dma_kernel<WAVES, NT, R, EPI, true, XP>), grid, block, shmem, s, a);
-}
-static bool launch_gemv_wide8(const GemvArgs& a, int epi, hipStream_t s) {
-    const int tiles = a.N / 16, xr = x_rows(a);
-    if (tiles <= 512 || xr <= 8 || a.K % 64 != 0) return false;
-    const int nt = (tiles + 255) / 256;
-    if ((tiles + nt - 1) / nt < 218) return false;
-    const int xp = xr <= 16 ? 2 : xr <= 24 ? 3 : 4;
-#define VC_WIDE8(NT_, R_, XP_, E_)                                         \
-    if (nt == NT_ && xp == XP_ && epi == E_) {                             \
-        launch_gemv_wide8_1<NT_, R_, XP_, E_>(a, s);                       \
-        g_gemv_wide_launches.fetch_add(1, std::memory_order_relaxed);      \
-        return true;                                                       \
-    }
-    VC_WIDE8(3, 7, 2, GEMV_BF16) VC_WIDE8(4, 6, 2, GEMV_BF16) VC_WIDE8(6, 4, 2, GEMV_SWIGLU) VC_WIDE8(7, 4, 2, GEMV_SWIGLU)
-    VC_WIDE8(3, 6, 3, GEMV_BF16) VC_WIDE8(3, 5, 4, GEMV_BF16) VC_WIDE8(4, 5, 3, GEMV_BF16) VC_WIDE8(4, 4, 4, GEMV_BF16)
-    VC_WIDE8(6, 4, 3, GEMV_SWIGLU) VC_WIDE8(6, 3, 4, GEMV_SWIGLU) VC_WIDE8(7, 3, 3, GEMV_SWIGLU) VC_WIDE8(7, 3, 4, GEMV_SWIGLU)
-#undef VC_WIDE8
-    return false;
-}
-static bool launch_gemv_wide(const GemvArgs& a, int epi, hipStream_t s) {
-    const int wide = g_gemv_wide < 0 ? 1 : g_gemv_wide;
-    if (!wide || a.ksplit > 1 || a.split_rows) return false;
-    if (a.wscale) return launch_gemv_wide8(a, epi, s);
-    const int tiles = a.N / 16;
-    if (tiles <= 512) return false;
-    const int nt = (tiles + 255) / 256;
-    if (nt > 7 || (tiles + nt - 1) / nt < 218) return false;
-    const int xr = x_rows(a), xp = xr <= 8 ? 1 : xr <= 16 ? 2 : xr <= 24 ? 3 : 4;
-    if (wide == 1 && xp == 1 && (nt == 4 || nt == 6)) return false;   // the two classes that lose at <= 8 rows (table above)
-#define VC_WIDE(NT_, R_, XP_, E_)                                          \
-    if (nt == NT_ && xp == XP_ && epi == E_) {                             \
-        launch_gemv_wide1<NT_, R_, XP_, E_>(a, s);                         \
-        g_gemv_wide_launches.fetch_add(1, std::memory_order_relaxed);      \
-        return true;                                                       \
-    }
-    VC_WIDE(3, 5, 1, GEMV_BF16) VC_WIDE(3, 4, 2, GEMV_BF16) VC_WIDE(3, 3, 3, GEMV_BF16) VC_WIDE(3, 3, 4, GEMV_BF16)
-    VC_WIDE(4, 4, 1, GEMV_BF16) VC_WIDE(4, 3, 2, GEMV_BF16) VC_WIDE(4, 3, 3, GEMV_BF16) VC_WIDE(4, 3, 4, GEMV_BF16)
-    VC_WIDE(6, 3, 1, GEMV_SWIGLU) VC_WIDE(6, 2, 2, GEMV_SWIGLU) VC_WIDE(6, 2, 3, GEMV_SWIGLU) VC_WIDE(6, 2, 4, GEMV_SWIGLU)
-    VC_WIDE(7, 2, 1, GEMV_SWIGLU) VC_WIDE(7, 2, 2, GEMV_SWIGLU) VC_WIDE(7, 2, 3, GEMV_SWIGLU) VC_WIDE(7, 2, 4, GEMV_SWIGLU)
-#undef VC_WIDE
-    return false;
-}
+// Each class is instantiated for the epilogue of its matrices only (qkv: GEMV_BF16, gate / up: GEMV_SWIGLU); any other call keeps
+// the pair geometry.
+struct WideClass {
+    int nt, epi;
+    int r[2][4];   // ring slots by [W8A16][activation pieces - 1]; 0 = keeps pairs (W8A16: from 9 rows on)
+};
+static const WideClass kWideClasses[] = {
+    // NT  epilogue      bf16: 8 / 16 / 24 / 32 rows   W8A16
+    {3, GEMV_BF16, {{5, 4, 3, 3}, {0, 7, 6, 5}}},
+    {4, GEMV_BF16, {{4, 3, 3, 3}, {0, 6, 5, 4}}},
+    {6, GEMV_SWIGLU, {{3, 2, 2, 2}, {0, 4, 4, 3}}},
+    {7, GEMV_SWIGLU, {{2, 2, 2, 2}, {0, 4, 3, 3}}},
+};
 
-void launch_gemv(const GemvArgs& a, int epilogue, hipStream_t s) {
-    if (gemv_wg_enabled() && gemv_wg_applies(a)) {
-        launch_gemv_wg(a, epilogue, s);
-        return;
-    }
+GemvPlan gemv_plan(const GemvArgs& a, int epilogue, int variant_knob, int wide_knob) {
+    if (variant_knob != 0 && gemv_wg_applies(a)) return plan_wg(a, variant_knob);
     if (a.Wp_lo != nullptr)
         throw std::runtime_error("decode GEMV: the weight lo plane of an inexact checkpoint is served by the workgroup-shared split form only "
                                  "(precision mode split, bf16 weights, K % 64 == 0, set_gemv_variant != 0)");
-    if (a.split_rows) {
-        // hi rows [0, M) + lo rows [G, G + M) of X; the two MFMA forms that combine them: G = 8 inside one 16-slot row group
-        // (M <= 8), G = 16 across the two row groups (M <= 16).  No split-K hand-off in this mode.
-        if (!((a.split_rows == 8 && a.M <= 8) || (a.split_rows == 16 && a.M <= 16)))
-            throw std::runtime_error("split GEMV: rows per pass must fit the group (G = 8: M <= 8, G = 16: M <= 16)");
-        GemvArgs b = a;
-        b.sk_scratch = nullptr;
-        b.sk_counters = nullptr;
-        b.ksplit = 0;
-        if (b.wscale) launch_gemv_f<true>(b, epilogue, s);
-        else launch_gemv_f<false>(b, epilogue, s);
-        return;
+    // hi rows [0, M) + lo rows [G, G + M) of X; the two MFMA forms that combine them: G = 8 inside one 16-slot row group
+    // (M <= 8), G = 16 across the two row groups (M <= 16).  No split-K hand-off and no wide geometry in this mode.
+    if (a.split_rows && !((a.split_rows == 8 && a.M <= 8) || (a.split_rows == 16 && a.M <= 16)))
+        throw std::runtime_error("split GEMV: rows per pass must fit the group (G = 8: M <= 8, G = 16: M <= 16)");
+    const int tiles = a.N / 16, xr = x_rows(a);
+    const int ksplit = a.split_rows ? 0 : a.ksplit;
+    const bool sk_buffers = !a.split_rows && a.sk_scratch && a.sk_counters;
+    GemvPlan p{};
+    p.fp8 = a.wscale != nullptr;
+    p.xp = xr <= 8 ? 1 : xr <= 16 ? 2 : xr <= 24 ? 3 : 4;   // 8-row activation pieces per slot
+    p.ksplit = 1;
+    const int wide = wide_knob < 0 ? 1 : wide_knob;
+    if (wide && ksplit <= 1 && !a.split_rows && tiles > 512) {
+        const int nt = (tiles + 255) / 256;
+        bool ok = (tiles + nt - 1) / nt >= 218;
+        if (p.fp8) ok = ok && a.K % 64 == 0;
+        else ok = ok && !(wide == 1 && p.xp == 1 && (nt == 4 || nt == 6));   // the two classes that lose at <= 8 rows
+        for (const WideClass& w : kWideClasses)
+            if (ok && w.nt == nt && w.epi == epilogue && w.r[p.fp8][p.xp - 1]) {
+                p.form = GEMV_FORM_WIDE;
+                p.waves = 4;
+                p.nt = nt;
+                p.r = w.r[p.fp8][p.xp - 1];
+                return p;
+            }
     }
-    if (launch_gemv_wide(a, epilogue, s)) return;
-    if (a.wscale) launch_gemv_f<true>(a, epilogue, s);
-    else launch_gemv_f<false>(a, epilogue, s);
+    const bool split_k = ksplit > 1 || (sk_buffers && ksplit == 0 && tiles > 256 && tiles <= 512);
+    if (split_k) p.ksplit = ksplit > 1 ? ksplit : KS_MID;
+    const RingClass* c = split_k ? kRingSplitK : kRingClasses;
+    while (tiles > c->max_tiles) ++c;
+    const RingGeo& g = c->geo[xr > 16][p.fp8];
+    p.form = GEMV_FORM_RING;
+    p.waves = g.waves;
+    p.nt = g.nt;
+    p.r = g.r;
+    // W8A16 slots are 4 KiB (3 pieces) / 5 KiB (4 pieces): a 4-slot ring of the latter would need all 160 KiB + ss_part
+    if (p.fp8 && !split_k && tiles <= 256 && p.xp == 3) p.r = 4;
+    return p;
 }
+GemvPlan gemv_plan(const GemvArgs& a, int epilogue) { return gemv_plan(a, epilogue, g_gemv_variant, g_gemv_wide); }
+
+// ---- the launch: one helper per kernel, one list of the instances that exist -----------------------------------------------------
+template <class K>
+static void allow_big_lds(K kernel, size_t bytes) {
+#ifndef VC_EMU
+    if (bytes > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+#endif
+}
+
+template <int WAVES, int NT, int R, int EPI, bool FP8, int XP>
+static void launch_ring(const GemvArgs& a, hipStream_t s) {
+    const dim3 grid(((a.N / 16 + NT - 1) / NT) * (a.ksplit > 1 ? a.ksplit : 1)), block(WAVES * 64);
+    constexpr size_t shmem = (size_t)WAVES * R * ((FP8 ? 1 : 2) * NT + XP) * 1024;
+    // + the kernel's static ss_part[WAVES][16 * MG] floats
+    static_assert(shmem + WAVES * 16 * ((XP + 1) / 2) * 4 <= 160 * 1024, "ring exceeds the LDS of a CU");
+    static bool once = false;
+    if (!once) {
+        allow_big_lds(gemv_dma_kernel<WAVES, NT, R, EPI, FP8, XP>, shmem);
+        once = true;
+    }
+    VC_LAUNCH((gemv_dma_kernel<WAVES, NT, R, EPI, FP8, XP>), grid, block, shmem, s, a);
+}
+
+template <int XP, int CL, int R, int EPI, bool WL, int WAVES>
+static void launch_wg(const GemvArgs& a, hipStream_t s) {
+    constexpr int NTW = 1, KH = 2;
+    const int groups = (a.N / 16 + WAVES * NTW - 1) / (WAVES * NTW);
+    const dim3 grid((unsigned)(groups * (a.ksplit > 1 ? a.ksplit : 1))), block(WAVES * 64);
+    constexpr size_t shmem = (size_t)(2 * CL * XP * KH + WAVES * R * 2 * NTW * (WL ? 2 : 1)) * 1024;
+    static_assert(shmem + WAVES * 16 * ((XP + 1) / 2) * 4 <= 160 * 1024, "exceeds the LDS of a CU");
+    static bool once = false;
+    if (!once) {
+        allow_big_lds(gemv_wg_kernel<NTW, XP, KH, CL, R, EPI, WL, WAVES>, shmem);
+        once = true;
+    }
+    VC_LAUNCH((gemv_wg_kernel<NTW, XP, KH, CL, R, EPI, WL, WAVES>), grid, block, shmem, s, a);
+}
+
+// the epilogues a row is instantiated for: I(epilogue, row...) once per epilogue
+#define VC_EPI_ALL(I, ...) I(GEMV_BF16, __VA_ARGS__) I(GEMV_F32, __VA_ARGS__) I(GEMV_RESID_F32, __VA_ARGS__) I(GEMV_SWIGLU, __VA_ARGS__)
+#define VC_EPI_QKV(I, ...) I(GEMV_BF16, __VA_ARGS__)
+#define VC_EPI_GATE_UP(I, ...) I(GEMV_SWIGLU, __VA_ARGS__)
+// every gemv_dma_kernel instance in the library: X(FP8, WAVES, NT, R, XP, epilogues) — the cells of kRingClasses / kRingSplitK with
+// the piece counts of their column (1, 2 | 3, 4), then those of kWideClasses.  (true, 8, 1, 3, 3) is chosen by no plan — three W8A16
+// pieces take the 4-slot ring — and stays so that the library's set of kernels is the one the measurements were made with.
+#define VC_GEMV_RING_INSTANCES(X)                                                                                                   \
+    X(false, 8, 1, 4, 1, VC_EPI_ALL) X(false, 8, 1, 4, 2, VC_EPI_ALL) X(false, 8, 1, 3, 3, VC_EPI_ALL) X(false, 8, 1, 3, 4, VC_EPI_ALL) \
+    X(false, 4, 1, 5, 1, VC_EPI_ALL) X(false, 4, 1, 5, 2, VC_EPI_ALL) X(false, 4, 1, 3, 3, VC_EPI_ALL) X(false, 4, 1, 3, 4, VC_EPI_ALL) \
+    X(false, 4, 1, 3, 1, VC_EPI_ALL) X(false, 4, 1, 3, 2, VC_EPI_ALL) X(false, 4, 1, 2, 3, VC_EPI_ALL) X(false, 4, 1, 2, 4, VC_EPI_ALL) \
+    X(false, 4, 2, 3, 1, VC_EPI_ALL) X(false, 4, 2, 3, 2, VC_EPI_ALL) X(false, 4, 2, 2, 3, VC_EPI_ALL) X(false, 4, 2, 2, 4, VC_EPI_ALL) \
+    X(true, 8, 1, 5, 1, VC_EPI_ALL) X(true, 8, 1, 5, 2, VC_EPI_ALL) X(true, 8, 1, 4, 3, VC_EPI_ALL) X(true, 8, 1, 3, 3, VC_EPI_ALL)     \
+    X(true, 8, 1, 3, 4, VC_EPI_ALL)                                                                                                 \
+    X(true, 4, 1, 5, 1, VC_EPI_ALL) X(true, 4, 1, 5, 2, VC_EPI_ALL) X(true, 4, 1, 3, 3, VC_EPI_ALL) X(true, 4, 1, 3, 4, VC_EPI_ALL)     \
+    X(true, 4, 1, 3, 1, VC_EPI_ALL) X(true, 4, 1, 3, 2, VC_EPI_ALL) X(true, 4, 1, 2, 3, VC_EPI_ALL) X(true, 4, 1, 2, 4, VC_EPI_ALL)     \
+    X(true, 4, 2, 3, 1, VC_EPI_ALL) X(true, 4, 2, 3, 2, VC_EPI_ALL) X(true, 4, 2, 2, 3, VC_EPI_ALL) X(true, 4, 2, 2, 4, VC_EPI_ALL)     \
+    X(true, 4, 4, 2, 3, VC_EPI_ALL) X(true, 4, 4, 2, 4, VC_EPI_ALL)                                                                 \
+    X(false, 4, 3, 5, 1, VC_EPI_QKV) X(false, 4, 3, 4, 2, VC_EPI_QKV) X(false, 4, 3, 3, 3, VC_EPI_QKV) X(false, 4, 3, 3, 4, VC_EPI_QKV) \
+    X(false, 4, 4, 4, 1, VC_EPI_QKV) X(false, 4, 4, 3, 2, VC_EPI_QKV) X(false, 4, 4, 3, 3, VC_EPI_QKV) X(false, 4, 4, 3, 4, VC_EPI_QKV) \
+    X(false, 4, 6, 3, 1, VC_EPI_GATE_UP) X(false, 4, 6, 2, 2, VC_EPI_GATE_UP) X(false, 4, 6, 2, 3, VC_EPI_GATE_UP)                  \
+    X(false, 4, 6, 2, 4, VC_EPI_GATE_UP)                                                                                            \
+    X(false, 4, 7, 2, 1, VC_EPI_GATE_UP) X(false, 4, 7, 2, 2, VC_EPI_GATE_UP) X(false, 4, 7, 2, 3, VC_EPI_GATE_UP)                  \
+    X(false, 4, 7, 2, 4, VC_EPI_GATE_UP)                                                                                            \
+    X(true, 4, 3, 7, 2, VC_EPI_QKV) X(true, 4, 3, 6, 3, VC_EPI_QKV) X(true, 4, 3, 5, 4, VC_EPI_QKV)                                 \
+    X(true, 4, 4, 6, 2, VC_EPI_QKV) X(true, 4, 4, 5, 3, VC_EPI_QKV) X(true, 4, 4, 4, 4, VC_EPI_QKV)                                 \
+    X(true, 4, 6, 4, 2, VC_EPI_GATE_UP) X(true, 4, 6, 4, 3, VC_EPI_GATE_UP) X(true, 4, 6, 3, 4, VC_EPI_GATE_UP)                     \
+    X(true, 4, 7, 4, 2, VC_EPI_GATE_UP) X(true, 4, 7, 3, 3, VC_EPI_GATE_UP) X(true, 4, 7, 3, 4, VC_EPI_GATE_UP)
+// every gemv_wg_kernel instance: X(XP, CL, R, WL, WAVES, epilogues) — plan_wg's choices
+#define VC_GEMV_WG_INSTANCES(X)                                                                                                     \
+    X(1, 4, 4, false, 4, VC_EPI_ALL) X(2, 4, 4, false, 4, VC_EPI_ALL) X(3, 2, 4, false, 4, VC_EPI_ALL) X(4, 2, 4, false, 4, VC_EPI_ALL) \
+    X(1, 4, 4, true, 4, VC_EPI_ALL) X(2, 4, 4, true, 4, VC_EPI_ALL) X(3, 2, 4, true, 4, VC_EPI_ALL) X(4, 2, 4, true, 4, VC_EPI_ALL)     \
+    X(1, 3, 6, false, 6, VC_EPI_ALL) X(2, 3, 6, false, 6, VC_EPI_ALL) X(3, 2, 6, false, 6, VC_EPI_ALL) X(4, 3, 6, false, 6, VC_EPI_ALL) \
+    X(1, 3, 4, true, 6, VC_EPI_ALL) X(2, 3, 4, true, 6, VC_EPI_ALL) X(3, 2, 4, true, 6, VC_EPI_ALL) X(4, 3, 4, true, 6, VC_EPI_ALL)
+
+void launch_gemv(const GemvArgs& a0, int epilogue, hipStream_t s) {
+    const GemvPlan p = gemv_plan(a0, epilogue);
+    GemvArgs a = a0;
+    a.ksplit = p.ksplit;
+    if (p.form != GEMV_FORM_WG && a.split_rows) {   // the ring kernel's split mode has no split-K hand-off
+        a.sk_scratch = nullptr;
+        a.sk_counters = nullptr;
+    }
+    if (p.form == GEMV_FORM_WIDE) g_gemv_wide_launches.fetch_add(1, std::memory_order_relaxed);
+    if (p.form == GEMV_FORM_WG) g_gemv_wg_launches.fetch_add(1, std::memory_order_relaxed);
+#define VC_TRY_RING(E, FP8, WAVES, NT, R, XP) \
+    if (epilogue == E && p.fp8 == FP8 && p.waves == WAVES && p.nt == NT && p.r == R && p.xp == XP) return launch_ring<WAVES, NT, R, E, FP8, XP>(a, s);
+#define VC_TRY_WG(E, XP, CL, R, WL, WAVES) \
+    if (epilogue == E && p.xp == XP && p.cl == CL && p.r == R && p.wlo == WL && p.waves == WAVES) return launch_wg<XP, CL, R, E, WL, WAVES>(a, s);
+#define VC_ROW_RING(FP8, WAVES, NT, R, XP, EPIS) EPIS(VC_TRY_RING, FP8, WAVES, NT, R, XP)
+#define VC_ROW_WG(XP, CL, R, WL, WAVES, EPIS) EPIS(VC_TRY_WG, XP, CL, R, WL, WAVES)
+    if (p.form == GEMV_FORM_WG) {
+        VC_GEMV_WG_INSTANCES(VC_ROW_WG)
+    } else {
+        VC_GEMV_RING_INSTANCES(VC_ROW_RING)
+    }
+#undef VC_ROW_WG
+#undef VC_ROW_RING
+#undef VC_TRY_WG
+#undef VC_TRY_RING
+    throw std::logic_error("decode GEMV: no kernel instance for the plan form " + std::to_string(p.form) + " waves " + std::to_string(p.waves) +
+                           " nt " + std::to_string(p.nt) + " r " + std::to_string(p.r) + " xp " + std::to_string(p.xp) + " cl " +
+                           std::to_string(p.cl) + " fp8 " + std::to_string(p.fp8) + " wlo " + std::to_string(p.wlo) + " ksplit " +
+                           std::to_string(p.ksplit) + " epilogue " + std::to_string(epilogue));
+}
+
 
 // ---- W8A16 quantiser (load time).  One workgroup per output row n of W [N, K] bf16:
 //   s_n = 2^e, e = the smallest integer with absmax_n <= 448 * 2^e     (power of two -> W/s and q*s are exact)

@@ -1,6 +1,8 @@
 // kernel_api.cpp — C-ABI entry points over the individual kernel launchers (declared in
 // include/vcoder_kernels.h).  The `-m gpu` parity tests call every kernel through these with device
 // pointers; the CPU emulator build (tests/emu) exports the same symbols over host pointers.
+#include <stdexcept>
+
 #include "kernels.h"
 using namespace vc;
 
@@ -287,6 +289,30 @@ VCK_EXPORT void vck_gemv_full(const uint16_t* X, const void* Wp, const float* ws
     a.sk_scratch_floats = (size_t)sk_scratch_floats; a.sk_counters_n = sk_counters_n;
     a.split_rows = G;
     launch_gemv(a, epi, S(stream));
+}
+/* what vck_gemv_full would launch for these arguments under the current knobs, without launching (only which optional buffers are
+ * present matters, not where they are): 0 and out = {form, waves, nt, r, xp, cl, fp8, wlo, ksplit, workgroups}, or -1 where the
+ * call would be refused */
+VCK_EXPORT int vck_gemv_plan(int M, int N, int K, int epi, int fp8, int split_rows, int ksplit, int has_sk,
+                             unsigned long long sk_scratch_floats, int sk_counters_n, int has_wlo, int out[10]) {
+    static float present_f;
+    static unsigned present_u;
+    static const uint16_t present_h = 0;
+    GemvArgs a{};
+    a.M = M; a.N = N; a.K = K; a.split_rows = split_rows; a.ksplit = ksplit;
+    if (fp8) a.wscale = &present_f;
+    if (has_sk) { a.sk_scratch = &present_f; a.sk_counters = &present_u; }
+    a.sk_scratch_floats = (size_t)sk_scratch_floats; a.sk_counters_n = sk_counters_n;
+    if (has_wlo) a.Wp_lo = &present_h;
+    try {
+        const GemvPlan p = gemv_plan(a, epi);
+        const int per_wg = p.form == GEMV_FORM_WG ? p.waves * p.nt : p.nt;
+        const int v[10] = {p.form, p.waves, p.nt, p.r, p.xp, p.cl, p.fp8, p.wlo, p.ksplit, (N / 16 + per_wg - 1) / per_wg * p.ksplit};
+        for (int i = 0; i < 10; ++i) out[i] = v[i];
+        return 0;
+    } catch (const std::runtime_error&) {
+        return -1;
+    }
 }
 /* split-mode GEMV: 0 = per-wave rings, 1 / -1 = workgroup-shared activation chunks (default) */
 VCK_EXPORT void vck_set_gemv_variant(int v) { set_gemv_variant(v); }

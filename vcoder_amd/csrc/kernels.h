@@ -148,12 +148,27 @@ struct GemvArgs {
     const bf16_t* Wp_lo;
 };
 void launch_gemv(const GemvArgs& a, int epilogue, hipStream_t s);
+// What launch_gemv launches for a call: the kernel instance and the K-slices, a pure function of the arguments and the two knobs
+// (decode.hip: the geometry tables).  Throws std::runtime_error for the calls launch_gemv refuses.
+enum GemvForm : int {
+    GEMV_FORM_RING = 0,  // gemv_dma_kernel, pair / single-tile geometry by tile-count class
+    GEMV_FORM_WIDE = 1,  // gemv_dma_kernel, one deep-ringed workgroup per CU
+    GEMV_FORM_WG = 2,    // gemv_wg_kernel (precision mode "split")
+};
+struct GemvPlan {
+    int form;
+    int waves, nt, r, xp, cl;   // template parameters of the kernel instance (nt: tiles per workgroup, per wave in the wg form; cl: wg form only)
+    bool fp8, wlo;
+    int ksplit;                 // the K-slices launched (>= 1)
+};
+GemvPlan gemv_plan(const GemvArgs& a, int epilogue, int variant_knob, int wide_knob);
+GemvPlan gemv_plan(const GemvArgs& a, int epilogue);   // ... with the current set_gemv_variant / set_gemv_wide values
 // the decode GEMV of precision mode "split": 0 = per-wave rings (two weight passes of 16 rows), -1 / 1 = the workgroup-shared form
 void set_gemv_variant(int v);
 void set_gemm_force_8phase(bool on);   // test hook: the bf16 GEMMs of every size take the 8-phase 256 x 256 kernel
 unsigned long gemm_dma_launches();      // launches launch_gemm sent to the 128 x 128 LDS-DMA kernel so far (tests)
 unsigned long gemm_8phase_launches();   // ... and to the 8-phase 256 x 256 kernel (split-K fix-up launches not counted)
-void set_gemv_wide(int v);       // -1 / 1 = the measured classes (default), 0 = off, 2 = every class (launch_gemv_wide)
+void set_gemv_wide(int v);       // -1 / 1 = the measured classes (default), 0 = off, 2 = every class (decode.hip kWideClasses)
 unsigned long gemv_wide_launches();
 bool gemv_wg_enabled();                          // the workgroup-shared form serves the split step's GEMVs
 bool gemv_wg_applies(int K, bool fp8_weights);   // ... for a matrix with this K / weight format
