@@ -235,6 +235,16 @@ int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logits_all, 
 int vc_request_token_scores(vc_model* m, const int64_t* labels, int B, int T, float* logprobs /* [B, S] or [B, n] host */,
                             int64_t* spliced_labels /* same shape, may be NULL */, size_t cap /* elements of each output buffer */);
 
+/* Top-K alternatives of the scored positions (one-shot): accompanies a PENDING vc_request_token_scores and shares its lifetime (the
+ * scored vc_prefill / vc_extend consumes both; cancelling or replacing the score request drops it).  That call fills, at every
+ * position that carries a score, top_ids / top_logprobs [B, S] or [B, n] x top_k with the top_k most likely tokens of the row in front
+ * of it — what the model would have said instead of the label — ordered by (log-prob descending, id ascending; ties break as the
+ * greedy argmax breaks them), each as logit - logsumexp over the fp32 logits; positions without a score hold 0.0 / -1.  top_k in
+ * 1 .. 32; cap = entries of each buffer (>= B * S * top_k resp. B * n * top_k, else that call fails with VC_ERR_INVALID, the
+ * session's cache and position unchanged).  Without a pending score request: VC_ERR_STATE. */
+int vc_request_top_logprobs(vc_model* m, int top_k, float* top_logprobs /* [B, S] or [B, n] x top_k host */,
+                            int32_t* top_ids /* same shape */, size_t cap);
+
 /* the loop steps back to position P (prefill's S <= P <= current position): cached rows >= P are dead.  Nothing is copied; the
  * prefill's hidden keys stay hidden; every precision mode.  The token the last step selected on the device is no longer valid:
  * vc_decode_step(tok = NULL) returns VC_ERR_STATE until a vc_extend or a vc_decode_step with explicit tokens has run.  K candidate
@@ -281,6 +291,25 @@ int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const float* img,
                 int pixels_on_device, int max_new, int eos_id, int pad_id, const int32_t* stop_ids, const int32_t* stop_lens,
                 int n_stop, const vc_sampling* samp, vc_token_cb cb, void* cb_user, int cb_every, int32_t* out_ids,
                 int* n_generated);
+
+/* Per-token log-probs of the NEXT vc_generate / vc_generate_greedy* call (one-shot; HF: generate(output_scores=True) +
+ * compute_transition_scores(normalize_logits=True), a serving API's logprobs / top_logprobs) without logits leaving the device:
+ *   token_logprobs [B, max_new]        log p(generated token)
+ *   top_ids / top_logprobs [B, max_new, top_k]   the top_k most likely tokens of every step, ordered by (log-prob descending, id
+ *                                      ascending — ties break as the greedy argmax breaks them); NULL iff top_k == 0
+ * of the model's own next-token distribution: log_softmax of the step's fp32 logits, taken BEFORE temperature / top-k / top-p, also
+ * when sampling.  A kernel behind every selection of the loop reduces the step's logits rows; the slabs come back once, beside
+ * out_ids.  A row's finishing token (its EOS, or the token that completes a stop sequence) is scored; positions behind it (the row
+ * emits pad there) and columns the loop never reached hold 0.0 / 0.0 / -1.  When a greedy row's token is among its top ids, the two
+ * log-probs are bit-equal.
+ * The call then runs on the session's own loop (every precision mode, whatever VC_POOL says): the decode pool does not serve
+ * log-probs.  The ids are those of the same call without the request.  Buffers: host, cap_rows rows ([.] or [top_k] per row), valid
+ * until that call returns; cap_rows < B * max_new makes that call fail with VC_ERR_INVALID before anything is touched.  top_k
+ * outside 0 .. 32 (or a missing buffer): VC_ERR_INVALID here, nothing changed.  Cleared when that call returns, also when it fails;
+ * every other entry point ignores and clears it; token_logprobs == NULL cancels. */
+int vc_request_generate_logprobs(vc_model* m, int top_k, float* token_logprobs /* [B, max_new] host */,
+                                 float* top_logprobs /* [B, max_new, top_k] host, NULL iff top_k == 0 */,
+                                 int32_t* top_ids /* same shape */, size_t cap_rows /* >= B * max_new of the call it applies to */);
 
 /* spliced sequence length (text rows + feature rows) of the last vc_generate_greedy* call: lets a caller that splits a large
  * batch into replica-sized pieces reproduce the reference's whole-batch behaviour for unequal lengths (quirk 6) */

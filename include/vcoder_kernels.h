@@ -121,6 +121,20 @@ void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, void* 
  * the row starts need no alignment; columns V..ldl are never read).  -inf entries are legal while one entry of the row is finite; a
  * -inf target gives -inf.  target[r] in [0, V). */
 void vck_token_logprob(const float* logits, int ldl, const int* target, float* logprob, int rows, int V, void* stream);
+/* log-prob of a chosen token and the K most likely tokens of every row (generate(logprobs), score(top_logprobs)); rows as above.
+ *   chosen_lp[r]    = logits[r, chosen[r]] - logsumexp(logits[r, 0:V]); a -inf logit gives -inf, chosen[r] < 0 gives 0.0
+ *                     (chosen == NULL: every row 0.0; chosen_lp == NULL: not written)
+ *   top_ids[r, 0:K], top_lp[r, 0:K]: the K largest logits of the row ordered by (value descending, id ascending) — ties break as
+ *                     the greedy argmax breaks them — each as logit - logsumexp; when fewer than K entries are finite the
+ *                     remaining slots hold id -1 and -inf.  K in 0 .. VC_MAX_TOP_LOGPROBS (K = 0: top_lp / top_ids untouched;
+ *                     outside the range nothing is launched).
+ * The log-prob of an id is the same expression wherever it appears: chosen_lp[r] is bit-equal to the top_lp entry of chosen[r].
+ * The selection is exact (bisection over the order-preserving integer image of the values; -0.0 ties with +0.0).  lds_floats: LDS
+ * floats the row may be staged in — < 0: what the device allows, 0 (or < V): every pass re-reads the row from global memory;
+ * both paths give the same bits. */
+#define VC_MAX_TOP_LOGPROBS 32
+void vck_topk_logprob(const float* logits, int ldl, const int* chosen, float* chosen_lp, float* top_lp, int32_t* top_ids, int rows,
+                      int V, int K, int lds_floats, void* stream);
 void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w, uint16_t* xg, int B,
                           int D, int npart, void* stream);
 void vck_advance(int* step_dev, int* pos_dev, int* ctx_dev, void* stream);

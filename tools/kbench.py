@@ -608,6 +608,52 @@ def bench_token_logprob():
         print(f"argmax scan   rows {rows:4d} V {V}: {us:7.1f} us  {gbs:7.1f} GB/s = {gbs / 8000:.2f} of 8 TB/s", flush=True)
 
 
+def bench_topk_logprob():
+    """topk_logprob_kernel over [rows, 32000] fp32 logits at K = 0 / 5 / 32 (rows 8 / 32: a decode step's launch; 1024: a score chunk), beside
+    token_logprob_kernel, the greedy row scan of select_embed_kernel and its sampled path at top_k = 50 (the same 32-pass bisection
+    over the row in LDS) over the same buffers"""
+    V = 32000
+    stride = int(lib.vck_row_state_stride())
+    for rows in (8, 32, 1024):
+        lg = [torch.randn(rows, V, device=dev) * 3 for _ in range(4)]
+        tgt = torch.randint(0, V, (rows,), dtype=torch.int32, device=dev)
+        out = torch.zeros(rows, device=dev)
+        tlp = torch.zeros((rows, 32), device=dev)
+        tid = torch.zeros((rows, 32), dtype=torch.int32, device=dev)
+        it = [0]
+        for K in (0, 5, 32):
+            for lds in (-1, 0):
+                if K == 0 and lds == 0:
+                    continue
+
+                def f():
+                    it[0] += 1
+                    lib.vck_topk_logprob(P(lg[it[0] % 4]), V, P(tgt), P(out), P(tlp), P(tid), rows, V, K, lds, None)
+                us = timeit(f, iters=40)
+                print(f"topk_logprob  rows {rows:4d} V {V} K {K:2d} {'staged  ' if lds else 'unstaged'}: {us:7.1f} us", flush=True)
+
+        def tl():
+            it[0] += 1
+            lib.vck_token_logprob(P(lg[it[0] % 4]), V, P(tgt), P(out), rows, V, None)
+        print(f"token_logprob rows {rows:4d} V {V}: {timeit(tl, iters=40):7.1f} us", flush=True)
+        for sample in (0, 1):
+            rs = torch.zeros((rows, stride), dtype=torch.int32, device=dev)
+            rs[:, 0] = 1    # RS_ACTIVE
+            rs[:, 5] = -1   # RS_EOS: none
+            rs[:, 8] = sample
+            rs[:, 9] = 0x3F800000   # RS_INVTEMP: 1.0
+            rs[:, 10] = 50          # RS_TOPK
+            rs[:, 11] = 0x3F800000  # RS_TOPP: 1.0 (off)
+            rs[:, 14] = torch.arange(rows, dtype=torch.int32, device=dev)   # RS_OUT_OFF
+            nxt = torch.zeros(rows, dtype=torch.int32, device=dev)
+            ids = torch.zeros(rows, dtype=torch.int32, device=dev)
+
+            def g():
+                it[0] += 1
+                lib.vck_select_embed(P(lg[it[0] % 4]), V, P(rs), P(nxt), P(ids), None, None, None, None, None, 4096, 16, V, rows, 0, None)
+            print(f"{'select top_k=50' if sample else 'argmax scan    '} rows {rows:4d} V {V}: {timeit(g, iters=40):7.1f} us", flush=True)
+
+
 def bench_score_head():
     """The score path's chunk at 7b dims (D 4096, V 32000): gathered final RMSNorm + lm_head + token_logprob over M scored rows (16 .. 1024), the
     lm_head as ceil(M / 32) passes of the weight-streaming GEMV (packed weights) against one GEMM — the crossover behind
@@ -682,6 +728,7 @@ if __name__ == "__main__":
              "gemm_f8": bench_gemm_f8, "gemv_rows8": bench_gemv_rows8, "gemv_wide": bench_gemv_wide, "gemm_chunk": bench_gemm_chunk,
              "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,
              "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn, "token_logprob": bench_token_logprob,
+             "topk_logprob": bench_topk_logprob,
              "score_head": bench_score_head}
     for w in what:
         table[w]()

@@ -101,6 +101,12 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_reorder_cache.restype = C.c_int
     lib.vc_request_token_scores.argtypes = [vp, vp, i32, i32, vp, vp, C.c_size_t]
     lib.vc_request_token_scores.restype = C.c_int
+    lib.vc_request_top_logprobs.argtypes = [vp, i32, vp, vp, C.c_size_t]
+    lib.vc_request_top_logprobs.restype = C.c_int
+    lib.vc_request_generate_logprobs.argtypes = [vp, i32, vp, vp, vp, C.c_size_t]
+    lib.vc_request_generate_logprobs.restype = C.c_int
+    lib.vck_topk_logprob.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.vck_topk_logprob.restype = None
     lib.vc_rewind.argtypes = [vp, i32]
     lib.vc_rewind.restype = C.c_int
     lib.vc_request_attentions.argtypes = [vp, vp, C.c_size_t]

@@ -196,6 +196,24 @@ struct vc_model {
     bool score_on = false;
     std::vector<int64_t> spliced_labels;   // [B, S] of the prefill being scored (IGNORE_INDEX on feature rows and right padding)
     Buf sc_idx, sc_lp, sc_xn, sc_logits;   // scored rows: indices | targets, log-probs, normed rows and logits of one chunk
+    // top-K alternatives of the scored positions (vc_request_top_logprobs; travels with the token-score request): the host buffers
+    // [B, S] or [B, n] x top_k the scored call fills, cap entries each
+    int stk_k = 0;
+    float* stk_lp = nullptr;
+    int32_t* stk_ids = nullptr;
+    size_t stk_cap = 0;
+    Buf sc_tlp, sc_tid;           // scored rows x top_k: log-probs and ids of one call
+    // per-token log-probs of the NEXT vc_generate* (vc_request_generate_logprobs; one-shot): the host buffers [B, max_new] and
+    // [B, max_new, top_k] (cap_rows rows each), and — while that call runs on the session's loop — lp_on: the loop's steps then
+    // carry a topk_logprob launch behind their selection, writing the slabs below (laid out like out_ids: row stride out_stride)
+    int glp_k = 0;
+    float* glp_tok = nullptr;
+    float* glp_top = nullptr;
+    int32_t* glp_ids = nullptr;
+    size_t glp_cap = 0;
+    bool lp_on = false;
+    int lp_k = 0;
+    Buf lp_tok, lp_top, lp_ids;
     bool tok_stale = false;       // vc_rewind ran: the token the last step selected on the device no longer continues the sequence
     bool plan_only = false;       // do_prefill stops behind the splice plan (vc_plan_spliced_len): no tower pass, no state change
     int reserve_new = 64;         // KV slots a vc_prefill keeps free behind the prompt (vc_model_reserve_decode)
@@ -216,6 +234,9 @@ struct vc_model {
     int last_S = 0;               // spliced prompt length of the last prefill / generate
     hipGraphExec_t graph = nullptr;  // one decode step over graph_rows rows (parameters live in the RowState records)
     int graph_rows = 0;
+    hipGraphExec_t graph_lp = nullptr;   // the same step with the log-prob launch (lp_on), for graph_lp_k alternatives
+    int graph_lp_rows = 0, graph_lp_k = 0;
+    bool graph_lp_masked = false;
     struct vc_pool* pool = nullptr;  // the root model's shared decode pool (created on first use; sessions point at it)
     bool pool_profile = false;       // root model: the pool's step graphs carry in-situ timing stamps (vc_pool_profile)
     bool fp8_kv = true;              // weight format 2: the KV cache of the bf16-step modes in e4m3 (vc_model_set_fp8_kv)
@@ -249,6 +270,16 @@ static void clear_score_request(vc_model* m) {
     m->score_labels_out = nullptr;
     m->score_cap = 0;
     m->score_on = false;
+    m->stk_k = 0;
+    m->stk_lp = nullptr;
+    m->stk_ids = nullptr;
+    m->stk_cap = 0;
+}
+static void clear_generate_logprobs_request(vc_model* m) {
+    m->glp_k = 0;
+    m->glp_tok = m->glp_top = nullptr;
+    m->glp_ids = nullptr;
+    m->glp_cap = 0;
 }
 
 // the one-shot requests of the NEXT prefill / generate call (vc_set_image_counts, vc_set_attention_mask,
@@ -264,6 +295,7 @@ struct OneShotReset {
         m->attn_out = nullptr;
         m->attn_cap = 0;
         clear_score_request(m);
+        clear_generate_logprobs_request(m);
     }
 };
 

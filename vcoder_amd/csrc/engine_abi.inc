@@ -176,8 +176,7 @@ VC_API void vc_model_destroy(vc_model* m) {
         pool_destroy(m->pool);
         m->pool = nullptr;
     }
-    if (m->graph) (void)hipGraphExecDestroy(m->graph);
-    m->graph = nullptr;
+    drop_graph(m);
     if (m->owns_weights)
         for (void* p : m->owned) (void)hipFree(p);
     for (Buf* b : {&m->stage, &m->stage2, &m->v_pixels, &m->v_cols, &m->v_patches, &m->v_x, &m->v_xn, &m->v_qkv, &m->v_q,
@@ -188,7 +187,8 @@ VC_API void vc_model_destroy(vc_model* m) {
                    &m->s_vq, &m->s_vk, &m->s_vv, &m->s_vattn, &m->s_vh, &m->s_sel, &m->s_mid, &m->s_feats, &m->s_xn, &m->s_qkv,
                    &m->s_q, &m->s_attn, &m->s_h, &m->s_kc, &m->s_vc, &m->s_xl, &m->pp_src, &m->pp_sq, &m->pp_tmp, &m->pp_out,
                    &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre,
-                   &m->ext_tok, &m->sc_idx, &m->sc_lp, &m->sc_xn, &m->sc_logits})
+                   &m->ext_tok, &m->sc_idx, &m->sc_lp, &m->sc_xn, &m->sc_logits, &m->sc_tlp, &m->sc_tid, &m->lp_tok, &m->lp_top,
+                   &m->lp_ids})
         b->release();
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
@@ -600,6 +600,48 @@ VC_API int vc_request_token_scores(vc_model* m, const int64_t* labels, int B, in
     return VC_OK;
 }
 
+/* Top-K alternatives of the scored positions: accompanies the pending vc_request_token_scores (one-shot with it).  The scored call fills
+ * top_logprobs / top_ids (host, [B, S] or [B, n] x top_k, cap entries each) at the positions that carry a score; 0.0 / -1 elsewhere.
+ * See include/vcoder_hip.h. */
+VC_API int vc_request_top_logprobs(vc_model* m, int top_k, float* top_logprobs, int32_t* top_ids, size_t cap) {
+    if (!m) return VC_ERR_INVALID;
+    if (m->score_labels.empty()) {
+        m->ctx->err = "vc_request_top_logprobs without a pending vc_request_token_scores";
+        return VC_ERR_STATE;
+    }
+    if (top_k < 1 || top_k > VC_MAX_TOP_LOGPROBS || !top_logprobs || !top_ids) {
+        m->ctx->err = "vc_request_top_logprobs needs top_k in 1 .. 32 and both output buffers";
+        return VC_ERR_INVALID;
+    }
+    m->stk_k = top_k;
+    m->stk_lp = top_logprobs;
+    m->stk_ids = top_ids;
+    m->stk_cap = cap;
+    return VC_OK;
+}
+
+/* Per-token log-probs of the NEXT vc_generate* call (one-shot): log p(generated token) [B, max_new] and, with top_k > 0, the top_k most
+ * likely tokens of every step [B, max_new, top_k], of the model's own next-token distribution.  token_logprobs == NULL cancels.  See
+ * include/vcoder_hip.h. */
+VC_API int vc_request_generate_logprobs(vc_model* m, int top_k, float* token_logprobs, float* top_logprobs, int32_t* top_ids,
+                                        size_t cap_rows) {
+    if (!m) return VC_ERR_INVALID;
+    if (!token_logprobs) {
+        clear_generate_logprobs_request(m);
+        return VC_OK;
+    }
+    if (top_k < 0 || top_k > VC_MAX_TOP_LOGPROBS || (top_k > 0 && (!top_logprobs || !top_ids)) || cap_rows < 1) {
+        m->ctx->err = "vc_request_generate_logprobs needs top_k in 0 .. 32, the top buffers iff top_k > 0, and cap_rows >= 1";
+        return VC_ERR_INVALID;   // (a pending request stays as it was: nothing touched)
+    }
+    m->glp_k = top_k;
+    m->glp_tok = token_logprobs;
+    m->glp_top = top_k ? top_logprobs : nullptr;
+    m->glp_ids = top_k ? top_ids : nullptr;
+    m->glp_cap = cap_rows;
+    return VC_OK;
+}
+
 /* KV-cache slots the next vc_prefill keeps free behind the prompt for vc_decode_step (default 64; clamped to
  * max_position_embeddings).  A decode loop that outruns the reserve still works — the cache grows, at the cost of a copy. */
 VC_API int vc_model_reserve_decode(vc_model* m, int max_new_tokens) {
@@ -789,6 +831,7 @@ void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* n
             m->hidden_out = nullptr;
             m->attn_out = nullptr;
             m->hidden_cap = m->attn_cap = 0;
+            clear_generate_logprobs_request(m);
         }
     } step_requests{m};
     if (m->precision == 1) {
@@ -796,8 +839,7 @@ void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* n
     } else if (m->hidden_out || m->attn_out) {
         enqueue_decode_step(m, session_view(m), B, m->cur_pos);
     } else {
-        ensure_graph(m, B);
-        HIPCHK(hipGraphLaunch(m->graph, m->st));
+        HIPCHK(hipGraphLaunch(ensure_graph(m, B), m->st));
     }
     m->cur_pos += 1;
     m->tok_stale = false;
@@ -828,6 +870,7 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
             m->attn_out = nullptr;
             m->hidden_cap = m->attn_cap = 0;
             clear_score_request(m);
+            clear_generate_logprobs_request(m);
         }
     } requests{m};
     GUARD_BEGIN
@@ -852,6 +895,8 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
                 B, n);
         REQUIRE(m->score_cap >= (size_t)B * n, VC_ERR_INVALID, "token-score buffers hold %zu elements, the call yields [%d, %d]",
                 m->score_cap, B, n);
+        REQUIRE(!m->stk_k || m->stk_cap >= (size_t)B * n * m->stk_k, VC_ERR_INVALID,
+                "top-logprob buffers hold %zu entries, the call yields [%d, %d, %d]", m->stk_cap, B, n, m->stk_k);
         for (size_t i = 0; i < (size_t)B * n; ++i)
             REQUIRE(labels[i] == IGNORE_INDEX || (labels[i] >= 0 && labels[i] < V), VC_ERR_INDEX, "Target %lld is out of bounds.",
                     (long long)labels[i]);
@@ -871,6 +916,7 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
                     if (labels[(size_t)b * n + t + 1] != IGNORE_INDEX) tgt[(size_t)t * B + b] = (int)labels[(size_t)b * n + t + 1];
             m->sc_idx.ensure(tgt.size() * 4);
             m->sc_lp.ensure(tgt.size() * 4);
+            ensure_score_top(m, tgt.size());
             HIPCHK(hipMemcpyAsync(m->sc_idx.p, tgt.data(), tgt.size() * 4, hipMemcpyHostToDevice, m->st));
         }
         for (int t = 0; t < n; ++t) {
@@ -886,9 +932,11 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
                 m->attn_cap = at.size();
             }
             decode_step_impl(m, col.data(), step_lg.data(), nullptr);
-            if (scored && t + 1 < n)
+            if (scored && t + 1 < n) {
                 launch_token_logprob(m->logits.as<float>(), V, m->sc_idx.as<int>() + (size_t)t * B, m->sc_lp.as<float>() + (size_t)t * B, B,
                                      V, m->st);
+                score_top_rows(m, m->logits.as<float>(), (size_t)t * B, B);
+            }
             if (logits_all)
                 for (int b = 0; b < B; ++b) memcpy(logits_all + ((size_t)b * n + t) * V, step_lg.data() + (size_t)b * V, (size_t)V * 4);
             if (hidden_req)
@@ -901,13 +949,19 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
         if (logits_last) memcpy(logits_last, step_lg.data(), step_lg.size() * 4);
         if (scored) {
             std::fill(m->score_out, m->score_out + (size_t)B * n, 0.f);
+            top_fill(m, (size_t)B * n);
             if (n > 1) {
                 std::vector<float> lp((size_t)(n - 1) * B);
+                TopHost top;
                 HIPCHK(hipMemcpyAsync(lp.data(), m->sc_lp.p, lp.size() * 4, hipMemcpyDeviceToHost, m->st));
+                top.fetch(m, lp.size());
                 HIPCHK(hipStreamSynchronize(m->st));
                 for (int t = 0; t + 1 < n; ++t)
                     for (int b = 0; b < B; ++b)
-                        if (labels[(size_t)b * n + t + 1] != IGNORE_INDEX) m->score_out[(size_t)b * n + t + 1] = lp[(size_t)t * B + b];
+                        if (labels[(size_t)b * n + t + 1] != IGNORE_INDEX) {
+                            m->score_out[(size_t)b * n + t + 1] = lp[(size_t)t * B + b];
+                            top.scatter(m, (size_t)t * B + b, (size_t)b * n + t + 1);
+                        }
             }
             if (m->score_labels_out) std::copy(labels, labels + (size_t)B * n, m->score_labels_out);
         }

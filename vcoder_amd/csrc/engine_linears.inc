@@ -122,6 +122,12 @@ struct LoopView {
     int* stamp_next;
     unsigned long long* prof_acc;
     unsigned* stamp_scratch;
+    // per-token log-probs of a generate() call (vc_request_generate_logprobs): slabs laid out like out_ids — the chosen token's
+    // log-prob [slots], the lp_k most likely tokens [slots, lp_k].  lp_tok == nullptr (every loop but a session's while such a call
+    // runs): the step has no log-prob launch.
+    float *lp_tok, *lp_top;
+    int* lp_ids;
+    int lp_k;
 };
 
 // the next timing slot of the step being enqueued (nullptr: profiling off)

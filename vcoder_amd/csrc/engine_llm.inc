@@ -127,6 +127,7 @@ void ensure_prefill_ws(vc_model* m, int B, int Scap) {
 
 void drop_graph(vc_model* m) {
     if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
+    if (m->graph_lp) { (void)hipGraphExecDestroy(m->graph_lp); m->graph_lp = nullptr; }
 }
 
 // the session's own decode loop: KV cache for B sequences of S_total positions + the per-step buffers
@@ -195,6 +196,12 @@ LoopView session_view(vc_model* m) {
     v.ssq = m->ssq.as<float>();
     v.sk_scratch = m->sk_scratch.as<float>();
     v.sk_counters = m->sk_counters.as<unsigned>();
+    if (m->lp_on) {
+        v.lp_tok = m->lp_tok.as<float>();
+        v.lp_top = m->lp_top.as<float>();
+        v.lp_ids = m->lp_ids.as<int>();
+        v.lp_k = m->lp_k;
+    }
     return v;
 }
 
@@ -486,6 +493,14 @@ SelectArgs select_args(vc_model* m, const LoopView& v, const float* logits, int 
     return a;
 }
 
+// log-prob of the token the selection just chose + the loop's lp_k most likely tokens, into the row's slot of the slabs: right behind
+// launch_select_embed, on the same logits (the raw distribution, whatever the sampler made of it).  Nothing without slabs.
+void enqueue_step_logprobs(vc_model* m, const LoopView& v, const float* logits, int nrows) {
+    if (!v.lp_tok) return;
+    TopkLogprobArgs a{logits, m->c.vocab, nullptr, v.lp_tok, v.lp_top, v.lp_ids, m->c.vocab, v.lp_k, v.rows, v.next_tok, 0};
+    launch_topk_logprob(a, nrows, -1, v.st);
+}
+
 // the fused decode attention of layer l of a step over the first `nrows` rows of a loop
 AttnDecodeFusedArgs decode_attn_args(const vc_model* m, const LoopView& v, int l, int nrows) {
     const KvTarget kv = loop_kv(v);
@@ -534,6 +549,7 @@ void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_
             if (hooks) emit_hidden(m, l + 1, nrows, 1, v.x_dec);
         });
     launch_select_embed(select_args(m, v, v.logits, nrows, 3), v.st);                                        // K19/K20+K10
+    enqueue_step_logprobs(m, v, v.logits, nrows);
     // in-situ timing: fold the step's slots (5 per layer: qkv, attention, o, gate/up, down; then lm_head) into the span's sums
     if (v.stamps && v.stamp_next && v.prof_acc)
         launch_stamp_accumulate(v.stamps, *v.stamp_next, m->c.layers, v.prof_acc, v.stamp_scratch, v.st);
@@ -546,6 +562,7 @@ void enqueue_decode_step_strict(vc_model* m, int B) {
     run_llm_layers_strict(m, m->x_dec.as<float>(), B, 1, v.rows + RS_POS, false);
     logits_strict(m, m->x_dec.as<float>(), nullptr, B);
     launch_select_embed(select_args(m, v, v.logits, B, 3), v.st);
+    enqueue_step_logprobs(m, v, v.logits, B);
 }
 
 // ---- logits of precision mode 0 from the residual rows x (B sequences of rows_per_seq rows) --------------------------------------
@@ -674,12 +691,25 @@ hipGraphExec_t capture_step(vc_model* m, const LoopView& v, int nrows) {
     return exec;
 }
 
-void ensure_graph(vc_model* m, int B) {
-    if (m->graph && m->graph_rows == B && m->graph_masked == m->kmask_in_decode) return;
-    drop_graph(m);
+// the session's captured step: the plain one, or — while a generate() call with log-probs runs (lp_on) — the one that carries the
+// log-prob launch for lp_k alternatives.  Both stay instantiated side by side: a vc_decode_step behind such a call replays the plain step.
+hipGraphExec_t ensure_graph(vc_model* m, int B) {
+    if (m->lp_on) {
+        if (m->graph_lp && m->graph_lp_rows == B && m->graph_lp_masked == m->kmask_in_decode && m->graph_lp_k == m->lp_k)
+            return m->graph_lp;
+        if (m->graph_lp) { (void)hipGraphExecDestroy(m->graph_lp); m->graph_lp = nullptr; }
+        m->graph_lp = capture_step(m, session_view(m), B);
+        m->graph_lp_rows = B;
+        m->graph_lp_masked = m->kmask_in_decode;
+        m->graph_lp_k = m->lp_k;
+        return m->graph_lp;
+    }
+    if (m->graph && m->graph_rows == B && m->graph_masked == m->kmask_in_decode) return m->graph;
+    if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
     m->graph = capture_step(m, session_view(m), B);
     m->graph_rows = B;
     m->graph_masked = m->kmask_in_decode;
+    return m->graph;
 }
 
 void ensure_out_ids(vc_model* m, int B, int max_new) {
@@ -689,6 +719,20 @@ void ensure_out_ids(vc_model* m, int B, int max_new) {
         m->out_ids.ensure((size_t)rup(B, 16) * m->out_stride * 4);
         drop_graph(m);  // pointer baked into the graph
     }
+}
+// the log-prob slabs of a generate() call, sized like out_ids (after ensure_out_ids): [rows, out_stride] (x K)
+void ensure_logprob_slabs(vc_model* m, int B, int K) {
+    const size_t slots = (size_t)rup(B, 16) * m->out_stride;
+    const void* before[] = {m->lp_tok.p, m->lp_top.p, m->lp_ids.p};
+    m->lp_tok.ensure(slots * 4);
+    m->lp_top.ensure(slots * std::max(K, 1) * 4);
+    m->lp_ids.ensure(slots * std::max(K, 1) * 4);
+    const void* after[] = {m->lp_tok.p, m->lp_top.p, m->lp_ids.p};
+    for (int i = 0; i < 3; ++i)
+        if (before[i] != after[i] && m->graph_lp) {   // pointers baked into the step that carries the launch
+            (void)hipGraphExecDestroy(m->graph_lp);
+            m->graph_lp = nullptr;
+        }
 }
 
 // ---- host-side RowState records ---------------------------------------------------------------------------------
@@ -839,6 +883,8 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
             }
         REQUIRE(m->score_cap >= (size_t)B * S, VC_ERR_INVALID,
                 "token-score buffers hold %zu elements, the call yields [%d, %zu]", m->score_cap, B, S);
+        REQUIRE(!m->stk_k || m->stk_cap >= (size_t)B * S * m->stk_k, VC_ERR_INVALID,
+                "top-logprob buffers hold %zu entries, the call yields [%d, %zu, %d]", m->stk_cap, B, S, m->stk_k);
         if (own_kv) m->cur_pos = -1;
     }
     if (m->plan_only) {
@@ -920,6 +966,43 @@ constexpr int SCORE_CHUNK_ROWS = 1024;
 // 32 rows 75 | 106, 64 rows 122 | 106, 128 rows 212 | 108).  The results land in m->sc_lp [row_idx.size()] on the device, in order;
 // nothing is synchronised.
 constexpr int SCORE_GEMV_ROWS = VC_GEMV_MAX_M;
+// vc_request_top_logprobs: the stk_k most likely tokens of `nr` logits rows into rows [r0, r0 + nr) of m->sc_tlp / m->sc_tid (sized by
+// ensure_score_top); nothing without the request
+void ensure_score_top(vc_model* m, size_t rows) {
+    if (!m->stk_k) return;
+    m->sc_tlp.ensure(rows * m->stk_k * 4);
+    m->sc_tid.ensure(rows * m->stk_k * 4);
+}
+void score_top_rows(vc_model* m, const float* logits, size_t r0, int nr) {
+    if (!m->stk_k) return;
+    const int K = m->stk_k, V = m->c.vocab;
+    TopkLogprobArgs a{logits, V, nullptr, nullptr, m->sc_tlp.as<float>() + r0 * K, m->sc_tid.as<int>() + r0 * K, V, K, nullptr, nullptr, 0};
+    launch_topk_logprob(a, nr, -1, m->st);
+}
+// the caller's top buffers: 0.0 / -1 over `positions` positions; then (top_scatter) device row i -> position pos of the call's layout
+void top_fill(vc_model* m, size_t positions) {
+    if (!m->stk_k) return;
+    std::fill(m->stk_lp, m->stk_lp + positions * m->stk_k, 0.f);
+    std::fill(m->stk_ids, m->stk_ids + positions * m->stk_k, -1);
+}
+struct TopHost {   // the device rows of a call on the host (one copy; the caller synchronises the stream before reading)
+    std::vector<float> lp;
+    std::vector<int32_t> id;
+    int K = 0;
+    void fetch(vc_model* m, size_t rows) {
+        K = m->stk_k;
+        if (!K || !rows) return;
+        lp.resize(rows * K);
+        id.resize(rows * K);
+        HIPCHK(hipMemcpyAsync(lp.data(), m->sc_tlp.p, lp.size() * 4, hipMemcpyDeviceToHost, m->st));
+        HIPCHK(hipMemcpyAsync(id.data(), m->sc_tid.p, id.size() * 4, hipMemcpyDeviceToHost, m->st));
+    }
+    void scatter(vc_model* m, size_t row, size_t pos) const {
+        if (!K) return;
+        std::copy(lp.begin() + row * K, lp.begin() + (row + 1) * K, m->stk_lp + pos * K);
+        std::copy(id.begin() + row * K, id.begin() + (row + 1) * K, m->stk_ids + pos * K);
+    }
+};
 void score_rows(vc_model* m, const float* x, const std::vector<int>& row_idx, const std::vector<int>& tgt) {
     const vc_model_cfg& c = m->c;
     const int D = c.hidden, V = c.vocab, n = (int)row_idx.size();
@@ -928,6 +1011,7 @@ void score_rows(vc_model* m, const float* x, const std::vector<int>& row_idx, co
     const int ldx = split_ld(D);
     m->sc_idx.ensure((size_t)2 * n * 4);
     m->sc_lp.ensure((size_t)n * 4);
+    ensure_score_top(m, (size_t)n);
     m->sc_xn.ensure((size_t)chunk_cap * std::max((size_t)D * 4, (size_t)ldx * 2), true);
     m->sc_logits.ensure((size_t)chunk_cap * V * 4, true);
     int* idx_dev = m->sc_idx.as<int>();
@@ -954,6 +1038,7 @@ void score_rows(vc_model* m, const float* x, const std::vector<int>& row_idx, co
             }
         }
         launch_token_logprob(lg, V, tgt_dev + r0, m->sc_lp.as<float>() + r0, nr, V, m->st);
+        score_top_rows(m, lg, r0, nr);
     }
 }
 // the labelled positions of `labels` [B, n] (n rows per sequence in x): row b n + j - 1 scores label j >= 1.  The caller's buffer
@@ -969,12 +1054,18 @@ void score_labelled_rows(vc_model* m, const float* x, const int64_t* labels, int
             tgt.push_back((int)l);
         }
     std::fill(out, out + (size_t)B * n, 0.f);
+    top_fill(m, (size_t)B * n);
     if (row_idx.empty()) return;
     score_rows(m, x, row_idx, tgt);
     std::vector<float> lp(row_idx.size());
+    TopHost top;
     HIPCHK(hipMemcpyAsync(lp.data(), m->sc_lp.p, lp.size() * 4, hipMemcpyDeviceToHost, m->st));
+    top.fetch(m, row_idx.size());
     HIPCHK(hipStreamSynchronize(m->st));
-    for (size_t i = 0; i < lp.size(); ++i) out[row_idx[i] + 1] = lp[i];
+    for (size_t i = 0; i < lp.size(); ++i) {
+        out[row_idx[i] + 1] = lp[i];
+        top.scatter(m, i, (size_t)row_idx[i] + 1);
+    }
 }
 // logits rows [B * n, V] already on the device (a continuation whose lm_head ran over every row): every row is scored in place —
 // row b n + j - 1 against label j, unlabelled rows against token 0 and dropped on the host
@@ -990,17 +1081,25 @@ void score_logits_rows(vc_model* m, const float* logits, const int64_t* labels, 
             any = true;
         }
     std::fill(out, out + (size_t)M, 0.f);
+    top_fill(m, (size_t)M);
     if (!any) return;
     m->sc_idx.ensure((size_t)M * 4);
     m->sc_lp.ensure((size_t)M * 4);
+    ensure_score_top(m, (size_t)M);
     HIPCHK(hipMemcpyAsync(m->sc_idx.p, tgt.data(), (size_t)M * 4, hipMemcpyHostToDevice, m->st));
     launch_token_logprob(logits, m->c.vocab, m->sc_idx.as<int>(), m->sc_lp.as<float>(), M, m->c.vocab, m->st);
+    score_top_rows(m, logits, 0, M);
     std::vector<float> lp(M);
+    TopHost top;
     HIPCHK(hipMemcpyAsync(lp.data(), m->sc_lp.p, (size_t)M * 4, hipMemcpyDeviceToHost, m->st));
+    top.fetch(m, (size_t)M);
     HIPCHK(hipStreamSynchronize(m->st));
     for (int b = 0; b < B; ++b)
         for (int j = 1; j < n; ++j)
-            if (labels[(size_t)b * n + j] != IGNORE_INDEX) out[b * n + j] = lp[b * n + j - 1];
+            if (labels[(size_t)b * n + j] != IGNORE_INDEX) {
+                out[b * n + j] = lp[b * n + j - 1];
+                top.scatter(m, (size_t)b * n + j - 1, (size_t)b * n + j);
+            }
 }
 
 // decoder stack over the spliced batch + last-row logits (m->logits [B,V]); keys / values go to `kv`

@@ -22,17 +22,21 @@ int row_stop_end(const GenParams& g, const int32_t* row, const int* tail_b, int 
 }
 
 // columns HF's loop would have returned: it stops right after the first step at which every row has produced EOS / met a stop
+// columns of one row up to and including its finishing token (its EOS, or the token that completes a stop sequence); `produced`
+// when the row never finished
+int row_finish_end(const GenParams& g, const int32_t* row, const int* tail_b, int produced) {
+    int e = produced;
+    if (g.eos >= 0)
+        for (int s_ = 0; s_ < produced; ++s_)
+            if (row[s_] == g.eos) { e = s_ + 1; break; }
+    if (g.n_stop > 0) e = std::min(e, row_stop_end(g, row, tail_b, produced));
+    return e;
+}
 int trim_columns(const GenParams& g, const int32_t* out_ids, int ld, const int* tail, int B, int produced) {
     if (!(g.eos >= 0 || g.n_stop > 0)) return produced;
     int last = 0;
-    for (int b = 0; b < B; ++b) {
-        int e = produced;
-        if (g.eos >= 0)
-            for (int s_ = 0; s_ < produced; ++s_)
-                if (out_ids[(size_t)b * ld + s_] == g.eos) { e = s_ + 1; break; }
-        if (g.n_stop > 0) e = std::min(e, row_stop_end(g, out_ids + (size_t)b * ld, tail + (size_t)b * (VC_MAX_STOP_LEN - 1), produced));
-        last = std::max(last, e);
-    }
+    for (int b = 0; b < B; ++b)
+        last = std::max(last, row_finish_end(g, out_ids + (size_t)b * ld, tail + (size_t)b * (VC_MAX_STOP_LEN - 1), produced));
     return std::min(produced, last);
 }
 
@@ -586,6 +590,21 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     ensure_out_ids(m, B, max_new);
     finish_prefill(m, session_kv(m), nullptr);
     m->kmask_in_decode = false;   // generate(): the cached steps run under an all-ones mask (vcoder_ds_llava_arch.py:130-133)
+    // vc_request_generate_logprobs: every selection of this call is followed by the log-prob launch (session_view: lp_on)
+    const bool want_lp = m->glp_tok != nullptr;
+    struct LpScope {
+        vc_model* m;
+        ~LpScope() { m->lp_on = false; }
+    } lp_scope{m};
+    if (want_lp) {
+        m->lp_k = m->glp_k;
+        ensure_logprob_slabs(m, B, m->lp_k);
+        m->lp_on = true;
+        // positions nothing writes (behind max_new, or never reached) read 0.0 / 0.0 / -1
+        HIPCHK(hipMemsetAsync(m->lp_tok.p, 0, m->lp_tok.cap, m->st));
+        HIPCHK(hipMemsetAsync(m->lp_top.p, 0, m->lp_top.cap, m->st));
+        HIPCHK(hipMemsetAsync(m->lp_ids.p, 0xFF, m->lp_ids.cap, m->st));
+    }
     if (m->ev[2]) HIPCHK(hipEventRecord(m->ev[2], m->st));
     arm_session_rows(m, g, tail.data());
     const LoopView v = session_view(m);
@@ -593,6 +612,7 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     std::vector<int> fill((size_t)B * m->out_stride, g.pad);
     HIPCHK(hipMemcpyAsync(m->out_ids.p, fill.data(), fill.size() * 4, hipMemcpyHostToDevice, m->st));
     launch_select_embed(select_args(m, v, v.logits, B, 1), m->st);  // step 0 -> 1; the position stays at S
+    enqueue_step_logprobs(m, v, v.logits, B);
     HIPCHK(hipStreamSynchronize(m->st));
     gate.unlock();
     int produced = 1, reported = 0;
@@ -618,10 +638,10 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     const int every = cb ? std::max(cb_every, 1) : 8;
     if (cb && every == 1) report(1);
     if (max_new > 1 && !all_finished()) {
-        if (m->precision != 1) ensure_graph(m, B);
+        const hipGraphExec_t step_graph = m->precision != 1 ? ensure_graph(m, B) : nullptr;
         for (int step = 1; step < max_new; ++step) {
             if (m->precision == 1) enqueue_decode_step_strict(m, B);
-            else HIPCHK(hipGraphLaunch(m->graph, m->st));
+            else HIPCHK(hipGraphLaunch(step_graph, m->st));
             m->cur_pos += 1;
             produced = step + 1;
             // the reference checks its stopping criteria on the host every token; checking every few tokens only
@@ -638,7 +658,34 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     if (m->ev[3]) HIPCHK(hipEventRecord(m->ev[3], m->st));
     HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, m->out_ids.p, (size_t)m->out_stride * 4, (size_t)max_new * 4, B,
                             hipMemcpyDeviceToHost, m->st));
+    if (want_lp) {   // the slabs come back once, beside out_ids
+        const int K = m->lp_k;
+        HIPCHK(hipMemcpy2DAsync(m->glp_tok, (size_t)max_new * 4, m->lp_tok.p, (size_t)m->out_stride * 4, (size_t)max_new * 4, B,
+                                hipMemcpyDeviceToHost, m->st));
+        if (K > 0) {
+            HIPCHK(hipMemcpy2DAsync(m->glp_top, (size_t)max_new * K * 4, m->lp_top.p, (size_t)m->out_stride * K * 4,
+                                    (size_t)max_new * K * 4, B, hipMemcpyDeviceToHost, m->st));
+            HIPCHK(hipMemcpy2DAsync(m->glp_ids, (size_t)max_new * K * 4, m->lp_ids.p, (size_t)m->out_stride * K * 4,
+                                    (size_t)max_new * K * 4, B, hipMemcpyDeviceToHost, m->st));
+        }
+    }
     HIPCHK(hipStreamSynchronize(m->st));
+    if (want_lp) {
+        // a row's finishing token (its EOS, or the token completing a stop sequence) is scored; behind it the row emitted pad: those
+        // positions, and the columns the loop never reached, hold 0.0 / 0.0 / -1
+        const int K = m->lp_k;
+        for (int b = 0; b < B; ++b) {
+            const int e = row_finish_end(g, out_ids + (size_t)b * max_new, tail.data() + (size_t)b * (VC_MAX_STOP_LEN - 1), produced);
+            for (int s_ = e; s_ < max_new; ++s_) {
+                const size_t i = (size_t)b * max_new + s_;
+                m->glp_tok[i] = 0.f;
+                for (int k = 0; k < K; ++k) {
+                    m->glp_top[i * K + k] = 0.f;
+                    m->glp_ids[i * K + k] = -1;
+                }
+            }
+        }
+    }
     produced = trim_columns(g, out_ids, max_new, tail.data(), B, produced);
     if (cb) report(produced);
     if (n_generated) *n_generated = produced;
@@ -696,7 +743,10 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
     // concurrent generate() calls share their decode steps in the root model's pool (VC_POOL=0: every call on its own
     // loop); strict mode keeps fp32 caches of its own
     static const bool use_pool = !(getenv("VC_POOL") && atoi(getenv("VC_POOL")) == 0);
-    if (use_pool && m->precision != 1)
+    // vc_request_generate_logprobs: the call runs on the session's own loop, whose steps carry the log-prob launch
+    REQUIRE(!m->glp_tok || m->glp_cap >= (size_t)B * max_new, VC_ERR_INVALID,
+            "log-prob buffers hold %zu rows, the call yields [%d, %d]", m->glp_cap, B, max_new);
+    if (use_pool && m->precision != 1 && !m->glp_tok)
         generate_on_pool(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids, n_generated);
     else
         generate_on_session(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids,

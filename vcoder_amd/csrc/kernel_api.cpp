@@ -90,6 +90,12 @@ VCK_EXPORT void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, in
 VCK_EXPORT void vck_token_logprob(const float* logits, int ldl, const int* target, float* logprob, int rows, int V, void* stream) {
     launch_token_logprob(logits, ldl, target, logprob, rows, V, S(stream));
 }
+VCK_EXPORT void vck_topk_logprob(const float* logits, int ldl, const int* chosen, float* chosen_lp, float* top_lp, int* top_ids,
+                                 int rows, int V, int K, int lds_floats, void* stream) {
+    if (K < 0 || K > VC_MAX_TOP_LOGPROBS) return;   // nothing is launched, nothing written
+    TopkLogprobArgs a{logits, ldl, chosen, chosen_lp, top_lp, top_ids, V, K, nullptr, nullptr, 0};
+    launch_topk_logprob(a, rows, lds_floats, S(stream));
+}
 VCK_EXPORT void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w,
                                      uint16_t* xg, int B, int D, int npart, void* stream) {
     launch_embed_tokens_ssq(tok, embed, x, ssq, xg_w, xg, B, D, npart, S(stream));

@@ -409,6 +409,25 @@ void launch_advance(int* step_dev, int* pos_dev, int* ctx_dev, hipStream_t s);
 // scoring: logprob[r] = logits[r, target[r]] - logsumexp(logits[r, 0:V]) for `rows` rows of stride ldl floats (ldl >= V; any V, any
 // alignment), one workgroup per row, fp32 throughout (select.hip)
 void launch_token_logprob(const float* logits, int ldl, const int* target, float* logprob, int rows, int V, hipStream_t s);
+// log-prob of a chosen token + the K most likely tokens of every logits row (select.hip topk_logprob_kernel): one workgroup per row;
+// top entries ordered by (value descending, id ascending), slots beyond the row's finite entries -1 / -inf.  Output slot of
+// workgroup r: r, or — rows != nullptr, the decode loop right behind launch_select_embed — rows[r][RS_OUT_OFF] + RS_STEP - 1 with
+// the token next_tok[r] (inactive rows and steps >= RS_MAXNEW write nothing).
+constexpr int VC_MAX_TOP_LOGPROBS = 32;
+struct TopkLogprobArgs {
+    const float* logits;   // [nrows, ldl] fp32
+    int ldl;
+    const int* chosen;     // [nrows] or nullptr (rows == nullptr only); < 0: chosen_lp 0.0
+    float* chosen_lp;      // [slots] or nullptr
+    float* top_lp;         // [slots, K] (K > 0)
+    int* top_ids;          // [slots, K]
+    int V, K;              // K in 0 .. VC_MAX_TOP_LOGPROBS
+    const int* rows;       // [nrows][RS_STRIDE] or nullptr
+    const int* next_tok;   // [nrows] (rows != nullptr)
+    int lds_floats;        // filled by the launcher: floats of LDS staging available
+};
+// lds_floats < 0: stage the row in LDS when the device allows; 0 (or < V): every pass re-reads the row from global memory
+void launch_topk_logprob(const TopkLogprobArgs& a, int nrows, int lds_floats, hipStream_t s);
 // test hook: u[i] = the sampler's uniform for hash value h[i], gumbel[i] = -log(-log(u[i]))
 void launch_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, hipStream_t s);
 

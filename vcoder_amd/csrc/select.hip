@@ -463,6 +463,192 @@ void launch_token_logprob(const float* logits, int ldl, const int* target, float
     VC_LAUNCH(token_logprob_kernel, dim3((unsigned)rows), dim3(LOGPROB_THREADS), 0, s, logits, ldl, target, logprob, V);
 }
 
+// ---- log-probability of the chosen token and the K most likely tokens of a logits row (generate(logprobs), score(top_logprobs)) ----
+//   chosen_lp[s]     = logits[r, chosen] - logsumexp(logits[r, 0:V])      (-inf logit: -inf; chosen < 0: 0.0)
+//   top_ids[s, 0:K]  = the K largest logits of the row ordered by (value descending, id ascending) — ties break as the greedy
+//   top_lp[s, 0:K]     argmax breaks them — each with logit - logsumexp; slots beyond the row's finite entries hold -1 / -inf
+// the model's own next-token distribution (log_softmax of the fp32 logits), whatever the sampler does with it afterwards.
+// One workgroup of 1024 threads per row, as select_embed_kernel, and the same exact selection: the row is staged in LDS in the pass that
+// accumulates the (max, sum) pairs of token_logprob_kernel (lse_add / lse_merge, fixed merge order), the K-th largest value is found
+// by bisection over the order-preserving key (32 counting passes over LDS), elements strictly above it are taken, ties at it by
+// ascending id until K is reached, and one wave orders the <= 32 survivors.  No per-thread candidate lists (32 (value, id) pairs
+// per thread would spill).  The survivors are gathered without atomics: every wave owns a contiguous range of ids, counts its
+// entries above / at the threshold, and a second walk places them behind the counts of the waves in front of it.
+// A row that does not fit the LDS staging (lds_floats < V) is re-read from global memory in every pass.
+// The log-prob of an id is ONE expression, lp_value(): chosen_lp is bit-equal to the top_lp entry of the same id.
+// -0.0 and +0.0 are one value to the tie rule (as to the argmax's float compare): the key maps both to +0.0's.
+// rows != nullptr (the decode loop): workgroup r reads its slot from the row's record as the select kernel that just ran left it —
+// step = RS_STEP - 1, token next_tok[r], slot RS_OUT_OFF + step; inactive rows and steps >= RS_MAXNEW write nothing.
+VC_DEV uint32_t topk_key(float f) {
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+constexpr uint32_t TOPK_KEY_NINF = 0x007FFFFFu;   // topk_key(-inf): every finite value lies above it
+VC_DEV float lp_value(float v, float mx, float lsum) { return v > -INFINITY ? (v - mx) - lsum : -INFINITY; }
+// lanes below this one whose pred holds, and (in every lane) the wave's total
+VC_DEV int wave_rank(bool pred, int lane, int& total) {
+#ifdef VC_EMU
+    int x = pred ? 1 : 0;
+    const int own = x;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = shfl(x, lane - d);
+        if (lane >= d) x += o;
+    }
+    total = shfl(x, 63);
+    return x - own;
+#else
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(pred);
+    total = __builtin_popcountll(b);
+    return __builtin_popcountll(b & ((1ull << lane) - 1ull));
+#endif
+}
+constexpr int TOPK_THREADS = 1024, TOPK_WAVES = TOPK_THREADS / 64;
+__global__ __launch_bounds__(TOPK_THREADS) void topk_logprob_kernel(TopkLogprobArgs p) {
+    VC_DYNAMIC_SMEM(float, zs);  // [V] the row (staged path)
+    __shared__ BlockRed red;
+    __shared__ float red_m[TOPK_WAVES], red_s[TOPK_WAVES];
+    __shared__ int wave_gt[TOPK_WAVES], wave_eq[TOPK_WAVES];
+    __shared__ float cand_v[VC_MAX_TOP_LOGPROBS];
+    __shared__ int cand_i[VC_MAX_TOP_LOGPROBS];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int V = p.V, K = p.K;
+    size_t slot = (size_t)r;
+    int chosen = p.chosen ? p.chosen[r] : -1;
+    if (p.rows != nullptr) {
+        const int* rs = p.rows + (size_t)r * RS_STRIDE;
+        if (!rs[RS_ACTIVE]) return;
+        const int step = rs[RS_STEP] - 1;
+        if (step < 0 || step >= rs[RS_MAXNEW]) return;
+        slot = (size_t)rs[RS_OUT_OFF] + (size_t)step;
+        chosen = p.next_tok[r];
+    }
+    const float* lg = p.logits + (size_t)r * p.ldl;
+    const bool staged = K > 0 && p.lds_floats >= V;
+    // ---- pass 1: (max, sum) pairs, the count of entries above -inf, the row into LDS --------------------------------------------
+    // columns [0, head) and [body_end, V) go one float at a time, [head, body_end) in aligned float4s
+    const int mis = (int)((reinterpret_cast<uintptr_t>(lg) >> 2) & 3);
+    const int head = min(V, (4 - mis) & 3);
+    const int body_end = head + ((V - head) & ~3);
+    float mx = -INFINITY, sm = 0.f;
+    int nfin = 0;
+    auto take = [&](int i, float v) {
+        lse_add(mx, sm, v);
+        nfin += topk_key(v) > TOPK_KEY_NINF;
+        if (staged) zs[i] = v;
+    };
+    if (tid < head) take(tid, lg[tid]);
+    for (int i = head + tid * 4; i < body_end; i += TOPK_THREADS * 4) {
+        const f32x4 v = ld16f(lg + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) take(i + e, v[e]);
+    }
+    if (body_end + tid < V) take(body_end + tid, lg[body_end + tid]);
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        const float om = shfl_xor(mx, k), os = shfl_xor(sm, k);
+        lse_merge(mx, sm, om, os);
+    }
+    if (lane == 0) { red_m[wave] = mx; red_s[wave] = sm; }
+    __syncthreads();   // (also: the staged row is complete)
+    mx = red_m[0];
+    sm = red_s[0];
+#pragma unroll
+    for (int w = 1; w < TOPK_WAVES; ++w) lse_merge(mx, sm, red_m[w], red_s[w]);   // fixed order, the same in every thread
+    const float lsum = logf(sm);
+    if (tid == 0 && p.chosen_lp != nullptr)
+        p.chosen_lp[slot] = (unsigned)chosen < (unsigned)V ? lp_value(lg[chosen], mx, lsum) : 0.0f;
+    if (K <= 0) return;
+    float* out_lp = p.top_lp + slot * (size_t)K;
+    int* out_id = p.top_ids + slot * (size_t)K;
+    const int keff = min(K, block_sum_i(nfin, red, lane, wave));
+    if (keff == 0) {
+        if (tid < K) { out_lp[tid] = -INFINITY; out_id[tid] = -1; }
+        return;
+    }
+    auto z = [&](int i) { return staged ? zs[i] : lg[i]; };
+    // ---- the keff-th largest key: the largest t with count(key >= t) >= keff (above TOPK_KEY_NINF, as keff entries are) ---------
+    uint32_t t = 0;
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t cand = t | (1u << bit);
+        int c = 0;
+        for (int i = tid; i < V; i += TOPK_THREADS) c += topk_key(z(i)) >= cand;
+        if (block_sum_i(c, red, lane, wave) >= keff) t = cand;
+    }
+    // ---- gather: wave w owns ids [w * seg, (w + 1) * seg) ------------------------------------------------------------------------
+    const int seg = (((V + TOPK_WAVES - 1) / TOPK_WAVES) + 63) & ~63;
+    const int i0 = wave * seg, i1 = min(V, i0 + seg);
+    int cg = 0, ce = 0;
+    for (int i = i0 + lane; i < i1; i += 64) {
+        const uint32_t k = topk_key(z(i));
+        cg += k > t;
+        ce += k == t;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        cg += shfl_xor(cg, m);
+        ce += shfl_xor(ce, m);
+    }
+    if (lane == 0) { wave_gt[wave] = cg; wave_eq[wave] = ce; }
+    __syncthreads();
+    int goff = 0, eoff = 0, total_gt = 0;
+    for (int w = 0; w < TOPK_WAVES; ++w) {
+        if (w < wave) { goff += wave_gt[w]; eoff += wave_eq[w]; }
+        total_gt += wave_gt[w];
+    }
+    const int need = keff - total_gt;   // ties taken at the threshold, by ascending id (>= 1: count(key > t) < keff)
+    for (int b = i0; b < i1; b += 64) {   // (wave-uniform trip count: every lane takes part in the ranks)
+        const int i = b + lane;
+        const bool in = i < i1;
+        const float v = in ? z(i) : 0.f;
+        const uint32_t k = in ? topk_key(v) : 0u;
+        int ng, ne;
+        const int rg = goff + wave_rank(in && k > t, lane, ng);
+        const int re = eoff + wave_rank(in && k == t, lane, ne);
+        int s_ = -1;
+        if (in && k > t) s_ = rg;
+        else if (in && k == t && re < need) s_ = total_gt + re;
+        if (s_ >= 0 && s_ < VC_MAX_TOP_LOGPROBS) { cand_v[s_] = v; cand_i[s_] = i; }
+        goff += ng;
+        eoff += ne;
+    }
+    __syncthreads();
+    // ---- one wave orders the keff survivors: rank = survivors in front by (value descending, id ascending) -----------------------
+    if (wave != 0 || lane >= K) return;
+    if (lane >= keff) {
+        out_lp[lane] = -INFINITY;
+        out_id[lane] = -1;
+        return;
+    }
+    const float v = cand_v[lane];
+    const int id = cand_i[lane];
+    int rank = 0;
+    for (int o = 0; o < keff; ++o) {
+        const float ov = cand_v[o];
+        const int oi = cand_i[o];
+        rank += ov > v || (ov == v && oi < id);
+    }
+    out_lp[rank] = lp_value(v, mx, lsum);
+    out_id[rank] = id;
+}
+void launch_topk_logprob(const TopkLogprobArgs& a0, int nrows, int lds_floats, hipStream_t s) {
+    if (nrows <= 0) return;
+    TopkLogprobArgs a = a0;
+    // the row is staged in LDS when it fits (the selection reads it ~35 times); lds_floats < 0: what the device allows
+    size_t lds = (size_t)a.V * 4;
+    if (lds > 150 * 1024 || a.K <= 0 || (lds_floats >= 0 && lds_floats < a.V)) lds = 0;
+    a.lds_floats = (int)(lds / 4);
+#ifndef VC_EMU
+    static size_t allowed = 0;
+    if (lds > 48 * 1024 && lds > allowed) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(topk_logprob_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        allowed = lds;
+    }
+#endif
+    VC_LAUNCH(topk_logprob_kernel, dim3((unsigned)nrows), dim3(TOPK_THREADS), lds, s, a);
+}
+
 // embedding + sum-of-squares partials for tokens supplied by the host (vc_decode_step with explicit tokens)
 __global__ __launch_bounds__(256) void embed_tokens_ssq_kernel(const int* tok, const bf16_t* embed, float* x, float* ssq,
                                                                const float* xg_w, bf16_t* xg, int B, int D, int npart, int G,

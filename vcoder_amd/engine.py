@@ -337,8 +337,9 @@ class HipEngine:
 
     def prefill(self, input_ids, images, segs=None, depths=None, has_attention_mask: bool = False,
                 all_logits: bool = False, reserve: Optional[int] = None, attention_mask=None, hidden_states: bool = False,
-                attentions: bool = False, labels=None):
-        """-> (logits_last [B,V], logits_all [B,S,V] or None, S).  labels [B,T] (aligned with input_ids, -100 = not scored):
+                attentions: bool = False, labels=None, top_logprobs: int = 0):
+        """-> (logits_last [B,V], logits_all [B,S,V] or None, S).  top_logprobs = K (with labels): last_top_logprobs / last_top_ids
+        [B,S,K] receive the K most likely tokens of the row in front of every scored position (0.0 / -1 elsewhere).  labels [B,T] (aligned with input_ids, -100 = not scored):
         last_token_logprobs [B,S] receives log p(label) of every labelled position of the spliced sequence (0 elsewhere; HF's
         shift: the row in front of a position scores it) and last_spliced_labels [B,S] the labels as the splice laid them out —
         the lm_head runs over the scored rows only and no logits leave the device for it.  reserve: decode_step calls the caller intends to make
@@ -365,10 +366,13 @@ class HipEngine:
         worst = T + rows * self._max_feature_blocks(ids)
         full = np.empty((B * worst * V,), dtype=np.float32) if all_logits else None
         lab = self._labels(labels, B, T)
-        lp = sl = None
+        K = self._top_k(top_logprobs, lab)
+        lp = sl = tlp = tid = None
+        self.last_top_logprobs = self.last_top_ids = None
         try:
             if lab is not None:
                 lp, sl = self._request_scores(lab, B * worst)
+                tlp, tid = self._request_top(K, B * worst)
             if attentions:      # [L, B, H, S, S]
                 att = np.empty((self.cfg.num_hidden_layers, B, self.cfg.num_attention_heads, S_att, S_att), dtype=np.float32)
                 self._check(self.lib.vc_request_attentions(self._model, att.ctypes.data_as(C.c_void_p), C.c_size_t(att.size)))
@@ -392,12 +396,37 @@ class HipEngine:
         if lab is not None:
             self.last_token_logprobs = lp[: B * S.value].reshape(B, S.value).copy()
             self.last_spliced_labels = sl[: B * S.value].reshape(B, S.value).copy()
+            if K:
+                self.last_top_logprobs = tlp[: B * S.value * K].reshape(B, S.value, K).copy()
+                self.last_top_ids = tid[: B * S.value * K].reshape(B, S.value, K).copy()
         self.last_attentions = att
         return last, (full[: B * S.value * V].reshape(B, S.value, V).copy() if all_logits else None), S.value
 
     last_attentions = None
     last_token_logprobs = None    # [B, S] / [B, n] float32 of the last prefill / extend with labels
     last_spliced_labels = None    # int64, same shape
+    last_top_logprobs = None      # [B, S, K] / [B, n, K] float32 of the last prefill / extend with labels and top_logprobs=K
+    last_top_ids = None           # int32, same shape (-1 where nothing is scored)
+    last_generate_logprobs = None  # (token_logprobs [B, n], top_logprobs [B, n, K], top_ids [B, n, K]) of the last generate(logprobs=True)
+    MAX_TOP_LOGPROBS = 32
+
+    def _top_k(self, top_logprobs, lab=True) -> int:
+        K = int(top_logprobs or 0)
+        if K < 0 or K > self.MAX_TOP_LOGPROBS:
+            raise ValueError(f"top_logprobs must be in 0 .. {self.MAX_TOP_LOGPROBS}, got {K}")
+        if K and lab is None:
+            raise ValueError("top_logprobs needs labels (the positions that are scored)")
+        return K
+
+    def _request_top(self, K: int, positions: int):
+        """announces top-K alternatives beside the pending score request; -> the host buffers that call fills"""
+        if not K:
+            return None, None
+        tlp = np.zeros((positions * K,), dtype=np.float32)
+        tid = np.full((positions * K,), -1, dtype=np.int32)
+        self._check(self.lib.vc_request_top_logprobs(self._model, K, tlp.ctypes.data_as(C.c_void_p), tid.ctypes.data_as(C.c_void_p),
+                                                     C.c_size_t(tlp.size)))
+        return tlp, tid
 
     @staticmethod
     def _labels(labels, B: int, n: int):
@@ -482,8 +511,10 @@ class HipEngine:
         self.last_hidden_states, self.last_attentions = hid, att
         return lg, nxt
 
-    def extend(self, tokens, all_logits: bool = True, hidden_states: bool = False, attentions: bool = False, labels=None):
-        """Multi-token continuation of the current loop: tokens [B, n] at positions P .. P+n-1 (P = the position the next
+    def extend(self, tokens, all_logits: bool = True, hidden_states: bool = False, attentions: bool = False, labels=None,
+               top_logprobs: int = 0):
+        """top_logprobs = K (with labels): last_top_logprobs / last_top_ids [B, n, K], as prefill().
+        Multi-token continuation of the current loop: tokens [B, n] at positions P .. P+n-1 (P = the position the next
         decode_step would take), causal inside the chunk over every cached key.  -> (logits_last [B, V], logits_all [B, n, V] or
         None).  hidden_states / attentions: [(L + 1), B, n, D] / [L, B, H, n, P + n] in last_hidden_states / last_attentions.
         decode_step continues at P + n.  labels [B, n] (aligned with tokens): last_token_logprobs [B, n] = log p(label) of the
@@ -499,10 +530,13 @@ class HipEngine:
         full = np.empty((B, n, V), dtype=np.float32) if all_logits else None
         hid = att = None
         lab = self._labels(labels, B, n)
-        lp = sl = None
+        K = self._top_k(top_logprobs, lab)
+        lp = sl = tlp = tid = None
+        self.last_top_logprobs = self.last_top_ids = None
         try:
             if lab is not None:
                 lp, sl = self._request_scores(lab, B * n)
+                tlp, tid = self._request_top(K, B * n)
             if hidden_states:
                 hid = np.empty((self.cfg.num_hidden_layers + 1, B, n, self.cfg.hidden_size), dtype=np.float32)
                 self._check(self.lib.vc_request_hidden_states(self._model, hid.ctypes.data_as(C.c_void_p), C.c_size_t(hid.size)))
@@ -520,6 +554,8 @@ class HipEngine:
         self.last_hidden_states, self.last_attentions = hid, att
         if lab is not None:
             self.last_token_logprobs, self.last_spliced_labels = lp.reshape(B, n), sl.reshape(B, n)
+            if K:
+                self.last_top_logprobs, self.last_top_ids = tlp.reshape(B, n, K), tid.reshape(B, n, K)
         return last, full
 
     _step_pos = 0   # position of the token the next decode_step processes (prefill: S)
@@ -539,12 +575,21 @@ class HipEngine:
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
                  stop_sequences: Optional[Sequence[Sequence[int]]] = None, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                 on_tokens=None, stream_every: int = 1, attention_mask=None) -> np.ndarray:
+                 on_tokens=None, stream_every: int = 1, attention_mask=None, logprobs: bool = False,
+                 top_logprobs: int = 0) -> np.ndarray:
         """generate() on the device (vc_generate): greedy, or temperature / top-k / top-p sampling with a counter-based
         generator (same seed -> same tokens).  on_tokens(first_step, ids [B, n]) is called with every `stream_every` new
-        columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32."""
+        columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32.
+        logprobs / top_logprobs = K (vc_request_generate_logprobs): last_generate_logprobs = (token_logprobs [B, n] float32,
+        top_logprobs [B, n, K] float32, top_ids [B, n, K] int32) of the n columns returned — log_softmax of every step's fp32 logits,
+        the model's own distribution before temperature / top-k / top-p; a row's finishing token is scored, positions behind it hold
+        0.0 / 0.0 / -1.  The call then runs on the session's own loop (not in the decode pool); the ids are the same.  None when not
+        asked."""
         ids = self._ids(input_ids)
         B, T = ids.shape
+        K = self._top_k(top_logprobs)
+        want_lp = bool(logprobs) or K > 0
+        self.last_generate_logprobs = None
         pad = int(self.cfg.pad_token_id or 0) if pad_token_id is None else int(pad_token_id)
         if B > self.MAX_BATCH:
             # a replica prefills at most 16 sequences at a time: larger batches run as consecutive pieces.  Rows are
@@ -552,18 +597,24 @@ class HipEngine:
             # spliced lengths ACROSS pieces fail like they do inside one (the reference's quirk 6)
             if on_tokens is not None:
                 raise ValueError(f"streaming needs a batch of at most {self.MAX_BATCH} sequences")
-            parts, lens = [], set()
+            parts, lens, lps = [], set(), []
             for b0 in range(0, B, self.MAX_BATCH):
                 sl = slice(b0, b0 + self.MAX_BATCH)
                 parts.append(self.generate(ids[sl], *(None if a is None else a[sl] for a in (images, segs, depths)),
                                            attention_mask=None if attention_mask is None else attention_mask[sl],
                                            max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                            pad_token_id=pad_token_id, stop_sequences=stop_sequences, do_sample=do_sample,
-                                           temperature=temperature, top_k=top_k, top_p=top_p, seed=seed + b0))
+                                           temperature=temperature, top_k=top_k, top_p=top_p, seed=seed + b0,
+                                           logprobs=want_lp, top_logprobs=K))
+                lps.append(self.last_generate_logprobs)
                 lens.add(int(self.lib.vc_last_spliced_len(self._model)))
             if len(lens) > 1:
                 raise UnboundLocalError("local variable '_new_labels' referenced before assignment")
             n = max(p.shape[1] for p in parts)
+            if want_lp:   # pieces pad to the longest one with what a finished row holds: 0.0 / 0.0 / -1
+                wide = lambda a, fill: np.pad(a, ((0, 0), (0, n - a.shape[1])) + ((0, 0),) * (a.ndim - 2), constant_values=fill)
+                self.last_generate_logprobs = tuple(np.concatenate([wide(q[i], fill) for q in lps], axis=0)
+                                                    for i, fill in enumerate((0.0, 0.0, -1)))
             return np.concatenate([np.pad(p, ((0, 0), (0, n - p.shape[1])), constant_values=pad) for p in parts], axis=0)
         (pi, ps, pd), on_dev, keep = self._pixels(*self._image_blocks(B, images, segs, depths))
         out = np.empty((B, max_new_tokens), dtype=np.int32)
@@ -588,6 +639,19 @@ class HipEngine:
         # hides keys in the prefill; the cached steps see every key (the reference).  Announced last: the one-shot mask is
         # consumed by the call right below, nothing in between can raise and leave it armed
         self._announce_mask(attention_mask, B, T)
+        tok_lp = top_lp = top_id = None
+        if want_lp:
+            rows = B * int(max_new_tokens)
+            tok_lp = np.zeros((rows,), dtype=np.float32)
+            top_lp = np.zeros((rows * K,), dtype=np.float32)
+            top_id = np.full((rows * K,), -1, dtype=np.int32)
+            try:
+                self._check(self.lib.vc_request_generate_logprobs(self._model, K, tok_lp.ctypes.data_as(C.c_void_p),
+                                                                  top_lp.ctypes.data_as(C.c_void_p) if K else None,
+                                                                  top_id.ctypes.data_as(C.c_void_p) if K else None, C.c_size_t(rows)))
+            except BaseException:
+                self.lib.vc_clear_attention_mask(self._model)
+                raise
         self._check(self.lib.vc_generate(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev,
                                          int(max_new_tokens), eos, pad,
                                          flat.ctypes.data_as(C.c_void_p) if stops else None,
@@ -597,6 +661,10 @@ class HipEngine:
         if errs:
             raise errs[0]
         self._cur_batch = B
+        if want_lp:
+            mn = int(max_new_tokens)
+            self.last_generate_logprobs = (tok_lp.reshape(B, mn)[:, : n.value].copy(), top_lp.reshape(B, mn, K)[:, : n.value].copy(),
+                                           top_id.reshape(B, mn, K)[:, : n.value].copy())
         return out[:, : n.value].copy()
 
     # bookkeeping used by decode_step

@@ -67,10 +67,34 @@ class KVCacheHandle:
         self.length = int(length)
 
 
+class GenerateOutput(dict):
+    """What generate(return_dict_in_generate=True / output_logprobs=True / top_logprobs=K) returns; attribute + mapping access,
+    out[0] = sequences.  sequences: the tensor generate() returns otherwise.  token_logprobs [B, n] float32: log p(generated token);
+    top_logprobs [B, n, K] float32 / top_token_ids [B, n, K] int64: the K most likely tokens of every step, ordered by (log-prob
+    descending, id ascending); sequence_logprob [B]: row sums of token_logprobs.  n = generated columns.  A row's finishing token is
+    scored; positions behind it hold 0.0 / 0.0 / -1.  Fields that were not requested are None."""
+
+    def __init__(self, sequences=None, token_logprobs=None, top_logprobs=None, top_token_ids=None, sequence_logprob=None):
+        super().__init__(sequences=sequences, token_logprobs=token_logprobs, top_logprobs=top_logprobs,
+                         top_token_ids=top_token_ids, sequence_logprob=sequence_logprob)
+        self.__dict__ = self
+
+    def __getitem__(self, k):
+        if isinstance(k, int):
+            return [v for v in (self.sequences, self.token_logprobs, self.top_logprobs, self.top_token_ids, self.sequence_logprob)
+                    if v is not None][k]
+        return dict.__getitem__(self, k)
+
+
+MAX_TOP_LOGPROBS = 32
+
+
 class TokenScores(dict):
     """What score() returns: token_logprobs [B, S] (log p(label) where labels != -100 and a row stands in front, 0 elsewhere), labels
     [B, S] as the splice laid them out, sequence_logprob [B] (row sums), loss (mean of -logprob over the scored entries, nan when
-    there are none) and past_key_values."""
+    there are none) and past_key_values.  With score(top_logprobs=K): top_logprobs [B, S, K] float32 and top_token_ids [B, S, K]
+    int64 — the K most likely tokens at every scored position (what the model would have said instead of the label), 0.0 / -1
+    elsewhere; None otherwise."""
 
     def __init__(self, **kw):
         super().__init__(**kw)
@@ -259,17 +283,23 @@ class _HipCausalLMBase:
         return self._forward(input_ids, attention_mask, past_key_values, labels, use_cache, output_attentions, output_hidden_states,
                              images, segs, depths, return_dict, want_logits=True)
 
-    def score(self, input_ids, labels, images=None, segs=None, depths=None, past_key_values=None, attention_mask=None):
+    def score(self, input_ids, labels, images=None, segs=None, depths=None, past_key_values=None, attention_mask=None,
+              top_logprobs: int = 0):
         """log p(label) per token without logits leaving the device: same dispatch as forward (prefill with images, text-only
         prefill, continuation of `past_key_values`), no all-row logits.  -> TokenScores.  Candidate answers behind one prompt:
-        prefill once, then per candidate score(candidate_ids, candidate_ids, past_key_values=pkv) and pkv.crop(prompt_length)."""
+        prefill once, then per candidate score(candidate_ids, candidate_ids, past_key_values=pkv) and pkv.crop(prompt_length).
+        top_logprobs = K (0 .. 32): additionally the K most likely tokens at every scored position (TokenScores.top_logprobs /
+        top_token_ids), ordered by (log-prob descending, id ascending)."""
         if labels is None:
             raise ValueError("score() needs labels")
+        K = int(top_logprobs or 0)
+        if K < 0 or K > MAX_TOP_LOGPROBS:
+            raise ValueError(f"top_logprobs must be in 0 .. {MAX_TOP_LOGPROBS}, got {K}")
         return self._forward(input_ids, attention_mask, past_key_values, labels, None, None, None, images, segs, depths, None,
-                             want_logits=False)
+                             want_logits=False, top_logprobs=K)
 
     def _forward(self, input_ids, attention_mask, past_key_values, labels, use_cache, output_attentions, output_hidden_states,
-                 images, segs, depths, return_dict, want_logits):
+                 images, segs, depths, return_dict, want_logits, top_logprobs=0):
         import torch
 
         if labels is not None:
@@ -308,6 +338,8 @@ class _HipCausalLMBase:
             if labels is not None:   # one new position: the shift leaves nothing to score (torch's mean over an empty set)
                 self.engine.last_token_logprobs = np.zeros((B, 1), dtype=np.float32)
                 self.engine.last_spliced_labels = lab1
+                self.engine.last_top_logprobs = np.zeros((B, 1, top_logprobs), dtype=np.float32) if top_logprobs else None
+                self.engine.last_top_ids = np.full((B, 1, top_logprobs), -1, dtype=np.int32) if top_logprobs else None
         elif past_key_values is not None:
             # multi-token continuation of the cache: with images=None, prepare_inputs_labels_for_multimodal returns early
             # (vcoder_ds_llava_arch.py:129-133) and LlamaModel runs the n new ids at positions past .. past+n-1, causal inside
@@ -340,7 +372,7 @@ class _HipCausalLMBase:
             else:
                 self.engine.clear_attention_mask()
             _, full = self.engine.extend(tok, all_logits=want_logits, hidden_states=bool(output_hidden_states),
-                                         attentions=bool(output_attentions), labels=labels)
+                                         attentions=bool(output_attentions), labels=labels, top_logprobs=top_logprobs)
             past_key_values.length += n
             logits = torch.from_numpy(full) if want_logits else None
             pkv = past_key_values
@@ -356,7 +388,7 @@ class _HipCausalLMBase:
                                              all_logits=want_logits, reserve=self._decode_reserve,
                                              attention_mask=attention_mask if images is not None else None,
                                              hidden_states=bool(output_hidden_states), attentions=bool(output_attentions),
-                                             labels=labels)
+                                             labels=labels, top_logprobs=top_logprobs)
             self._generation += 1
             logits = torch.from_numpy(full) if want_logits else None
             pkv = KVCacheHandle(self, self._generation, S, B)
@@ -364,7 +396,12 @@ class _HipCausalLMBase:
         if labels is not None:
             lp, sl, loss = _score_outputs(self.engine)
             if not want_logits:
-                return TokenScores(token_logprobs=lp, labels=sl, sequence_logprob=lp.sum(dim=1), loss=loss, past_key_values=pkv)
+                tlp = tid = None
+                if top_logprobs:
+                    tlp = torch.from_numpy(np.ascontiguousarray(self.engine.last_top_logprobs))
+                    tid = torch.from_numpy(np.ascontiguousarray(self.engine.last_top_ids).astype(np.int64))
+                return TokenScores(token_logprobs=lp, labels=sl, sequence_logprob=lp.sum(dim=1), loss=loss, past_key_values=pkv,
+                                   top_logprobs=tlp, top_token_ids=tid)
         if hasattr(ids, "device") and getattr(ids, "is_cuda", False):
             logits = logits.to(ids.device)
         hs = None
@@ -407,9 +444,21 @@ class _HipCausalLMBase:
                  temperature: float = 1.0, top_p: Optional[float] = None, top_k: Optional[int] = None, num_beams: int = 1,
                  max_new_tokens: Optional[int] = None, max_length: Optional[int] = None, streamer=None,
                  use_cache: bool = True, stopping_criteria=None, eos_token_id=None, pad_token_id=None,
-                 attention_mask=None, generator=None, seed: Optional[int] = None, **kwargs):
+                 attention_mask=None, generator=None, seed: Optional[int] = None, return_dict_in_generate: bool = False,
+                 output_logprobs: bool = False, top_logprobs: int = 0, **kwargs):
         """Returns cat(input_ids, new_ids) [B, T+n] int64 — the prompt part keeps its negative placeholder ids,
         callers slice `[:, T:]` (serve/cli.py:135).
+
+        return_dict_in_generate / output_logprobs / top_logprobs = K (0 .. 32; implies output_logprobs): a GenerateOutput instead —
+        `sequences` (that tensor), `token_logprobs` [B, n], `top_logprobs` / `top_token_ids` [B, n, K], `sequence_logprob` [B]; what
+        was not asked for is None.  The log-probs are those of the model's own next-token distribution: log_softmax of the step's
+        fp32 logits, taken BEFORE temperature / top-k / top-p — also when sampling (the probability the model gave the token, not
+        the one the warped distribution drew it with).  For greedy decoding this is what HF's
+        compute_transition_scores(..., normalize_logits=True) gives.  Ties order by the lower id, as the greedy argmax.  A row's
+        finishing token (EOS / the token completing a stop sequence) is scored; later positions hold 0.0 / 0.0 / -1.  They come from
+        a kernel behind every selection of the device loop (the call then runs on the session's own loop, not in the decode pool);
+        the host fallback loop computes the same from its logits.  HF's full-vocabulary `output_scores` is not implemented: with
+        return_dict_in_generate it raises, alone it is ignored as before.
 
         Everything the reference's callers ask for runs on the device inside the hipGraph-replayed decode loop
         (vc_generate): greedy argmax; sampling with HF's warper order temperature -> top-k -> top-p -> multinomial
@@ -425,6 +474,17 @@ class _HipCausalLMBase:
             input_ids = inputs
         if temperature is not None and float(temperature) <= 0.0:
             do_sample = False
+        # every refusal of the log-prob arguments comes before the engine is touched
+        K = int(top_logprobs or 0)
+        if K < 0 or K > MAX_TOP_LOGPROBS:
+            raise ValueError(f"top_logprobs must be in 0 .. {MAX_TOP_LOGPROBS}, got {K}")
+        want_lp = bool(output_logprobs) or K > 0
+        as_dict = bool(return_dict_in_generate) or want_lp
+        if return_dict_in_generate and kwargs.get("output_scores"):
+            raise NotImplementedError("output_scores (HF's full-vocabulary score tuples) is not implemented: ask for "
+                                      "output_logprobs=True / top_logprobs=K instead")
+        if num_beams != 1 and want_lp:
+            raise NotImplementedError("per-token log-probs (output_logprobs / top_logprobs) are not implemented for num_beams != 1")
         if num_beams != 1:
             if streamer is not None:
                 raise ValueError("`streamer` cannot be used with beam search")   # HF's own check
@@ -434,10 +494,11 @@ class _HipCausalLMBase:
                     generator = torch.Generator().manual_seed(int(seed if seed is not None else torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF)
                 sample = dict(temperature=float(temperature or 1.0), top_k=50 if top_k is None else int(top_k),
                               top_p=1.0 if top_p is None else float(top_p), generator=generator)
-            return self._beam_search(input_ids, images, segs, depths, int(num_beams), max_new_tokens, max_length, eos_token_id,
+            seqs = self._beam_search(input_ids, images, segs, depths, int(num_beams), max_new_tokens, max_length, eos_token_id,
                                      pad_token_id, attention_mask, stopping_criteria,
                                      float(kwargs.get("length_penalty", 1.0)), kwargs.get("early_stopping", False),
                                      kwargs.get("_beam_len_counts_prompt", True), sample)
+            return GenerateOutput(sequences=seqs) if as_dict else seqs
         T = input_ids.shape[1]
         B = input_ids.shape[0]
         if max_new_tokens is None:
@@ -485,9 +546,12 @@ class _HipCausalLMBase:
                                        do_sample=bool(do_sample), temperature=float(temperature or 1.0),
                                        top_k=top_k or 0, top_p=1.0 if top_p is None else top_p, seed=seed or 0,
                                        on_tokens=on_tokens, stream_every=kwargs.get("stream_every", 1),
-                                       attention_mask=attention_mask)
+                                       attention_mask=attention_mask, logprobs=want_lp, top_logprobs=K)
             self._generation += 1
             out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
+            if want_lp:
+                tok_lp, top_lp, top_id = (torch.from_numpy(np.ascontiguousarray(a)) for a in self.engine.last_generate_logprobs)
+                top_id = top_id.to(torch.int64)
             if streamer is not None:
                 streamer.end()
         else:
@@ -500,8 +564,11 @@ class _HipCausalLMBase:
             cur = ids_cpu
             if generator is None and do_sample:
                 generator = torch.Generator().manual_seed(int(seed) & 0x7FFFFFFFFFFFFFFF)
+            lp_cols, top_lp_cols, top_id_cols = [], [], []
+            alive = torch.ones(B, dtype=torch.bool)   # rows whose finishing token has not been emitted yet
             for step in range(max_new_tokens):
                 scores = logits.float()
+                raw = scores
                 if do_sample:
                     scores = scores / float(temperature)
                     if top_k and 0 < top_k < scores.shape[-1]:
@@ -516,6 +583,23 @@ class _HipCausalLMBase:
                 if eos is not None:
                     nxt = nxt * unfinished + pad * (1 - unfinished)
                 cur = torch.cat([cur, nxt[:, None]], dim=1)
+                if want_lp:
+                    # the raw distribution, as the device kernel: log_softmax of the fp32 logits; stable descending sort = ties to
+                    # the lower id; entries that are -inf hold id -1; rows behind their finishing token 0.0 / 0.0 / -1
+                    lsm = torch.log_softmax(raw, dim=-1)
+                    col = lsm.gather(1, nxt[:, None]).squeeze(1)
+                    lp_cols.append(torch.where(alive, col, torch.zeros_like(col)))
+                    if K:
+                        order = torch.sort(raw, dim=-1, descending=True, stable=True)[1][:, :K]
+                        if order.shape[1] < K:
+                            order = torch.cat([order, order.new_zeros(B, K - order.shape[1])], 1)
+                        tl = lsm.gather(1, order)
+                        tl[:, raw.shape[-1]:] = float("-inf")
+                        ti = torch.where(torch.isinf(tl) & (tl < 0), torch.full_like(order, -1), order)
+                        top_lp_cols.append(torch.where(alive[:, None], tl, torch.zeros_like(tl)))
+                        top_id_cols.append(torch.where(alive[:, None], ti, torch.full_like(ti, -1)))
+                    if eos is not None:
+                        alive = alive & unfinished.bool() & ~torch.isin(nxt, torch.tensor([eos] + eos_more))
                 if streamer is not None:
                     streamer.put(nxt.cpu())
                 if eos is not None:
@@ -530,11 +614,20 @@ class _HipCausalLMBase:
                 lg, _ = self.engine.decode_step(nxt.numpy().astype(np.int32))
                 logits = torch.from_numpy(lg)
             out = cur
+            if want_lp:
+                tok_lp = torch.stack(lp_cols, 1).float()
+                top_lp = torch.stack(top_lp_cols, 1).float() if K else torch.zeros(B, tok_lp.shape[1], 0)
+                top_id = torch.stack(top_id_cols, 1).to(torch.int64) if K else torch.zeros(B, tok_lp.shape[1], 0, dtype=torch.int64)
             if streamer is not None:
                 streamer.end()
         if hasattr(input_ids, "device"):
             out = out.to(input_ids.device)
-        return out
+        if not as_dict:
+            return out
+        if not want_lp:
+            return GenerateOutput(sequences=out)
+        return GenerateOutput(sequences=out, token_logprobs=tok_lp, top_logprobs=top_lp if K else None,
+                              top_token_ids=top_id if K else None, sequence_logprob=tok_lp.sum(dim=1))
 
     _sample_calls = 0
 
