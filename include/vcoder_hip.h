@@ -254,8 +254,30 @@ int vc_rewind(vc_model* m, int P);
 
 /* beam search support: the KV rows of the current vc_prefill / vc_decode_step loop are permuted, row r <- old row src_rows[r] —
  * `past_key_values` reordered by beam_idx after a beam step ([HF] generation/utils.py beam_search; the reference's eval loaders
- * forward num_beams: eval/model_seg_loader.py:129-139) */
+ * forward num_beams: eval/model_seg_loader.py:129-139).  It serves a host-driven beam loop (beam-sample, stopping criteria, strict
+ * mode); plain beam search runs inside the device loop, vc_generate_beam below. */
 int vc_reorder_cache(vc_model* m, const int32_t* src_rows, int B);
+
+/* generate(num_beams = n) inside the device loop ([HF] GenerationMixin.beam_search + BeamSearchScorer of Transformers 4.31, as the
+ * reference's eval loaders call it: batch 1, no stopping criteria).  ids [B, T] are the un-expanded rows; the engine expands every
+ * sequence to n rows (b * n .. b * n + n - 1) for the encode, the splice and the prefill, then replays one captured beam step per
+ * token: the linears and attention of a decode step over B * n rows, the 2 n best log-probs of every row, a selection kernel (the
+ * 2 n best candidates per sequence by score, then flat index beam * V + id; BeamSearchScorer.process; hypotheses kept as
+ * back-pointers), a cache permute that copies only the positions behind the prompt, and the embedding of the chosen tokens.  Scores
+ * are fp32: candidate = log-prob + running beam score, hypothesis = sum / len ** length_penalty with the power taken on the host.
+ * early_stopping: 0 false, 1 true, 2 "never"; len_counts_prompt != 0: a hypothesis' length counts the T prompt ids (4.31).
+ * eos_ids: up to 8 ids (n_eos 0: none), pad_id < 0: none (the rows of a done sequence then emit id 0, and a result that needs
+ * padding fails with VC_ERR_INVALID as HF's "`pad_token_id` has to be defined").
+ * out_ids [B, max_new] host: the best hypothesis of every sequence, one EOS (eos_ids[0]) behind it where it is shorter than the
+ * returned width min(longest + 1, max_new), pad_id elsewhere; out_len [B] its length; out_score [B] its score; n_steps the steps run.
+ * Honours vc_set_attention_mask / vc_set_image_counts (given for the B un-expanded rows).  Runs on the session's own loop.
+ * Refused before anything is touched: num_beams < 1, B * num_beams > 16, n_eos > 8 (VC_ERR_INVALID); precision mode "strict", a
+ * pending vc_request_generate_logprobs (VC_ERR_STATE).  More than n EOS ids among a step's 2 n best fails with VC_ERR_INVALID (HF's
+ * ValueError). */
+int vc_generate_beam(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
+                     int pixels_on_device, int num_beams, int max_new, const int32_t* eos_ids, int n_eos, int pad_id,
+                     float length_penalty, int early_stopping /* 0 false, 1 true, 2 "never" */, int len_counts_prompt,
+                     int32_t* out_ids /* [B, max_new] */, int32_t* out_len /* [B] */, float* out_score /* [B] */, int* n_steps);
 
 /* greedy generate(): encode + splice + prefill + (max_new-1) hipGraph-replayed decode steps, HF semantics
  * (SURVEY.md Appendix C): eos_id < 0 disables EOS; finished rows emit pad_id; stops when all rows finished.

@@ -135,6 +135,26 @@ void vck_token_logprob(const float* logits, int ldl, const int* target, float* l
 #define VC_MAX_TOP_LOGPROBS 32
 void vck_topk_logprob(const float* logits, int ldl, const int* chosen, float* chosen_lp, float* top_lp, int32_t* top_ids, int rows,
                       int V, int K, int lds_floats, void* stream);
+/* One beam-search step of B sequences of n beams (rows b * n .. b * n + n - 1, R = B * n <= 16) behind a vck_topk_logprob with
+ * K = 2 n into cand_lp / cand_id [R, 2 n]: candidate score = lp + beam_score[row] (one fp32 add), the 2 n best per sequence by
+ * (score descending, then row, then id ascending; id -1 entries are no candidates), then HF's BeamSearchScorer.process (4.31): an id of
+ * the EOS set at rank < n adds a hypothesis (score = sum / hyp_den[step]; at most n kept, the worst leaves), at rank >= n it is
+ * skipped, anything else fills the next of the n beam slots; is_done with done_den[step] in the early_stopping mode.  Layouts:
+ *   rows   [R][vck_row_state_stride()] RowState records: word 2 (step) is read, words 2 / 3 advance by advance & 1 / advance & 2
+ *   seq    [B][4]: done, hypotheses held, float bits of the worst score (1e9 at the start), the step that set done
+ *   hyp    [B][n][4]: float bits of score and of sum_logprobs, step, source row — back-pointers into
+ *   tok_tab / parent_tab [max_new][R] (row `step` is written: the token and the source row of every row)
+ *   params [12]: number of EOS ids (<= 8), pad id, early_stopping (0 false, 1 true, 2 "never"), max_new, 8 EOS ids
+ *   flags  [2]: every sequence done (written each step); set when fewer than n beam slots could be filled (the host raises)
+ * A done sequence emits pad with score 0, keeps its parents as the identity and ignores its candidates. */
+void vck_beam_step(const float* cand_lp, const int* cand_id, float* beam_score, int* rows, int* next_tok, int* perm, int* tok_tab,
+                   int* parent_tab, int* seq, int* hyp, const float* hyp_den, const float* done_den, const int* params, int* flags,
+                   int B, int n, int advance, void* stream);
+/* The beam loop's cache permutation: K and V of one layer, [R][H][cap_positions][pos_bytes] each; row r <- old row perm[r] for the
+ * positions [start[r], rows[r] word 3 (position)) only, staged through tmp ([2][R][H][span_positions * pos_bytes] bytes; a longer
+ * tail is cut at span_positions).  perm, start and the records are read on the device.  pos_bytes a multiple of 16. */
+void vck_kv_permute_tail(void* kcache, void* vcache, void* tmp, const int* perm, const int* start, const int* rows, int R, int H,
+                         int cap_positions, int pos_bytes, int span_positions, void* stream);
 void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w, uint16_t* xg, int B,
                           int D, int npart, void* stream);
 void vck_advance(int* step_dev, int* pos_dev, int* ctx_dev, void* stream);

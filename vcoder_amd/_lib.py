@@ -99,6 +99,13 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_debug_prefill_layers.restype = C.c_int
     lib.vc_reorder_cache.argtypes = [vp, vp, i32]
     lib.vc_reorder_cache.restype = C.c_int
+    lib.vc_generate_beam.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, i32, C.c_float, i32, i32, vp, vp, vp,
+                                     C.POINTER(C.c_int)]
+    lib.vc_generate_beam.restype = C.c_int
+    lib.vck_beam_step.argtypes = [vp] * 14 + [i32, i32, i32, vp]
+    lib.vck_beam_step.restype = None
+    lib.vck_kv_permute_tail.argtypes = [vp] * 6 + [i32] * 5 + [vp]
+    lib.vck_kv_permute_tail.restype = None
     lib.vc_request_token_scores.argtypes = [vp, vp, i32, i32, vp, vp, C.c_size_t]
     lib.vc_request_token_scores.restype = C.c_int
     lib.vc_request_top_logprobs.argtypes = [vp, i32, vp, vp, C.c_size_t]

@@ -237,6 +237,15 @@ struct vc_model {
     hipGraphExec_t graph_lp = nullptr;   // the same step with the log-prob launch (lp_on), for graph_lp_k alternatives
     int graph_lp_rows = 0, graph_lp_k = 0;
     bool graph_lp_masked = false;
+    // the device beam loop (vc_generate_beam; engine_llm.inc BeamLoop): bm_state holds the fixed-size part (candidates, beam scores,
+    // perm, prompt lengths, sequence records, hypotheses, parameters, flags), bm_tab the tok / parent tables, bm_den the two
+    // denominator tables, bm_tmp the staging of the tail permute — the last three sized for bm_cap_new steps.  graph_beam is one
+    // captured beam step over graph_beam_rows rows of graph_beam_n beams, kept beside the plain and the log-prob step.
+    Buf bm_state, bm_tab, bm_den, bm_tmp;
+    int bm_cap_new = 0;
+    hipGraphExec_t graph_beam = nullptr;
+    int graph_beam_rows = 0, graph_beam_n = 0, graph_beam_cap_new = 0;
+    bool graph_beam_masked = false;
     struct vc_pool* pool = nullptr;  // the root model's shared decode pool (created on first use; sessions point at it)
     bool pool_profile = false;       // root model: the pool's step graphs carry in-situ timing stamps (vc_pool_profile)
     bool fp8_kv = true;              // weight format 2: the KV cache of the bf16-step modes in e4m3 (vc_model_set_fp8_kv)

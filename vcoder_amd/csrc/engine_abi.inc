@@ -188,7 +188,7 @@ VC_API void vc_model_destroy(vc_model* m) {
                    &m->s_q, &m->s_attn, &m->s_h, &m->s_kc, &m->s_vc, &m->s_xl, &m->pp_src, &m->pp_sq, &m->pp_tmp, &m->pp_out,
                    &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre,
                    &m->ext_tok, &m->sc_idx, &m->sc_lp, &m->sc_xn, &m->sc_logits, &m->sc_tlp, &m->sc_tid, &m->lp_tok, &m->lp_top,
-                   &m->lp_ids})
+                   &m->lp_ids, &m->bm_state, &m->bm_tab, &m->bm_den, &m->bm_tmp})
         b->release();
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);

@@ -128,6 +128,7 @@ void ensure_prefill_ws(vc_model* m, int B, int Scap) {
 void drop_graph(vc_model* m) {
     if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
     if (m->graph_lp) { (void)hipGraphExecDestroy(m->graph_lp); m->graph_lp = nullptr; }
+    if (m->graph_beam) { (void)hipGraphExecDestroy(m->graph_beam); m->graph_beam = nullptr; }
 }
 
 // the session's own decode loop: KV cache for B sequences of S_total positions + the per-step buffers
@@ -501,6 +502,80 @@ void enqueue_step_logprobs(vc_model* m, const LoopView& v, const float* logits, 
     launch_topk_logprob(a, nrows, -1, v.st);
 }
 
+// ---- the device beam loop (vc_generate_beam) -----------------------------------------------------------------------------------
+// Its buffers: the fixed-size part carved from m->bm_state, the tables from m->bm_tab / m->bm_den (ensure_beam sizes them).
+struct BeamLoop {
+    float* cand_lp;   // [16, 32]
+    int* cand_id;
+    float* score;     // [16]
+    int *perm, *start, *seq, *hyp, *params, *flags;
+    int *tok_tab, *parent_tab;   // [cap_new][R]
+    float *hyp_den, *done_den;   // [cap_new + 1]
+    int B, n, cap_new;
+};
+constexpr int BEAM_CAND = VC_BEAM_MAX_ROWS * VC_MAX_TOP_LOGPROBS;
+constexpr int BEAM_STATE_INTS = 2 * BEAM_CAND + 3 * VC_BEAM_MAX_ROWS + VC_BEAM_MAX_ROWS * (BQ_STRIDE + BH_STRIDE) + BP_STRIDE + 4;
+BeamLoop beam_view(vc_model* m, int B, int n) {
+    BeamLoop bl{};
+    int* p = m->bm_state.as<int>();
+    bl.cand_lp = reinterpret_cast<float*>(p);
+    bl.cand_id = p + BEAM_CAND;
+    p += 2 * BEAM_CAND;
+    bl.score = reinterpret_cast<float*>(p);
+    bl.perm = p + VC_BEAM_MAX_ROWS;
+    bl.start = p + 2 * VC_BEAM_MAX_ROWS;
+    bl.seq = p + 3 * VC_BEAM_MAX_ROWS;
+    bl.hyp = bl.seq + VC_BEAM_MAX_ROWS * BQ_STRIDE;
+    bl.params = bl.hyp + VC_BEAM_MAX_ROWS * BH_STRIDE;
+    bl.flags = bl.params + BP_STRIDE;
+    bl.cap_new = m->bm_cap_new;
+    bl.tok_tab = m->bm_tab.as<int>();
+    bl.parent_tab = bl.tok_tab + (size_t)bl.cap_new * VC_BEAM_MAX_ROWS;
+    bl.hyp_den = m->bm_den.as<float>();
+    bl.done_den = bl.hyp_den + bl.cap_new + 1;
+    bl.B = B;
+    bl.n = n;
+    return bl;
+}
+// bytes one (row, head) of the tail-permute staging holds: the cache rows of cap_new positions
+size_t beam_span_cap(const vc_model* m, int cap_new) { return (size_t)cap_new * m->hd * m->kv_es; }
+// the buffers of a call of R rows and max_new steps; the captured beam step bakes their pointers and the capacity in
+void ensure_beam(vc_model* m, int R, int max_new) {
+    m->bm_state.ensure((size_t)BEAM_STATE_INTS * 4, true);
+    const int cap_new = std::max((int)rup(max_new, 64), m->bm_cap_new);
+    const void* before[] = {m->bm_tab.p, m->bm_den.p, m->bm_tmp.p};
+    m->bm_tab.ensure((size_t)2 * cap_new * VC_BEAM_MAX_ROWS * 4);
+    m->bm_den.ensure((size_t)2 * (cap_new + 1) * 4);
+    m->bm_tmp.ensure((size_t)2 * R * m->c.heads * beam_span_cap(m, cap_new));
+    m->bm_cap_new = cap_new;
+    const void* after[] = {m->bm_tab.p, m->bm_den.p, m->bm_tmp.p};
+    for (int i = 0; i < 3; ++i)
+        if (before[i] != after[i] && m->graph_beam) {
+            (void)hipGraphExecDestroy(m->graph_beam);
+            m->graph_beam = nullptr;
+        }
+}
+// the tail of a beam step on `logits`: the 2 n best log-probs of every row, the selection / bookkeeping kernel, the tail permute of
+// every layer's K and V (`permute`; nothing to move behind the prefill) and the embedding of the chosen tokens
+void enqueue_beam_tail(vc_model* m, const LoopView& v, const BeamLoop& bl, const float* logits, int advance, bool permute) {
+    const vc_model_cfg& c = m->c;
+    const int R = bl.B * bl.n;
+    TopkLogprobArgs ta{logits, c.vocab, nullptr, nullptr, bl.cand_lp, bl.cand_id, c.vocab, 2 * bl.n, nullptr, nullptr, 0};
+    launch_topk_logprob(ta, R, -1, v.st);
+    BeamStepArgs ba{bl.cand_lp, bl.cand_id, bl.score, v.rows, v.next_tok, bl.perm, bl.tok_tab, bl.parent_tab, bl.seq, bl.hyp,
+                    bl.hyp_den, bl.done_den, bl.params, bl.flags, bl.B, bl.n, advance};
+    launch_beam_step(ba, v.st);
+    if (permute) {
+        const KvTarget kv = loop_kv(v);
+        const int pos_bytes = m->hd * v.es;
+        for (int l = 0; l < c.layers; ++l)
+            launch_kv_permute_tail(kcache(m, kv, l), vcache(m, kv, l), m->bm_tmp.p, bl.perm, bl.start, v.rows, R, c.heads,
+                                   (size_t)v.capS * pos_bytes, pos_bytes, beam_span_cap(m, bl.cap_new), v.st);
+    }
+    launch_embed_tokens_ssq(v.next_tok, m->embed, v.x_dec, v.ssq, m->llm[0].in_norm, v.xg_dec, R, c.hidden, m->npart, v.st, v.split_G,
+                            (m->precision || v.split_G) ? lo_plane(m, m->embed) : nullptr);
+}
+
 // the fused decode attention of layer l of a step over the first `nrows` rows of a loop
 AttnDecodeFusedArgs decode_attn_args(const vc_model* m, const LoopView& v, int l, int nrows) {
     const KvTarget kv = loop_kv(v);
@@ -517,7 +592,8 @@ AttnDecodeFusedArgs decode_attn_args(const vc_model* m, const LoopView& v, int l
 // layer's residual row, the final norm; and per layer the probabilities of the new token's query over the pos + 1 keys, recomputed
 // from the step's own roped q (rounded as the fused kernel rounds it) and the K cache — the fused decode attention keeps only
 // unnormalised scores.
-void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_pos = -1) {
+// beam != nullptr: a step of the device beam loop — the same linears and attention, the beam tail in place of the selection.
+void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_pos = -1, const BeamLoop* beam = nullptr) {
     const vc_model_cfg& c = m->c;
     const bool hooks = hook_pos >= 0;
     LoopView v = view;
@@ -548,8 +624,12 @@ void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_
         [&](int l) {
             if (hooks) emit_hidden(m, l + 1, nrows, 1, v.x_dec);
         });
-    launch_select_embed(select_args(m, v, v.logits, nrows, 3), v.st);                                        // K19/K20+K10
-    enqueue_step_logprobs(m, v, v.logits, nrows);
+    if (beam) {
+        enqueue_beam_tail(m, v, *beam, v.logits, 3, true);
+    } else {
+        launch_select_embed(select_args(m, v, v.logits, nrows, 3), v.st);                                    // K19/K20+K10
+        enqueue_step_logprobs(m, v, v.logits, nrows);
+    }
     // in-situ timing: fold the step's slots (5 per layer: qkv, attention, o, gate/up, down; then lm_head) into the span's sums
     if (v.stamps && v.stamp_next && v.prof_acc)
         launch_stamp_accumulate(v.stamps, *v.stamp_next, m->c.layers, v.prof_acc, v.stamp_scratch, v.st);
@@ -674,13 +754,13 @@ void run_extend(vc_model* m, const int* tok_dev, int B, int n, bool all_rows) {
     else last_row_logits(m, x, B, n);   // the last row of every sequence through the lm_head GEMV, as a prefill does
 }
 
-hipGraphExec_t capture_step(vc_model* m, const LoopView& v, int nrows) {
+hipGraphExec_t capture_step(vc_model* m, const LoopView& v, int nrows, const BeamLoop* beam = nullptr) {
     hipGraph_t g = nullptr;
     hipGraphExec_t exec = nullptr;
     // thread-local mode: other sessions (host threads) may allocate / copy while this thread captures
     HIPCHK(hipStreamBeginCapture(v.st, hipStreamCaptureModeThreadLocal));
     try {
-        enqueue_decode_step(m, v, nrows);
+        enqueue_decode_step(m, v, nrows, -1, beam);
     } catch (...) {
         (void)hipStreamEndCapture(v.st, &g);
         throw;
@@ -710,6 +790,22 @@ hipGraphExec_t ensure_graph(vc_model* m, int B) {
     m->graph_rows = B;
     m->graph_masked = m->kmask_in_decode;
     return m->graph;
+}
+
+// the captured beam step of B sequences of n beams (after ensure_beam), kept beside the plain and the log-prob step
+hipGraphExec_t ensure_beam_graph(vc_model* m, int B, int n) {
+    const int R = B * n;
+    if (m->graph_beam && m->graph_beam_rows == R && m->graph_beam_n == n && m->graph_beam_masked == m->kmask_in_decode &&
+        m->graph_beam_cap_new == m->bm_cap_new)
+        return m->graph_beam;
+    if (m->graph_beam) { (void)hipGraphExecDestroy(m->graph_beam); m->graph_beam = nullptr; }
+    const BeamLoop bl = beam_view(m, B, n);
+    m->graph_beam = capture_step(m, session_view(m), R, &bl);
+    m->graph_beam_rows = R;
+    m->graph_beam_n = n;
+    m->graph_beam_masked = m->kmask_in_decode;
+    m->graph_beam_cap_new = m->bm_cap_new;
+    return m->graph_beam;
 }
 
 void ensure_out_ids(vc_model* m, int B, int max_new) {

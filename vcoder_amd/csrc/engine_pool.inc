@@ -1,5 +1,6 @@
 // engine_pool.inc — part of the host engine (textually included by engine.hip): generate() — column trimming, the session's own hipGraph
-// loop, the shared decode pool (driver thread, requests, hold policy) — and its C entry points.
+// loop, the shared decode pool (driver thread, requests, hold policy), beam search inside the session's loop (vc_generate_beam) — and
+// its C entry points.
 
 namespace {
 
@@ -696,6 +697,225 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     }
 }
 
+// ---- beam search inside the device loop (vc_generate_beam) -----------------------------------------------------------------------
+struct BeamCall {
+    int n = 1, max_new = 1, n_eos = 0, pad = -1, early = 0, len_counts_prompt = 1;
+    float length_penalty = 1.f;
+    int eos[VC_BEAM_MAX_EOS] = {};
+};
+struct BeamHypHost {
+    float score, sum;
+    int step, row;
+};
+// BeamHypotheses.add on the host, as beam_step_kernel states it (fp32; the worst — the first of equals — leaves, order kept)
+void beam_add_hyp(std::vector<BeamHypHost>& list, float& worst, int n, float sum, float den, int step, int row) {
+    const float score = sum / den;
+    if ((int)list.size() >= n && !(score > worst)) return;
+    if ((int)list.size() >= n) {
+        size_t lo = 0;
+        for (size_t j = 1; j < list.size(); ++j)
+            if (list[j].score < list[lo].score) lo = j;
+        list.erase(list.begin() + lo);
+    }
+    list.push_back({score, sum, step, row});
+    worst = score;
+    for (const BeamHypHost& h : list) worst = std::min(worst, h.score);
+}
+
+// Every sequence expanded to n rows (rows b * n .. b * n + n - 1, as HF's _expand_inputs_for_generation) for the encode, the splice
+// and the prefill; then one eager beam tail on the prefill logits and max_new - 1 replays of the captured beam step, polled every
+// 8 steps for "every sequence done"; the tables, hypotheses, beam scores and sequence records come back once and the tail of HF's
+// beam_search (BeamSearchScorer.finalize) runs here in fp32.
+void generate_beam_on_session(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
+                              int on_dev, const BeamCall& q, int32_t* out_ids, int32_t* out_len, float* out_score, int* n_steps) {
+    const vc_model_cfg& c = m->c;
+    const int n = q.n, R = B * n, max_new = q.max_new;
+    std::vector<int64_t> ids_x((size_t)R * T);
+    for (int r = 0; r < R; ++r) std::copy(ids + (size_t)(r / n) * T, ids + (size_t)(r / n + 1) * T, ids_x.begin() + (size_t)r * T);
+    if (!m->mask_next.empty()) {
+        REQUIRE(m->mask_B == B && m->mask_T == T, VC_ERR_INVALID, "attention_mask is [%d, %d], input_ids [%d, %d]", m->mask_B, m->mask_T,
+                B, T);
+        std::vector<uint8_t> mk((size_t)R * T);
+        for (int r = 0; r < R; ++r)
+            std::copy(m->mask_next.begin() + (size_t)(r / n) * T, m->mask_next.begin() + (size_t)(r / n + 1) * T, mk.begin() + (size_t)r * T);
+        m->mask_next.swap(mk);
+        m->mask_B = R;
+    }
+    // pixels: the images of sample b (img_counts, one each without them) n times in a row
+    const float* src[3] = {img, img ? seg : nullptr, img ? depth : nullptr};
+    const size_t img_elems = (size_t)3 * c.vit_image * c.vit_image;
+    std::vector<float> host_px[3];
+    Buf dev_px[3];
+    struct Release {
+        Buf* b;
+        ~Release() {
+            for (int k = 0; k < 3; ++k) b[k].release();
+        }
+    } release{dev_px};
+    const float* px[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; ++k) {
+        if (!src[k]) continue;
+        std::vector<int> cnt = m->img_counts[k];
+        if (cnt.empty()) cnt.assign(B, 1);
+        REQUIRE((int)cnt.size() == B, VC_ERR_INVALID, "image counts given for %zu samples, batch is %d", cnt.size(), B);
+        size_t total = 0;
+        for (int b = 0; b < B; ++b) total += (size_t)cnt[b] * n;
+        if (on_dev) dev_px[k].ensure(total * img_elems * 4);
+        else host_px[k].resize(total * img_elems);
+        float* dst = on_dev ? dev_px[k].as<float>() : host_px[k].data();
+        size_t first = 0, at = 0;
+        for (int b = 0; b < B; ++b) {
+            const size_t blk = (size_t)cnt[b] * img_elems;
+            for (int j = 0; j < n; ++j, at += blk) {
+                if (on_dev) HIPCHK(hipMemcpyAsync(dst + at, src[k] + first, blk * 4, hipMemcpyDeviceToDevice, m->st));
+                else std::copy(src[k] + first, src[k] + first + blk, dst + at);
+            }
+            first += blk;
+        }
+        if (!m->img_counts[k].empty()) {
+            std::vector<int> cx;
+            for (int b = 0; b < B; ++b) cx.insert(cx.end(), n, cnt[b]);
+            m->img_counts[k].swap(cx);
+        }
+        px[k] = dst;
+    }
+    m->cur_pos = -1;
+    int S = 0;
+    std::unique_lock<std::mutex> gate(g_prefill_gate);
+    do_prefill(m, ids_x.data(), R, T, px[0], px[1], px[2], on_dev, 1, max_new, true, &S);
+    m->last_S = S;
+    REQUIRE(S + max_new <= m->capS, VC_ERR_INVALID, "prompt %d + max_new %d exceeds the KV capacity %d", S, max_new, m->capS);
+    finish_prefill(m, session_kv(m), nullptr);
+    m->kmask_in_decode = false;   // generate(): the cached steps run under an all-ones mask (vcoder_ds_llava_arch.py:130-133)
+    ensure_beam(m, R, max_new);
+    // the tail permute cuts a tail at the span its grid and staging are sized for: the whole call must fit (it does: cap_new >= max_new)
+    REQUIRE(max_new <= m->bm_cap_new && m->bm_tmp.cap >= (size_t)2 * R * c.heads * beam_span_cap(m, m->bm_cap_new), VC_ERR_STATE,
+            "beam buffers hold %d steps, the call asks for %d", m->bm_cap_new, max_new);
+    if (m->ev[2]) HIPCHK(hipEventRecord(m->ev[2], m->st));
+    GenParams none;   // nothing is recorded in out_ids, no EOS bookkeeping in the records: the beam kernel keeps its own
+    arm_session_rows(m, none, nullptr);
+    const LoopView v = session_view(m);
+    const BeamLoop bl = beam_view(m, B, n);
+    // the state of step 0: beam 0 of every sequence alive, the others at -1e9 (HF: beam_scores[:, 1:] = -1e9), no hypotheses
+    int* const base = m->bm_state.as<int>();
+    std::vector<int> st(BEAM_STATE_INTS, 0);
+    auto at = [&](const void* p) { return st.data() + (reinterpret_cast<const int*>(p) - base); };
+    const float worst0 = 1e9f;
+    for (int r = 0; r < R; ++r) {
+        const float s0 = r % n ? -1e9f : 0.f;
+        memcpy(at(bl.score) + r, &s0, 4);
+        at(bl.perm)[r] = r;
+        at(bl.start)[r] = S;
+    }
+    for (int b = 0; b < B; ++b) memcpy(at(bl.seq) + b * BQ_STRIDE + BQ_WORST, &worst0, 4);
+    int* prm = at(bl.params);
+    prm[BP_N_EOS] = q.n_eos;
+    prm[BP_PAD] = q.pad >= 0 ? q.pad : 0;
+    prm[BP_EARLY] = q.early;
+    prm[BP_MAXNEW] = max_new;
+    for (int e = 0; e < q.n_eos; ++e) prm[BP_EOS + e] = q.eos[e];
+    // the two denominator tables (no powf on the device): hypothesis length -> length ** length_penalty, in double as the host loop
+    auto hyp_len = [&](int len) { return q.len_counts_prompt ? len : len - T; };
+    auto den_of = [&](int hl) { return (float)std::pow((double)std::max(hl, 1), (double)q.length_penalty); };
+    std::vector<float> den((size_t)2 * (bl.cap_new + 1), 1.f);
+    for (int s_ = 0; s_ <= max_new; ++s_) {
+        den[s_] = den_of(hyp_len(T + s_));
+        den[bl.cap_new + 1 + s_] = q.early == 2 && q.length_penalty > 0.f ? den_of(hyp_len(T + max_new)) : den[s_];
+    }
+    HIPCHK(hipMemcpyAsync(base, st.data(), st.size() * 4, hipMemcpyHostToDevice, m->st));
+    HIPCHK(hipMemcpyAsync(m->bm_den.p, den.data(), den.size() * 4, hipMemcpyHostToDevice, m->st));
+    enqueue_beam_tail(m, v, bl, v.logits, 1, false);   // step 0 -> 1 on the prefill logits; the position stays at S
+    HIPCHK(hipStreamSynchronize(m->st));   // (`st`, `den` are host memory)
+    gate.unlock();
+    int fl[2] = {0, 0};
+    auto poll = [&]() {
+        HIPCHK(hipMemcpyAsync(fl, bl.flags, 8, hipMemcpyDeviceToHost, m->st));
+        HIPCHK(hipStreamSynchronize(m->st));
+        return fl[0] || fl[1];
+    };
+    int produced = 1;
+    if (!poll() && max_new > 1) {
+        const hipGraphExec_t step_graph = ensure_beam_graph(m, B, n);
+        for (int step = 1; step < max_new; ++step) {
+            HIPCHK(hipGraphLaunch(step_graph, m->st));
+            m->cur_pos += 1;
+            produced = step + 1;
+            // a done sequence emits pad and changes nothing: polling every few steps only ends the loop later
+            if (((step + 1) % 8 == 0 || step == max_new - 1) && poll()) break;
+        }
+    }
+    if (m->ev[3]) HIPCHK(hipEventRecord(m->ev[3], m->st));
+    std::vector<int> tok((size_t)produced * R), par((size_t)produced * R);
+    HIPCHK(hipMemcpyAsync(st.data(), base, st.size() * 4, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipMemcpyAsync(tok.data(), bl.tok_tab, tok.size() * 4, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipMemcpyAsync(par.data(), bl.parent_tab, par.size() * 4, hipMemcpyDeviceToHost, m->st));
+    HIPCHK(hipStreamSynchronize(m->st));
+    REQUIRE(!at(bl.flags)[1], VC_ERR_INVALID, "At most %d tokens among the %d best continuations of a sequence can be equal to `eos_token_id: %d`.",
+            n, 2 * n, q.n_eos ? q.eos[0] : -1);
+    // steps the host loop would have run: up to the step that finished the last sequence, or all of them
+    bool all_done = true;
+    int steps = 0;
+    for (int b = 0; b < B; ++b) {
+        all_done = all_done && at(bl.seq)[b * BQ_STRIDE + BQ_DONE];
+        steps = std::max(steps, at(bl.seq)[b * BQ_STRIDE + BQ_DONE_STEP] + 1);
+    }
+    if (!all_done) steps = produced;
+    if (n_steps) *n_steps = steps;
+    // finalize: open beams of unfinished sequences become hypotheses, the best one (the first of equals) is returned
+    std::vector<std::vector<int>> best_ids(B);
+    int L = 0;
+    for (int b = 0; b < B; ++b) {
+        const int* sq = at(bl.seq) + b * BQ_STRIDE;
+        std::vector<BeamHypHost> list;
+        for (int j = 0; j < sq[BQ_NHYP]; ++j) {
+            const int* h = at(bl.hyp) + ((size_t)b * n + j) * BH_STRIDE;
+            BeamHypHost e;
+            memcpy(&e.score, h + BH_SCORE, 4);
+            memcpy(&e.sum, h + BH_SUM, 4);
+            e.step = h[BH_STEP];
+            e.row = h[BH_ROW];
+            list.push_back(e);
+        }
+        float worst;
+        memcpy(&worst, sq + BQ_WORST, 4);
+        if (!sq[BQ_DONE])
+            for (int j = 0; j < n; ++j) {
+                float sum;
+                memcpy(&sum, at(bl.score) + b * n + j, 4);
+                beam_add_hyp(list, worst, n, sum, den[steps], steps, b * n + j);
+            }
+        size_t bi = 0;
+        for (size_t j = 1; j < list.size(); ++j)
+            if (list[j].score > list[bi].score) bi = j;
+        const BeamHypHost& h = list[bi];
+        REQUIRE(h.step >= 0 && h.step <= produced && h.row >= 0 && h.row < R, VC_ERR_STATE, "beam hypothesis (%d, %d) outside the tables",
+                h.step, h.row);
+        std::vector<int>& out = best_ids[b];
+        out.resize(h.step);
+        for (int s_ = h.step - 1, r = h.row; s_ >= 0; --s_) {   // back-pointers: the token of row r at step s_, then its parent
+            out[s_] = tok[(size_t)s_ * R + r];
+            r = par[(size_t)s_ * R + r];
+        }
+        out_len[b] = h.step;
+        out_score[b] = h.score;
+        L = std::max(L, h.step);
+    }
+    const int L_out = std::min(L + 1, max_new);   // BeamSearchScorer.finalize: room for the EOS a finished hypothesis does not carry
+    for (int b = 0; b < B; ++b)
+        REQUIRE((int)best_ids[b].size() >= L_out || q.pad >= 0, VC_ERR_INVALID, "`pad_token_id` has to be defined");
+    for (int b = 0; b < B; ++b) {
+        int32_t* row = out_ids + (size_t)b * max_new;
+        std::fill(row, row + max_new, q.pad >= 0 ? q.pad : 0);
+        std::copy(best_ids[b].begin(), best_ids[b].end(), row);
+        if ((int)best_ids[b].size() < L_out && q.n_eos > 0) row[best_ids[b].size()] = q.eos[0];
+    }
+    if (m->ev[0]) {
+        (void)hipEventElapsedTime(&m->t_encode, m->ev[0], m->ev[1]);
+        (void)hipEventElapsedTime(&m->t_prefill, m->ev[1], m->ev[2]);
+        (void)hipEventElapsedTime(&m->t_decode, m->ev[2], m->ev[3]);
+    }
+}
+
 }  // namespace
 
 /* generate(): encode + splice + prefill + (max_new - 1) decode steps with the token selection on the device — greedy
@@ -751,6 +971,44 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
     else
         generate_on_session(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids,
                             n_generated);
+    GUARD_END(m->ctx)
+}
+
+/* generate(num_beams = n) inside the device loop: every sequence expanded to n rows, one captured beam step per token (top 2 n
+ * log-probs per row, the selection / hypothesis bookkeeping kernel, the tail-only cache permute, the embedding), HF's
+ * BeamSearchScorer.finalize on the host.  See include/vcoder_hip.h. */
+VC_API int vc_generate_beam(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
+                            int pixels_on_device, int num_beams, int max_new, const int32_t* eos_ids, int n_eos, int pad_id,
+                            float length_penalty, int early_stopping, int len_counts_prompt, int32_t* out_ids, int32_t* out_len,
+                            float* out_score, int* n_steps) {
+    if (!m) return VC_ERR_INVALID;
+    OneShotReset one_shot{m};
+    GUARD_BEGIN
+    USE_DEVICE(m->ctx);
+    // every refusal comes before anything of the session is touched
+    REQUIRE(ids && B >= 1 && T >= 1 && max_new >= 1 && out_ids && out_len && out_score, VC_ERR_INVALID, "bad ids / B / T / max_new / outputs");
+    REQUIRE(num_beams >= 1, VC_ERR_INVALID, "num_beams must be at least 1 (got %d)", num_beams);
+    REQUIRE((long long)B * num_beams <= VC_BEAM_MAX_ROWS, VC_ERR_INVALID, "batch %d x num_beams %d exceeds the %d rows a replica decodes at a time",
+            B, num_beams, VC_BEAM_MAX_ROWS);
+    REQUIRE(n_eos >= 0 && n_eos <= VC_BEAM_MAX_EOS && (n_eos == 0 || eos_ids), VC_ERR_INVALID, "at most %d EOS ids", VC_BEAM_MAX_EOS);
+    REQUIRE(early_stopping >= 0 && early_stopping <= 2, VC_ERR_INVALID, "early_stopping: 0 (false), 1 (true) or 2 (\"never\")");
+    REQUIRE(pad_id < m->c.vocab, VC_ERR_INDEX, "pad_token_id %d is outside the vocabulary (%d)", pad_id, m->c.vocab);
+    REQUIRE(m->precision != 1, VC_ERR_STATE, "strict mode keeps beam search on the host loop (vc_decode_step + vc_reorder_cache)");
+    REQUIRE(!m->glp_tok, VC_ERR_STATE, "per-token log-probs are not implemented for beam search: a vc_request_generate_logprobs is pending");
+    {   // the tail permute moves 16-byte chunks of a cache row: the element size the prefill below will give the session's cache
+        const int es = m->precision == 2 ? split_kv_es() : step_kv_es(m);
+        REQUIRE((m->hd * es) % 16 == 0, VC_ERR_STATE, "the tail permute moves 16-byte chunks: head_dim %d x %d bytes", m->hd, es);
+    }
+    BeamCall q;
+    q.n = num_beams;
+    q.max_new = max_new;
+    q.n_eos = n_eos;
+    for (int e = 0; e < n_eos; ++e) q.eos[e] = eos_ids[e];
+    q.pad = pad_id;
+    q.early = early_stopping;
+    q.len_counts_prompt = len_counts_prompt != 0;
+    q.length_penalty = length_penalty;
+    generate_beam_on_session(m, ids, B, T, img, seg, depth, pixels_on_device, q, out_ids, out_len, out_score, n_steps);
     GUARD_END(m->ctx)
 }
 

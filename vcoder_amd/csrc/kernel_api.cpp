@@ -96,6 +96,18 @@ VCK_EXPORT void vck_topk_logprob(const float* logits, int ldl, const int* chosen
     TopkLogprobArgs a{logits, ldl, chosen, chosen_lp, top_lp, top_ids, V, K, nullptr, nullptr, 0};
     launch_topk_logprob(a, rows, lds_floats, S(stream));
 }
+VCK_EXPORT void vck_beam_step(const float* cand_lp, const int* cand_id, float* beam_score, int* rows, int* next_tok, int* perm,
+                              int* tok_tab, int* parent_tab, int* seq, int* hyp, const float* hyp_den, const float* done_den,
+                              const int* params, int* flags, int B, int n, int advance, void* stream) {
+    BeamStepArgs a{cand_lp, cand_id, beam_score, rows, next_tok, perm, tok_tab, parent_tab, seq, hyp, hyp_den, done_den, params, flags,
+                   B, n, advance};
+    launch_beam_step(a, S(stream));
+}
+VCK_EXPORT void vck_kv_permute_tail(void* kcache, void* vcache, void* tmp, const int* perm, const int* start, const int* rows, int R,
+                                    int H, int cap_positions, int pos_bytes, int span_positions, void* stream) {
+    launch_kv_permute_tail(kcache, vcache, tmp, perm, start, rows, R, H, (size_t)cap_positions * pos_bytes, pos_bytes,
+                           (size_t)span_positions * pos_bytes, S(stream));
+}
 VCK_EXPORT void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w,
                                      uint16_t* xg, int B, int D, int npart, void* stream) {
     launch_embed_tokens_ssq(tok, embed, x, ssq, xg_w, xg, B, D, npart, S(stream));

@@ -428,6 +428,47 @@ struct TopkLogprobArgs {
 };
 // lds_floats < 0: stage the row in LDS when the device allows; 0 (or < V): every pass re-reads the row from global memory
 void launch_topk_logprob(const TopkLogprobArgs& a, int nrows, int lds_floats, hipStream_t s);
+// one beam-search step of B sequences of n beams each (rows b * n .. b * n + n - 1; R = B * n <= 16) behind a launch_topk_logprob
+// with K = 2 n into cand_lp / cand_id [R, 2 n] (select.hip beam_step_kernel): what one iteration of HF's beam_search does between
+// `topk` and `_reorder_cache` — the 2 n best of a sequence's n * 2 n candidates (score = lp + beam_score[row], one fp32 add; ordered
+// by score descending, then (row, id) ascending; id -1 entries are no candidates), BeamSearchScorer.process over them (an EOS at
+// rank < n adds a hypothesis, at rank >= n is skipped, anything else fills the next beam slot), the hypothesis list (at most n, the
+// worst evicted, insertion order kept) and the `done` decision of the early_stopping mode.  Hypotheses are back-pointers
+// (score, sum, step, source row); the ids of a beam or hypothesis are rebuilt from tok_tab / parent_tab [step][R].
+enum BeamSeq {        // per-sequence record
+    BQ_DONE = 0,      // the sequence is done: its rows emit pad, keep their parents and ignore their logits
+    BQ_NHYP = 1,      // hypotheses held (<= n)
+    BQ_WORST = 2,     // float bits: the lowest hypothesis score (1e9 while none is held)
+    BQ_DONE_STEP = 3, // the step at which BQ_DONE was set
+    BQ_STRIDE = 4,
+};
+enum BeamParam {      // per-call parameters, in device memory so that one captured step serves every call
+    BP_N_EOS = 0,     // ids in BP_EOS (<= VC_BEAM_MAX_EOS)
+    BP_PAD = 1,       // what the rows of a done sequence emit (a vocabulary id)
+    BP_EARLY = 2,     // early_stopping: 0 false, 1 true, 2 "never"
+    BP_MAXNEW = 3,    // steps of the call: rows of tok_tab / parent_tab and entries of hyp_den / done_den that may be touched
+    BP_EOS = 4,
+    BP_STRIDE = 12,
+};
+constexpr int VC_BEAM_MAX_EOS = 8, VC_BEAM_MAX_ROWS = 16;
+enum BeamHyp { BH_SCORE = 0, BH_SUM = 1, BH_STEP = 2, BH_ROW = 3, BH_STRIDE = 4 };   // score / sum: float bits
+struct BeamStepArgs {
+    const float* cand_lp;    // [R, 2 n]
+    const int* cand_id;      // [R, 2 n]
+    float* beam_score;       // [R] in / out
+    int* rows;               // [R][RS_STRIDE]: RS_STEP is the step; RS_STEP / RS_POS advance as SelectArgs::advance says
+    int* next_tok;           // [R] out
+    int* perm;               // [R] out: the source row of every row (the cache permutation)
+    int *tok_tab, *parent_tab;   // [BP_MAXNEW][R]: row `step` is written
+    int* seq;                // [B][BQ_STRIDE]
+    int* hyp;                // [B][n][BH_STRIDE]
+    const float* hyp_den;    // [BP_MAXNEW]: max(hyp_len, 1) ** length_penalty of a hypothesis added at that step
+    const float* done_den;   // [BP_MAXNEW]: the denominator of is_done at that step
+    const int* params;       // [BP_STRIDE]
+    int* flags;              // [0] = every sequence done (written each step), [1] = set when fewer than n beam slots could be filled
+    int B, n, advance;
+};
+void launch_beam_step(const BeamStepArgs& a, hipStream_t s);
 // test hook: u[i] = the sampler's uniform for hash value h[i], gumbel[i] = -log(-log(u[i]))
 void launch_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, hipStream_t s);
 
@@ -517,6 +558,12 @@ void launch_row_sum(const float* x, size_t n_per_row, int rows, float* out, hipS
 // rows of one layer's K or V cache permuted in place through `tmp`: row r <- old row perm[r], live prefix only (beam search)
 void launch_kv_permute(void* cache, void* tmp, const int* perm, int rows, int H, size_t cap_row_bytes, size_t live_row_bytes,
                        hipStream_t s);
+// the same permutation driven from device memory, positions [start[r], rows[r][RS_POS]) only (the device beam loop: the beams of a
+// sequence are copies of one prompt row, so the prompt part needs no copy): K and V of one layer in one launch pair.  pos_bytes =
+// hd * element size; tmp holds [2][R][H][span_cap] bytes, span_cap = the longest tail the grid and tmp are sized for (a longer one is
+// cut there); rows whose perm is themselves, or outside [0, R), are left alone.
+void launch_kv_permute_tail(void* kcache, void* vcache, void* tmp, const int* perm, const int* start, const int* rows, int R, int H,
+                            size_t cap_row_bytes, int pos_bytes, size_t span_cap, hipStream_t s);
 void launch_f32_to_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 // hi = bf16(in), lo = bf16(in - hi) (nullptr: skipped), *inexact = 1 if any in != hi (checkpoints bf16 cannot hold: the weight lo
 // planes of the strict / split precision modes)

@@ -5,6 +5,8 @@
 //   embed_tokens  : decode-step embedding lookup ([HF] llama/modeling_llama.py:377)                        K10
 //   greedy        : fp32 argmax, lowest index on ties, EOS -> pad bookkeeping
 //                   ([HF] generation/utils.py:2894,2925-2929)                        K19
+//   kv_permute    : KV rows reordered by beam_idx ([HF] _reorder_cache): the whole live prefix from host arguments
+//                   (vc_reorder_cache), or the tail behind the prompt from device memory (the device beam loop)
 #include "vc_device.h"
 #include "kernels.h"
 
@@ -204,6 +206,40 @@ void launch_kv_permute(void* cache, void* tmp, const int* perm, int rows, int H,
               cap_row_bytes, live_row_bytes, 0);
     VC_LAUNCH(kv_permute_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<char*>(cache), reinterpret_cast<char*>(tmp), perm, rows, H,
               cap_row_bytes, live_row_bytes, 1);
+}
+
+// The same permutation for the device beam loop: perm, the first position to copy and the live end come from device memory, so the
+// launch pair sits in a captured graph.  Workgroups (x, row * H + head, K | V) walk the 16-byte chunks of positions
+// [start[r], rows[r][RS_POS]) of their (row, head); a row that keeps itself costs its workgroups one read of perm.  A tail longer
+// than span_cap is cut there (the staging holds no more): the engine sizes span_cap for the call's max_new and refuses a call that
+// would not fit (generate_beam_on_session), so a step never reaches the cut.
+__global__ __launch_bounds__(256) void kv_permute_tail_kernel(char* kcache, char* vcache, char* tmp, const int* perm, const int* start,
+                                                              const int* rows, int R, int H, size_t cap_row_bytes, int pos_bytes,
+                                                              size_t span_cap, int phase) {
+    const int rh = blockIdx.y, r = rh / H;
+    const int src = perm[r];
+    if (src == r || (unsigned)src >= (unsigned)R) return;
+    const int s0 = start[r], s1 = rows[(size_t)r * RS_STRIDE + RS_POS];
+    if (s0 < 0 || s1 <= s0 || (size_t)s1 * pos_bytes > cap_row_bytes) return;
+    const size_t span = min((size_t)(s1 - s0) * pos_bytes, span_cap);
+    const size_t off = (size_t)s0 * pos_bytes;
+    char* cache = blockIdx.z ? vcache : kcache;
+    char* t = tmp + ((size_t)blockIdx.z * R * H + rh) * span_cap;
+    char* own = cache + (size_t)rh * cap_row_bytes + off;
+    const char* from = cache + ((size_t)src * H + rh % H) * cap_row_bytes + off;
+    for (size_t c = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16; c + 16 <= span; c += (size_t)gridDim.x * 256 * 16) {
+        if (phase == 0) st16(t + c, ld16(from + c));
+        else st16(own + c, ld16(t + c));
+    }
+}
+void launch_kv_permute_tail(void* kcache, void* vcache, void* tmp, const int* perm, const int* start, const int* rows, int R, int H,
+                            size_t cap_row_bytes, int pos_bytes, size_t span_cap, hipStream_t s) {
+    if (R <= 0 || H <= 0 || span_cap < 16) return;
+    const unsigned gx = (unsigned)min((size_t)4, (span_cap / 16 + 255) / 256);
+    for (int phase = 0; phase < 2; ++phase)
+        VC_LAUNCH(kv_permute_tail_kernel, dim3(gx, (unsigned)(R * H), 2), dim3(256), 0, s, reinterpret_cast<char*>(kcache),
+                  reinterpret_cast<char*>(vcache), reinterpret_cast<char*>(tmp), perm, start, rows, R, H, cap_row_bytes, pos_bytes,
+                  span_cap, phase);
 }
 
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* in, bf16_t* out, size_t n) {

@@ -8,6 +8,7 @@
 //   finished rows emit pad, EOS finishes a row                [HF] generation/utils.py:2928-2929
 //   keyword stop: suffix match of the row's ids               vcoder_llava/mm_utils.py:128-151 (KeywordsStoppingCriteria)
 //   embedding of the chosen token                             [HF] llama/modeling_llama.py:377
+//   beam search: candidates, process, hypotheses, done        [HF] generation/utils.py beam_search, beam_search.py (4.31)
 //
 // Everything a row needs lives in its RowState record in device memory (kernels.h: RS_*), so ONE captured hipGraph serves
 // every step of every request: rows of different requests (different prompt lengths, step counts, sampling parameters,
@@ -647,6 +648,126 @@ void launch_topk_logprob(const TopkLogprobArgs& a0, int nrows, int lds_floats, h
     }
 #endif
     VC_LAUNCH(topk_logprob_kernel, dim3((unsigned)nrows), dim3(TOPK_THREADS), lds, s, a);
+}
+
+// ---- one beam-search step on the device (kernels.h BeamStepArgs; [HF] generation/utils.py beam_search + beam_search.py
+// BeamSearchScorer.process of Transformers 4.31) -----------------------------------------------------------------------------------
+// ONE workgroup, one wave per sequence (B * n <= 16 rows, so the launch holds at most 16 * 32 = 512 candidates): the lanes add
+// the running beam score to the candidates and rank them by counting (score descending, then (row, id) ascending — the flat index
+// beam * V + id, the argmax's tie rule; a score the -1e9 of an unborn beam swallowed ties with its neighbours), lane 0 then walks
+// the 2 n best in rank order exactly as the host loop does.  All arithmetic is one fp32 add and fp32 divisions by tabulated
+// denominators: a numpy float32 restatement reproduces every bit.  Clarity over occupancy: a few hundred candidates per step.
+VC_DEV bool beam_before(float s, int row, int id, float os, int orow, int oid) {   // (os, orow, oid) ranks in front of (s, row, id)
+    return os > s || (os == s && (orow < row || (orow == row && oid < id)));
+}
+__global__ __launch_bounds__(1024) void beam_step_kernel(BeamStepArgs p) {
+    constexpr int MAXC = VC_BEAM_MAX_ROWS * VC_MAX_TOP_LOGPROBS;
+    __shared__ float c_s[MAXC];
+    __shared__ int c_i[MAXC];
+    __shared__ int top_c[2 * VC_BEAM_MAX_ROWS];   // per sequence: candidate index by rank, -1 behind the last candidate
+    const int tid = threadIdx.x, lane = tid & 63, b = tid >> 6;
+    const int n = p.n, K = 2 * n, nc = n * K, R = p.B * n, base = b * nc;
+    for (int c = lane; c < nc; c += 64) {
+        const int id = p.cand_id[base + c];
+        c_i[base + c] = id;
+        c_s[base + c] = id >= 0 ? p.cand_lp[base + c] + p.beam_score[b * n + c / K] : -INFINITY;
+    }
+    if (lane < K) top_c[b * K + lane] = -1;
+    __syncthreads();
+    for (int c = lane; c < nc; c += 64) {
+        const int id = c_i[base + c];
+        if (id < 0) continue;
+        const float s = c_s[base + c];
+        int rank = 0;
+        for (int o = 0; o < nc; ++o) {
+            const int oid = c_i[base + o];
+            rank += oid >= 0 && beam_before(s, c / K, id, c_s[base + o], o / K, oid);
+        }
+        if (rank < K) top_c[b * K + rank] = c;
+    }
+    __syncthreads();
+    if (lane == 0) {
+        int* sq = p.seq + b * BQ_STRIDE;
+        int* hyp = p.hyp + (size_t)b * n * BH_STRIDE;
+        const int step = p.rows[(size_t)b * n * RS_STRIDE + RS_STEP];
+        const bool live = step >= 0 && step < p.params[BP_MAXNEW] && !sq[BQ_DONE];
+        const int pad = p.params[BP_PAD];
+        int k = 0;
+        auto emit = [&](float score, int tok, int src) {   // beam slot k of the sequence
+            const int r = b * n + k;
+            p.beam_score[r] = score;
+            p.next_tok[r] = tok;
+            p.perm[r] = src;
+            if (step >= 0 && step < p.params[BP_MAXNEW]) {
+                p.tok_tab[(size_t)step * R + r] = tok;
+                p.parent_tab[(size_t)step * R + r] = src;
+            }
+            ++k;
+        };
+        if (live) {
+            const int n_eos = p.params[BP_N_EOS];
+            for (int rank = 0; rank < K && k < n; ++rank) {
+                const int c = top_c[b * K + rank];
+                if (c < 0) break;
+                const int id = c_i[base + c], src = b * n + c / K;
+                const float sum = c_s[base + c];
+                bool is_eos = false;
+                for (int e = 0; e < n_eos; ++e) is_eos = is_eos || id == p.params[BP_EOS + e];
+                if (!is_eos) {
+                    emit(sum, id, src);
+                    continue;
+                }
+                if (rank >= n) continue;
+                // BeamHypotheses.add: kept while fewer than n are held or it beats the worst; the worst (the first of equals) leaves
+                const float score = sum / p.hyp_den[step];
+                int nh = sq[BQ_NHYP];
+                float worst = __builtin_bit_cast(float, sq[BQ_WORST]);
+                if (nh >= n && !(score > worst)) continue;
+                if (nh >= n) {
+                    int lo = 0;
+                    for (int j = 1; j < nh; ++j)
+                        if (__builtin_bit_cast(float, hyp[j * BH_STRIDE + BH_SCORE]) < __builtin_bit_cast(float, hyp[lo * BH_STRIDE + BH_SCORE])) lo = j;
+                    for (int j = lo; j + 1 < nh; ++j)
+                        for (int q = 0; q < BH_STRIDE; ++q) hyp[j * BH_STRIDE + q] = hyp[(j + 1) * BH_STRIDE + q];
+                    --nh;
+                }
+                hyp[nh * BH_STRIDE + BH_SCORE] = __builtin_bit_cast(int, score);
+                hyp[nh * BH_STRIDE + BH_SUM] = __builtin_bit_cast(int, sum);
+                hyp[nh * BH_STRIDE + BH_STEP] = step;
+                hyp[nh * BH_STRIDE + BH_ROW] = src;
+                ++nh;
+                worst = score;
+                for (int j = 0; j < nh; ++j) worst = fminf(worst, __builtin_bit_cast(float, hyp[j * BH_STRIDE + BH_SCORE]));
+                sq[BQ_NHYP] = nh;
+                sq[BQ_WORST] = __builtin_bit_cast(int, worst);
+            }
+            if (k < n) p.flags[1] = 1;   // more than n EOS among the 2 n best (or too few candidates): the host raises
+            // BeamHypotheses.is_done against the best candidate of the step
+            const int c0 = top_c[b * K];
+            const float best = c0 >= 0 ? c_s[base + c0] : -INFINITY;
+            const int early = p.params[BP_EARLY];
+            if (sq[BQ_NHYP] >= n && (early == 1 || __builtin_bit_cast(float, sq[BQ_WORST]) >= best / p.done_den[step])) {
+                sq[BQ_DONE] = 1;
+                sq[BQ_DONE_STEP] = step;
+            }
+        }
+        while (k < n) emit(0.f, pad, b * n + k);   // a done sequence (and the slots an error left open): pad, its own row
+        for (int j = 0; j < n; ++j) {
+            int* rs = p.rows + (size_t)(b * n + j) * RS_STRIDE;
+            if (p.advance & 1) rs[RS_STEP] = step + 1;
+            if (p.advance & 2) rs[RS_POS] += 1;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int all = 1;
+        for (int q = 0; q < p.B; ++q) all = all && p.seq[q * BQ_STRIDE + BQ_DONE];
+        p.flags[0] = all;
+    }
+}
+void launch_beam_step(const BeamStepArgs& a, hipStream_t s) {
+    if (a.B < 1 || a.n < 1 || a.B * a.n > VC_BEAM_MAX_ROWS) return;   // nothing is launched, nothing written
+    VC_LAUNCH(beam_step_kernel, dim3(1), dim3(64 * a.B), 0, s, a);
 }
 
 // embedding + sum-of-squares partials for tokens supplied by the host (vc_decode_step with explicit tokens)

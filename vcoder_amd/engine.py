@@ -149,7 +149,11 @@ class HipEngine:
         """'bf16' (default: bf16 MFMA operands, what the benchmark runs); 'strict' (fp32 activations on fp32 MFMA —
         fp32-faithful to the reference's CPU path, slow); 'split' (fp32 activations in HBM, every MFMA operand as bf16 hi + lo
         fragments on the FAST kernels: the same 1e-3 / bit-exact-ids bar at about half the fast path's MFMA rate)."""
-        self._check(self.lib.vc_model_set_precision(self._model, {"bf16": 0, "fast": 0, "strict": 1, "fp32": 1, "split": 2}[mode]))
+        code = {"bf16": 0, "fast": 0, "strict": 1, "fp32": 1, "split": 2}[mode]
+        self._check(self.lib.vc_model_set_precision(self._model, code))
+        self.precision = ("bf16", "strict", "split")[code]
+
+    precision = "bf16"   # the session's precision mode (a new session starts in "bf16")
 
     def set_weight_format(self, fmt: str):
         """'bf16' (default); 'w8a16': decoder linears as e4m3 + per-row power-of-two scales, quantised at finalize and
@@ -666,6 +670,38 @@ class HipEngine:
             self.last_generate_logprobs = (tok_lp.reshape(B, mn)[:, : n.value].copy(), top_lp.reshape(B, mn, K)[:, : n.value].copy(),
                                            top_id.reshape(B, mn, K)[:, : n.value].copy())
         return out[:, : n.value].copy()
+
+    def generate_beam(self, input_ids, images, segs=None, depths=None, num_beams: int = 2, max_new_tokens: int = 128,
+                      eos_token_id=None, pad_token_id: Optional[int] = None, length_penalty: float = 1.0, early_stopping=False,
+                      len_counts_prompt: bool = True, attention_mask=None):
+        """Beam search inside the device loop (vc_generate_beam): input_ids [B, T] un-expanded, B * num_beams <= MAX_BATCH.
+        eos_token_id: an id, a list of up to 8, or None; early_stopping: False / True / "never" (HF).  -> (ids [B, L] int32: the best
+        hypothesis of every sequence, one EOS behind a shorter one, pad elsewhere; lengths [B]; scores [B] float32 —
+        sum_logprobs / len ** length_penalty of the winner).  last_beam_steps = the steps the loop ran."""
+        ids = self._ids(input_ids)
+        B, T = ids.shape
+        eos = [] if eos_token_id is None else [int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id])]
+        eos = np.ascontiguousarray([e for e in eos if e >= 0], dtype=np.int32)
+        early = {False: 0, True: 1, "never": 2}.get(early_stopping)
+        if early is None:
+            raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
+        mn = int(max_new_tokens)
+        (pi, ps, pd), on_dev, keep = self._pixels(*self._image_blocks(B, images, segs, depths))
+        out = np.empty((B, max(mn, 1)), dtype=np.int32)
+        lens = np.zeros((B,), dtype=np.int32)
+        score = np.zeros((B,), dtype=np.float32)
+        n = C.c_int(0)
+        self._announce_mask(attention_mask, B, T)   # last: nothing between it and the call can raise and leave it armed
+        self._check(self.lib.vc_generate_beam(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev, int(num_beams), mn,
+                                              eos.ctypes.data_as(C.c_void_p) if eos.size else None, int(eos.size),
+                                              -1 if pad_token_id is None else int(pad_token_id), float(length_penalty), early,
+                                              int(bool(len_counts_prompt)), out.ctypes.data_as(C.c_void_p),
+                                              lens.ctypes.data_as(C.c_void_p), score.ctypes.data_as(C.c_void_p), C.byref(n)))
+        self._cur_batch = B * int(num_beams)
+        self.last_beam_steps = n.value
+        return out[:, : min(int(lens.max()) + 1, mn)].copy(), lens, score
+
+    last_beam_steps = 0
 
     # bookkeeping used by decode_step
     def note_prefill(self, B: int):

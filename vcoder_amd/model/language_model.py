@@ -72,17 +72,19 @@ class GenerateOutput(dict):
     out[0] = sequences.  sequences: the tensor generate() returns otherwise.  token_logprobs [B, n] float32: log p(generated token);
     top_logprobs [B, n, K] float32 / top_token_ids [B, n, K] int64: the K most likely tokens of every step, ordered by (log-prob
     descending, id ascending); sequence_logprob [B]: row sums of token_logprobs.  n = generated columns.  A row's finishing token is
-    scored; positions behind it hold 0.0 / 0.0 / -1.  Fields that were not requested are None."""
+    scored; positions behind it hold 0.0 / 0.0 / -1.  sequences_scores [B] float32 (num_beams != 1; HF's name): the winning
+    hypothesis' sum_logprobs / len ** length_penalty.  Fields that were not requested are None."""
 
-    def __init__(self, sequences=None, token_logprobs=None, top_logprobs=None, top_token_ids=None, sequence_logprob=None):
+    def __init__(self, sequences=None, token_logprobs=None, top_logprobs=None, top_token_ids=None, sequence_logprob=None,
+                 sequences_scores=None):
         super().__init__(sequences=sequences, token_logprobs=token_logprobs, top_logprobs=top_logprobs,
-                         top_token_ids=top_token_ids, sequence_logprob=sequence_logprob)
+                         top_token_ids=top_token_ids, sequence_logprob=sequence_logprob, sequences_scores=sequences_scores)
         self.__dict__ = self
 
     def __getitem__(self, k):
         if isinstance(k, int):
-            return [v for v in (self.sequences, self.token_logprobs, self.top_logprobs, self.top_token_ids, self.sequence_logprob)
-                    if v is not None][k]
+            return [v for v in (self.sequences, self.token_logprobs, self.top_logprobs, self.top_token_ids, self.sequence_logprob,
+                                self.sequences_scores) if v is not None][k]
         return dict.__getitem__(self, k)
 
 
@@ -460,6 +462,12 @@ class _HipCausalLMBase:
         the host fallback loop computes the same from its logits.  HF's full-vocabulary `output_scores` is not implemented: with
         return_dict_in_generate it raises, alone it is ignored as before.
 
+        num_beams = n > 1: beam search (HF 4.31's beam_search + BeamSearchScorer; `length_penalty`, `early_stopping` as keyword
+        arguments).  Without sampling and stopping criteria, outside strict mode and with B * n <= 16 rows it runs inside the device
+        loop too (vc_generate_beam: one captured beam step per token, fp32 scores, ties by the lower flat index beam * V + id);
+        beam-sample, stopping criteria and strict mode — or beam_on_device=False — take the host loop `_beam_search`.  Both return
+        the same tensor; with return_dict_in_generate the GenerateOutput carries `sequences_scores` [B].
+
         Everything the reference's callers ask for runs on the device inside the hipGraph-replayed decode loop
         (vc_generate): greedy argmax; sampling with HF's warper order temperature -> top-k -> top-p -> multinomial
         (`top_k` defaults to 50 when sampling, HF's GenerationConfig default, which is what serve/cli.py:122-132 gets);
@@ -494,11 +502,19 @@ class _HipCausalLMBase:
                     generator = torch.Generator().manual_seed(int(seed if seed is not None else torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF)
                 sample = dict(temperature=float(temperature or 1.0), top_k=50 if top_k is None else int(top_k),
                               top_p=1.0 if top_p is None else float(top_p), generator=generator)
-            seqs = self._beam_search(input_ids, images, segs, depths, int(num_beams), max_new_tokens, max_length, eos_token_id,
-                                     pad_token_id, attention_mask, stopping_criteria,
-                                     float(kwargs.get("length_penalty", 1.0)), kwargs.get("early_stopping", False),
-                                     kwargs.get("_beam_len_counts_prompt", True), sample)
-            return GenerateOutput(sequences=seqs) if as_dict else seqs
+            beam_args = (input_ids, images, segs, depths, int(num_beams), max_new_tokens, max_length, eos_token_id, pad_token_id,
+                         attention_mask)
+            beam_kw = (float(kwargs.get("length_penalty", 1.0)), kwargs.get("early_stopping", False),
+                       kwargs.get("_beam_len_counts_prompt", True))
+            # plain beam search (what the reference's eval loaders ask for) runs inside the device loop; beam-sample, stopping
+            # criteria, strict mode and more rows than a replica decodes keep the host loop
+            on_device = (kwargs.get("beam_on_device", True) and sample is None and not stopping_criteria
+                         and self.engine.precision != "strict" and input_ids.shape[0] * int(num_beams) <= self.engine.MAX_BATCH)
+            if on_device:
+                seqs, scores = self._beam_search_device(*beam_args, *beam_kw)
+            else:
+                seqs, scores = self._beam_search(*beam_args, stopping_criteria, *beam_kw, sample, return_scores=True)
+            return GenerateOutput(sequences=seqs, sequences_scores=scores) if as_dict else seqs
         T = input_ids.shape[1]
         B = input_ids.shape[0]
         if max_new_tokens is None:
@@ -632,8 +648,36 @@ class _HipCausalLMBase:
     _sample_calls = 0
 
     # ---- beam search (HF GenerationMixin.beam_search + BeamSearchScorer of the reference's pinned Transformers 4.31) -----------
+    def _beam_search_device(self, input_ids, images, segs, depths, num_beams, max_new_tokens, max_length, eos_token_id, pad_token_id,
+                            attention_mask, length_penalty, early_stopping, len_counts_prompt):
+        """generate(num_beams=n) through HipEngine.generate_beam: the whole loop of `_beam_search` below on the device (one
+        captured beam step per token, scores in fp32), its finalisation in the engine.  -> ([B, T + L] int64 in the form
+        `_beam_search` returns, sequences_scores [B] float32)."""
+        import torch
+
+        ids_cpu = input_ids.detach().cpu() if hasattr(input_ids, "detach") else torch.as_tensor(np.asarray(input_ids))
+        T = ids_cpu.shape[1]
+        if max_new_tokens is None:
+            max_new_tokens = (max_length - T) if max_length is not None else 20
+        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
+        eos_list = [int(e) for e in (eos if isinstance(eos, (list, tuple)) else ([] if eos is None else [eos])) if int(e) >= 0]
+        pad = pad_token_id if pad_token_id is not None else (self.config.pad_token_id if self.config.pad_token_id is not None
+                                                             else (eos_list[0] if eos_list else None))
+        segs = segs if self.variant != "llava" else None
+        depths = depths if self.variant == "vcoder_ds" else None
+        new, _, scores = self.engine.generate_beam(ids_cpu.numpy(), images, segs, depths, num_beams=num_beams,
+                                                   max_new_tokens=max_new_tokens, eos_token_id=eos_list or None, pad_token_id=pad,
+                                                   length_penalty=length_penalty, early_stopping=early_stopping,
+                                                   len_counts_prompt=len_counts_prompt, attention_mask=attention_mask)
+        self._generation += 1
+        out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
+        if hasattr(input_ids, "device"):
+            out = out.to(input_ids.device)
+        return out, torch.from_numpy(scores)
+
     def _beam_search(self, input_ids, images, segs, depths, num_beams, max_new_tokens, max_length, eos_token_id, pad_token_id,
-                     attention_mask, stopping_criteria, length_penalty, early_stopping, len_counts_prompt, sample=None):
+                     attention_mask, stopping_criteria, length_penalty, early_stopping, len_counts_prompt, sample=None,
+                     return_scores=False):
         """`generate(num_beams=n)` as the reference's eval loaders can ask for it (eval/model_seg_loader.py:129-139 forwards
         args.num_beams): every sequence is expanded to n beams (rows b*n .. b*n+n-1, as `_expand_inputs_for_generation`), the
         prefill and one cached decode step per token run on the engine, scoring is HF's — log-softmax of the fp32 logits plus
@@ -778,12 +822,14 @@ class _HipCausalLMBase:
             lg, _ = self.engine.decode_step(ntok.view(-1).numpy().astype(np.int32))
             logits = torch.from_numpy(lg).float()
         # finalize: open beams become hypotheses, the best one per sequence is returned
-        out_rows = []
+        out_rows, best_scores = [], []
         for b in range(B):
             if not done[b]:
                 for j in range(nb):
                     add_hyp(b, seqs[b * nb + j], float(beam_scores[b * nb + j]))
-            out_rows.append(max(hyps[b], key=lambda t_: t_[0])[1])
+            best_score, best_row = max(hyps[b], key=lambda t_: t_[0])
+            out_rows.append(best_row)
+            best_scores.append(best_score)
         L = max(r.shape[0] for r in out_rows)
         max_len = T + max_new_tokens
         L_out = min(L + 1, max_len)            # BeamSearchScorer.finalize: room for the EOS a finished hypothesis does not carry
@@ -796,7 +842,7 @@ class _HipCausalLMBase:
                 out[b, r.shape[0]] = int(eos)
         if hasattr(input_ids, "device"):
             out = out.to(input_ids.device)
-        return out
+        return (out, torch.tensor(best_scores, dtype=torch.float32)) if return_scores else out
 
 
 def _all_ones(attention_mask) -> bool:
