@@ -272,7 +272,7 @@ int vc_reorder_cache(vc_model* m, const int32_t* src_rows, int B);
  * returned width min(longest + 1, max_new), pad_id elsewhere; out_len [B] its length; out_score [B] its score; n_steps the steps run.
  * Honours vc_set_attention_mask / vc_set_image_counts (given for the B un-expanded rows).  Runs on the session's own loop.
  * Refused before anything is touched: num_beams < 1, B * num_beams > 16, n_eos > 8 (VC_ERR_INVALID); precision mode "strict", a
- * pending vc_request_generate_logprobs (VC_ERR_STATE).  More than n EOS ids among a step's 2 n best fails with VC_ERR_INVALID (HF's
+ * pending vc_request_generate_logprobs or vc_request_logits_processors (VC_ERR_STATE).  More than n EOS ids among a step's 2 n best fails with VC_ERR_INVALID (HF's
  * ValueError). */
 int vc_generate_beam(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
                      int pixels_on_device, int num_beams, int max_new, const int32_t* eos_ids, int n_eos, int pad_id,
@@ -320,7 +320,7 @@ int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const float* img,
  *   top_ids / top_logprobs [B, max_new, top_k]   the top_k most likely tokens of every step, ordered by (log-prob descending, id
  *                                      ascending — ties break as the greedy argmax breaks them); NULL iff top_k == 0
  * of the model's own next-token distribution: log_softmax of the step's fp32 logits, taken BEFORE temperature / top-k / top-p, also
- * when sampling.  A kernel behind every selection of the loop reduces the step's logits rows; the slabs come back once, beside
+ * when sampling, and before the logits processors of vc_request_logits_processors (the raw rows).  A kernel behind every selection of the loop reduces the step's logits rows; the slabs come back once, beside
  * out_ids.  A row's finishing token (its EOS, or the token that completes a stop sequence) is scored; positions behind it (the row
  * emits pad there) and columns the loop never reached hold 0.0 / 0.0 / -1.  When a greedy row's token is among its top ids, the two
  * log-probs are bit-equal.
@@ -332,6 +332,42 @@ int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const float* img,
 int vc_request_generate_logprobs(vc_model* m, int top_k, float* token_logprobs /* [B, max_new] host */,
                                  float* top_logprobs /* [B, max_new, top_k] host, NULL iff top_k == 0 */,
                                  int32_t* top_ids /* same shape */, size_t cap_rows /* >= B * max_new of the call it applies to */);
+
+/* Logits processors of the NEXT vc_generate / vc_generate_greedy* call (one-shot), applied on the device in front of every selection
+ * of the loop, in HF 4.31's order (generation/logits_process.py):
+ *   repetition_penalty p   RepetitionPenaltyLogitsProcessor: every id t of the row's history gets raw[t] < 0 ? raw[t] * p : raw[t] / p
+ *                          (IEEE fp32).  > 0 and finite; 1.0: off
+ *   no_repeat_ngram_size n NoRepeatNGramLogitsProcessor: -inf for every token that would complete an n-gram the history already
+ *                          holds; n = 1 bans every history id; 0: off
+ *   bad words              NoBadWordsLogitsProcessor: at most 32 sequences of 1 .. 8 ids (bad_words_ids flattened, bad_words_lens[i]
+ *                          ids each): a one-id sequence is always -inf, a longer one bans its last id while the history ends
+ *                          with the ids in front of it
+ *   min_new_tokens m       MinNewTokensLengthLogitsProcessor: while fewer than m tokens are generated, the call's eos_id and the
+ *                          eos_extra ids (the further ids of an EOS list, at most 8) are -inf; stop sequences are unaffected.
+ *                          HF's min_length is max(m, min_length - T) on the caller's side (HF counts the un-spliced input_ids)
+ * The history of a row is the caller's ids [T] (image placeholders and all) followed by the ids generated so far.  History ids
+ * outside [0, vocab) are skipped — HF itself would raise an index error on the image placeholders there.  A token that is both
+ * penalised and banned is -inf.
+ * The call then runs on the session's own loop (every precision mode, whatever VC_POOL says; strict mode enqueues its steps
+ * eagerly): a kernel in front of every selection writes a processed copy of the step's logits rows, which the selection — greedy or
+ * sampled — reads; the parameters travel in the rows' records, so one captured step serves every setting.  Per-token log-probs
+ * (vc_request_generate_logprobs) of such a call stay those of the RAW rows: the model's own distribution, before processors as well
+ * as before temperature / top-k / top-p.
+ * Refused with VC_ERR_INVALID, nothing changed: a penalty that is not above 0 or not finite, a negative n or m, more than 32
+ * sequences, a sequence that is empty or longer than 8 ids, more than 8 eos_extra ids.  The struct and its arrays are copied here.
+ * Cleared when that call returns, also when it fails; every other entry point ignores and clears it — except vc_generate_beam,
+ * which refuses to run with VC_ERR_STATE while one is pending (and clears it); p == NULL cancels. */
+typedef struct vc_logits_processors {
+    float repetition_penalty;
+    int32_t no_repeat_ngram_size;
+    int32_t min_new_tokens;
+    int32_t n_bad_words;
+    const int32_t* bad_words_ids;
+    const int32_t* bad_words_lens;
+    int32_t n_eos_extra;
+    const int32_t* eos_extra;
+} vc_logits_processors;
+int vc_request_logits_processors(vc_model* m, const vc_logits_processors* p);
 
 /* spliced sequence length (text rows + feature rows) of the last vc_generate_greedy* call: lets a caller that splits a large
  * batch into replica-sized pieces reproduce the reference's whole-batch behaviour for unequal lengths (quirk 6) */

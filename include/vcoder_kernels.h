@@ -155,6 +155,22 @@ void vck_beam_step(const float* cand_lp, const int* cand_id, float* beam_score, 
  * tail is cut at span_positions).  perm, start and the records are read on the device.  pos_bytes a multiple of 16. */
 void vck_kv_permute_tail(void* kcache, void* vcache, void* tmp, const int* perm, const int* start, const int* rows, int R, int H,
                          int cap_positions, int pos_bytes, int span_positions, void* stream);
+/* logits processors in front of the selection (generate(repetition_penalty=, no_repeat_ngram_size=, bad_words_ids=, min_new_tokens=)):
+ * out[r, 0:V] = logits[r, 0:V] with the processors of row r applied; the raw rows are only read, columns V..ldo of `out` are not
+ * written, the rows need no alignment (16-byte accesses where source and destination allow them).  One workgroup per row; the
+ * parameters are the RowState record of the row (rows [nrows][128] int32, vck_row_state_stride()):
+ *   [0] active (0: the row is skipped)   [2] step: ids generated so far   [4] max_new (the step is clamped to it)
+ *   [5] EOS id (< 0: none)               [14] offset of the row's generated ids in out_ids
+ *   [15] repetition penalty, float bits (> 0; 1.0 or 0 bits: off)        [96] no-repeat n-gram size (0: off)
+ *   [97] min_new_tokens: while step < it, [5] and the ids of [102..] get -inf
+ *   [98] / [99] offset and count of the row's prompt ids in prompt_ids   [100] how many sequences of bad_words apply to the row
+ *   [101] count of further EOS ids (<= 8) in [102 .. 109]
+ * The history of a row is its prompt ids followed by out_ids[off .. off + step).  In HF's order: the repetition penalty
+ * (raw < 0 ? raw * p : raw / p, IEEE fp32, read from the raw row) over every history id, then -inf for every token that would
+ * repeat an n-gram of the history, that completes a bad word (bad_words [32][9]: length 1 .. 8, ids; a one-id word always), and for
+ * the EOS ids before min_new_tokens.  History and banned ids outside [0, V) are skipped (image placeholders). */
+void vck_logits_process(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
+                        const int* out_ids, const int* bad_words, int nrows, int V, void* stream);
 void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w, uint16_t* xg, int B,
                           int D, int npart, void* stream);
 void vck_advance(int* step_dev, int* pos_dev, int* ctx_dev, void* stream);

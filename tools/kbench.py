@@ -654,6 +654,43 @@ def bench_topk_logprob():
             print(f"{'select top_k=50' if sample else 'argmax scan    '} rows {rows:4d} V {V}: {timeit(g, iters=40):7.1f} us", flush=True)
 
 
+def bench_logits_process():
+    """logits_process_kernel over [rows, 32000] fp32 logits (rows 1 / 8 / 16: a decode step's launch): everything off (the copy), and all
+    processors on over a history of 1216 prompt ids + 64 / 127 generated ids (repetition penalty 1.3, n-gram 3, 2 bad words, min_new)"""
+    V, T = 32000, 1216
+    stride = int(lib.vck_row_state_stride())
+    f32 = lambda x: int(torch.tensor(x, dtype=torch.float32).view(torch.int32))
+    tab = torch.zeros((32, 9), dtype=torch.int32, device=dev)
+    tab[0, :2] = torch.tensor([1, 7])
+    tab[1, :3] = torch.tensor([2, 5, 9])
+    for rows in (1, 8, 16):
+        lg = [torch.randn(rows, V, device=dev) * 3 for _ in range(4)]
+        out = torch.empty(rows, V, device=dev)
+        prompt = torch.randint(0, V, (rows, T), dtype=torch.int32, device=dev)
+        gen = torch.randint(0, V, (rows, 128), dtype=torch.int32, device=dev)
+        it = [0]
+        for on, step in ((0, 0), (1, 64), (1, 127)):
+            rs = torch.zeros((rows, stride), dtype=torch.int32, device=dev)
+            rs[:, 0] = 1                  # RS_ACTIVE
+            rs[:, 2] = step               # RS_STEP
+            rs[:, 4] = 128                # RS_MAXNEW
+            rs[:, 5] = 2                  # RS_EOS
+            rs[:, 14] = torch.arange(rows, dtype=torch.int32, device=dev) * 128   # RS_OUT_OFF
+            if on:
+                rs[:, 15] = f32(1.3)      # RS_LP_PENALTY
+                rs[:, 96] = 3             # RS_LP_NGRAM
+                rs[:, 97] = 128           # RS_LP_MINNEW
+                rs[:, 98] = torch.arange(rows, dtype=torch.int32, device=dev) * T     # RS_LP_HIST_OFF
+                rs[:, 99] = T             # RS_LP_HIST_LEN
+                rs[:, 100] = 2            # RS_LP_NBAD
+
+            def f():
+                it[0] += 1
+                lib.vck_logits_process(P(lg[it[0] % 4]), V, P(out), V, P(rs), P(prompt), P(gen), P(tab), rows, V, None)
+            us = timeit(f, iters=40)
+            print(f"logits_process rows {rows:3d} V {V} {'all on, step %3d' % step if on else 'all off (copy) '}: {us:7.1f} us", flush=True)
+
+
 def bench_score_head():
     """The score path's chunk at 7b dims (D 4096, V 32000): gathered final RMSNorm + lm_head + token_logprob over M scored rows (16 .. 1024), the
     lm_head as ceil(M / 32) passes of the weight-streaming GEMV (packed weights) against one GEMM — the crossover behind
@@ -728,7 +765,7 @@ if __name__ == "__main__":
              "gemm_f8": bench_gemm_f8, "gemv_rows8": bench_gemv_rows8, "gemv_wide": bench_gemv_wide, "gemm_chunk": bench_gemm_chunk,
              "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,
              "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn, "token_logprob": bench_token_logprob,
-             "topk_logprob": bench_topk_logprob,
+             "topk_logprob": bench_topk_logprob, "logits_process": bench_logits_process,
              "score_head": bench_score_head}
     for w in what:
         table[w]()

@@ -34,6 +34,12 @@ class Sampling(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class LogitsProcessors(C.Structure):   # vc_logits_processors
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32), ("min_new_tokens", C.c_int32),
+                ("n_bad_words", C.c_int32), ("bad_words_ids", C.c_void_p), ("bad_words_lens", C.c_void_p),
+                ("n_eos_extra", C.c_int32), ("eos_extra", C.c_void_p)]
+
+
 TOKEN_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32))
 
 
@@ -114,6 +120,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_request_generate_logprobs.restype = C.c_int
     lib.vck_topk_logprob.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.vck_topk_logprob.restype = None
+    lib.vc_request_logits_processors.argtypes = [vp, C.POINTER(LogitsProcessors)]
+    lib.vc_request_logits_processors.restype = C.c_int
+    lib.vck_logits_process.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp]
+    lib.vck_logits_process.restype = None
     lib.vc_rewind.argtypes = [vp, i32]
     lib.vc_rewind.restype = C.c_int
     lib.vc_request_attentions.argtypes = [vp, vp, C.c_size_t]

@@ -214,6 +214,17 @@ struct vc_model {
     bool lp_on = false;
     int lp_k = 0;
     Buf lp_tok, lp_top, lp_ids;
+    // logits processors of the NEXT vc_generate* (vc_request_logits_processors; one-shot), copied from the caller's struct: the
+    // bad-word table as the kernel reads it ([VC_MAX_BAD_WORDS][1 + VC_MAX_BAD_WORD_LEN]: length, ids).  While that call runs on
+    // the session's loop — proc_on — every selection is preceded by logits_process_kernel: the call's prompt ids and table in
+    // proc_prompt / proc_bad, the processed rows in proc_logits [B, V]
+    bool gproc = false;
+    float gproc_penalty = 1.f;
+    int gproc_ngram = 0, gproc_minnew = 0, gproc_nbad = 0, gproc_neos = 0;
+    int gproc_eos[VC_MAX_EOS_EXTRA] = {};
+    std::vector<int> gproc_bad;
+    bool proc_on = false;
+    Buf proc_prompt, proc_bad, proc_logits;
     bool tok_stale = false;       // vc_rewind ran: the token the last step selected on the device no longer continues the sequence
     bool plan_only = false;       // do_prefill stops behind the splice plan (vc_plan_spliced_len): no tower pass, no state change
     int reserve_new = 64;         // KV slots a vc_prefill keeps free behind the prompt (vc_model_reserve_decode)
@@ -236,7 +247,7 @@ struct vc_model {
     int graph_rows = 0;
     hipGraphExec_t graph_lp = nullptr;   // the same step with the log-prob launch (lp_on), for graph_lp_k alternatives
     int graph_lp_rows = 0, graph_lp_k = 0;
-    bool graph_lp_masked = false;
+    bool graph_lp_masked = false, graph_lp_proc = false;   // (graph_lp also serves proc_on: with the processor launch in front of the selection)
     // the device beam loop (vc_generate_beam; engine_llm.inc BeamLoop): bm_state holds the fixed-size part (candidates, beam scores,
     // perm, prompt lengths, sequence records, hypotheses, parameters, flags), bm_tab the tok / parent tables, bm_den the two
     // denominator tables, bm_tmp the staging of the tail permute — the last three sized for bm_cap_new steps.  graph_beam is one
@@ -284,6 +295,10 @@ static void clear_score_request(vc_model* m) {
     m->stk_ids = nullptr;
     m->stk_cap = 0;
 }
+static void clear_logits_processors_request(vc_model* m) {
+    m->gproc = false;
+    m->gproc_bad.clear();
+}
 static void clear_generate_logprobs_request(vc_model* m) {
     m->glp_k = 0;
     m->glp_tok = m->glp_top = nullptr;
@@ -305,6 +320,7 @@ struct OneShotReset {
         m->attn_cap = 0;
         clear_score_request(m);
         clear_generate_logprobs_request(m);
+        clear_logits_processors_request(m);
     }
 };
 

@@ -188,7 +188,7 @@ VC_API void vc_model_destroy(vc_model* m) {
                    &m->s_q, &m->s_attn, &m->s_h, &m->s_kc, &m->s_vc, &m->s_xl, &m->pp_src, &m->pp_sq, &m->pp_tmp, &m->pp_out,
                    &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre,
                    &m->ext_tok, &m->sc_idx, &m->sc_lp, &m->sc_xn, &m->sc_logits, &m->sc_tlp, &m->sc_tid, &m->lp_tok, &m->lp_top,
-                   &m->lp_ids, &m->bm_state, &m->bm_tab, &m->bm_den, &m->bm_tmp})
+                   &m->lp_ids, &m->proc_prompt, &m->proc_bad, &m->proc_logits, &m->bm_state, &m->bm_tab, &m->bm_den, &m->bm_tmp})
         b->release();
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
@@ -642,6 +642,50 @@ VC_API int vc_request_generate_logprobs(vc_model* m, int top_k, float* token_log
     return VC_OK;
 }
 
+/* Logits processors of the NEXT vc_generate* call (one-shot): repetition penalty, no-repeat n-gram, bad words, minimum new tokens,
+ * applied on the device in front of every selection.  p == NULL cancels.  See include/vcoder_hip.h. */
+VC_API int vc_request_logits_processors(vc_model* m, const vc_logits_processors* p) {
+    if (!m) return VC_ERR_INVALID;
+    if (!p) {
+        clear_logits_processors_request(m);
+        return VC_OK;
+    }
+    // (a refusal leaves a pending request as it was: nothing touched)
+    if (!(p->repetition_penalty > 0.f) || !std::isfinite(p->repetition_penalty)) {
+        m->ctx->err = "vc_request_logits_processors: repetition_penalty must be a finite value above 0";
+        return VC_ERR_INVALID;
+    }
+    if (p->no_repeat_ngram_size < 0 || p->min_new_tokens < 0) {
+        m->ctx->err = "vc_request_logits_processors: no_repeat_ngram_size and min_new_tokens must not be negative";
+        return VC_ERR_INVALID;
+    }
+    if (p->n_bad_words < 0 || p->n_bad_words > VC_MAX_BAD_WORDS || (p->n_bad_words > 0 && (!p->bad_words_ids || !p->bad_words_lens)) ||
+        p->n_eos_extra < 0 || p->n_eos_extra > VC_MAX_EOS_EXTRA || (p->n_eos_extra > 0 && !p->eos_extra)) {
+        m->ctx->err = "vc_request_logits_processors: at most 32 bad-word sequences and 8 further EOS ids";
+        return VC_ERR_INVALID;
+    }
+    for (int q = 0; q < p->n_bad_words; ++q)
+        if (p->bad_words_lens[q] < 1 || p->bad_words_lens[q] > VC_MAX_BAD_WORD_LEN) {
+            m->ctx->err = "vc_request_logits_processors: a bad-word sequence holds 1 .. 8 ids";
+            return VC_ERR_INVALID;
+        }
+    m->gproc = true;
+    m->gproc_penalty = p->repetition_penalty;
+    m->gproc_ngram = p->no_repeat_ngram_size;
+    m->gproc_minnew = p->min_new_tokens;
+    m->gproc_nbad = p->n_bad_words;
+    m->gproc_neos = p->n_eos_extra;
+    for (int e = 0; e < p->n_eos_extra; ++e) m->gproc_eos[e] = p->eos_extra[e];
+    m->gproc_bad.assign((size_t)VC_MAX_BAD_WORDS * (1 + VC_MAX_BAD_WORD_LEN), 0);
+    for (int q = 0, off = 0; q < p->n_bad_words; ++q) {
+        int* e = m->gproc_bad.data() + (size_t)q * (1 + VC_MAX_BAD_WORD_LEN);
+        e[0] = p->bad_words_lens[q];
+        for (int j = 0; j < e[0]; ++j) e[1 + j] = p->bad_words_ids[off + j];
+        off += e[0];
+    }
+    return VC_OK;
+}
+
 /* KV-cache slots the next vc_prefill keeps free behind the prompt for vc_decode_step (default 64; clamped to
  * max_position_embeddings).  A decode loop that outruns the reserve still works — the cache grows, at the cost of a copy. */
 VC_API int vc_model_reserve_decode(vc_model* m, int max_new_tokens) {
@@ -832,6 +876,7 @@ void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* n
             m->attn_out = nullptr;
             m->hidden_cap = m->attn_cap = 0;
             clear_generate_logprobs_request(m);
+            clear_logits_processors_request(m);
         }
     } step_requests{m};
     if (m->precision == 1) {
@@ -871,6 +916,7 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
             m->hidden_cap = m->attn_cap = 0;
             clear_score_request(m);
             clear_generate_logprobs_request(m);
+            clear_logits_processors_request(m);
         }
     } requests{m};
     GUARD_BEGIN

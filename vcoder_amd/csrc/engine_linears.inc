@@ -128,6 +128,11 @@ struct LoopView {
     float *lp_tok, *lp_top;
     int* lp_ids;
     int lp_k;
+    // logits processors of a generate() call (vc_request_logits_processors): the call's prompt ids and bad-word table, and the
+    // processed rows the selection then reads.  proc_logits == nullptr (every loop but a session's while such a call runs): no
+    // processor launch, the selection reads the raw rows.
+    const int *proc_prompt, *proc_bad;
+    float* proc_logits;
 };
 
 // the next timing slot of the step being enqueued (nullptr: profiling off)

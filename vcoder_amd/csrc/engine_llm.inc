@@ -203,6 +203,11 @@ LoopView session_view(vc_model* m) {
         v.lp_ids = m->lp_ids.as<int>();
         v.lp_k = m->lp_k;
     }
+    if (m->proc_on) {
+        v.proc_prompt = m->proc_prompt.as<int>();
+        v.proc_bad = m->proc_bad.as<int>();
+        v.proc_logits = m->proc_logits.as<float>();
+    }
     return v;
 }
 
@@ -502,6 +507,15 @@ void enqueue_step_logprobs(vc_model* m, const LoopView& v, const float* logits, 
     launch_topk_logprob(a, nrows, -1, v.st);
 }
 
+// the logits processors of the loop's rows in front of the selection: -> the rows launch_select_embed reads (the raw ones without a
+// request: nothing is launched).  enqueue_step_logprobs keeps reading the raw rows.
+const float* enqueue_step_processors(vc_model* m, const LoopView& v, const float* logits, int nrows) {
+    if (!v.proc_logits) return logits;
+    LogitsProcessArgs a{logits, m->c.vocab, v.proc_logits, m->c.vocab, v.rows, v.proc_prompt, v.out_ids, v.proc_bad, m->c.vocab};
+    launch_logits_process(a, nrows, v.st);
+    return v.proc_logits;
+}
+
 // ---- the device beam loop (vc_generate_beam) -----------------------------------------------------------------------------------
 // Its buffers: the fixed-size part carved from m->bm_state, the tables from m->bm_tab / m->bm_den (ensure_beam sizes them).
 struct BeamLoop {
@@ -627,7 +641,7 @@ void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_
     if (beam) {
         enqueue_beam_tail(m, v, *beam, v.logits, 3, true);
     } else {
-        launch_select_embed(select_args(m, v, v.logits, nrows, 3), v.st);                                    // K19/K20+K10
+        launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, v.logits, nrows), nrows, 3), v.st);   // K19/K20+K10
         enqueue_step_logprobs(m, v, v.logits, nrows);
     }
     // in-situ timing: fold the step's slots (5 per layer: qkv, attention, o, gate/up, down; then lm_head) into the span's sums
@@ -641,7 +655,7 @@ void enqueue_decode_step_strict(vc_model* m, int B) {
     emit_hidden(m, 0, B, 1, m->x_dec.as<float>());
     run_llm_layers_strict(m, m->x_dec.as<float>(), B, 1, v.rows + RS_POS, false);
     logits_strict(m, m->x_dec.as<float>(), nullptr, B);
-    launch_select_embed(select_args(m, v, v.logits, B, 3), v.st);
+    launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, v.logits, B), B, 3), v.st);
     enqueue_step_logprobs(m, v, v.logits, B);
 }
 
@@ -771,17 +785,21 @@ hipGraphExec_t capture_step(vc_model* m, const LoopView& v, int nrows, const Bea
     return exec;
 }
 
-// the session's captured step: the plain one, or — while a generate() call with log-probs runs (lp_on) — the one that carries the
-// log-prob launch for lp_k alternatives.  Both stay instantiated side by side: a vc_decode_step behind such a call replays the plain step.
+// the session's captured step: the plain one, or — while a generate() call with log-probs (lp_on) and / or logits processors (proc_on)
+// runs — the one that carries the log-prob launch for lp_k alternatives and / or the processor launch.  Both stay instantiated side by
+// side: a vc_decode_step behind such a call replays the plain step.
 hipGraphExec_t ensure_graph(vc_model* m, int B) {
-    if (m->lp_on) {
-        if (m->graph_lp && m->graph_lp_rows == B && m->graph_lp_masked == m->kmask_in_decode && m->graph_lp_k == m->lp_k)
+    if (m->lp_on || m->proc_on) {
+        const int k = m->lp_on ? m->lp_k : -1;
+        if (m->graph_lp && m->graph_lp_rows == B && m->graph_lp_masked == m->kmask_in_decode && m->graph_lp_k == k &&
+            m->graph_lp_proc == m->proc_on)
             return m->graph_lp;
         if (m->graph_lp) { (void)hipGraphExecDestroy(m->graph_lp); m->graph_lp = nullptr; }
         m->graph_lp = capture_step(m, session_view(m), B);
         m->graph_lp_rows = B;
         m->graph_lp_masked = m->kmask_in_decode;
-        m->graph_lp_k = m->lp_k;
+        m->graph_lp_k = k;
+        m->graph_lp_proc = m->proc_on;
         return m->graph_lp;
     }
     if (m->graph && m->graph_rows == B && m->graph_masked == m->kmask_in_decode) return m->graph;
@@ -831,6 +849,20 @@ void ensure_logprob_slabs(vc_model* m, int B, int K) {
         }
 }
 
+// the buffers of a generate() call with logits processors: the prompt ids [B, T], the bad-word table, the processed rows [B, V]
+void ensure_processor_buffers(vc_model* m, int B, int T) {
+    const void* before[] = {m->proc_prompt.p, m->proc_bad.p, m->proc_logits.p};
+    m->proc_prompt.ensure((size_t)B * T * 4);
+    m->proc_bad.ensure((size_t)VC_MAX_BAD_WORDS * (1 + VC_MAX_BAD_WORD_LEN) * 4);
+    m->proc_logits.ensure((size_t)rup(B, 16) * m->c.vocab * 4);
+    const void* after[] = {m->proc_prompt.p, m->proc_bad.p, m->proc_logits.p};
+    for (int i = 0; i < 3; ++i)
+        if (before[i] != after[i] && m->graph_lp) {   // pointers baked into the step that carries the launch
+            (void)hipGraphExecDestroy(m->graph_lp);
+            m->graph_lp = nullptr;
+        }
+}
+
 // ---- host-side RowState records ---------------------------------------------------------------------------------
 struct GenParams {  // what a generate() call asks for (HF GenerationMixin subset; SURVEY.md Appendix C)
     int max_new = 0, eos = -1, pad = 0;
@@ -839,6 +871,10 @@ struct GenParams {  // what a generate() call asks for (HF GenerationMixin subse
     uint64_t seed = 0;
     int n_stop = 0;
     int stop[VC_MAX_STOP][1 + VC_MAX_STOP_LEN] = {};
+    // logits processors (vc_request_logits_processors; proc 0: the RS_LP_* slots stay zero); row b's prompt ids are ids[b * proc_T ..]
+    int proc = 0, proc_ngram = 0, proc_minnew = 0, proc_nbad = 0, proc_neos = 0, proc_T = 0;
+    float proc_penalty = 1.f;
+    int proc_eos[VC_MAX_EOS_EXTRA] = {};
 };
 
 uint32_t mix_seed(uint64_t seed, uint32_t row, uint32_t salt) {
@@ -871,6 +907,16 @@ void fill_rows(int* rec, int B, const GenParams& g, int pos, const int* tail /*[
         for (int j = 0; j < VC_MAX_STOP_LEN - 1; ++j) r[RS_TAIL + j] = tail ? tail[b * (VC_MAX_STOP_LEN - 1) + j] : INT32_MIN;
         for (int q = 0; q < g.n_stop; ++q)
             for (int j = 0; j < 1 + VC_MAX_STOP_LEN; ++j) r[RS_STOP + q * (1 + VC_MAX_STOP_LEN) + j] = g.stop[q][j];
+        if (g.proc) {
+            memcpy(&r[RS_LP_PENALTY], &g.proc_penalty, 4);
+            r[RS_LP_NGRAM] = g.proc_ngram;
+            r[RS_LP_MINNEW] = g.proc_minnew;
+            r[RS_LP_HIST_OFF] = b * g.proc_T;
+            r[RS_LP_HIST_LEN] = g.proc_T;
+            r[RS_LP_NBAD] = g.proc_nbad;
+            r[RS_LP_NEOS] = g.proc_neos;
+            for (int e = 0; e < g.proc_neos; ++e) r[RS_LP_EOS + e] = g.proc_eos[e];
+        }
     }
 }
 

@@ -606,13 +606,28 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
         HIPCHK(hipMemsetAsync(m->lp_top.p, 0, m->lp_top.cap, m->st));
         HIPCHK(hipMemsetAsync(m->lp_ids.p, 0xFF, m->lp_ids.cap, m->st));
     }
+    // vc_request_logits_processors: every selection of this call is preceded by the processor launch (session_view: proc_on), which
+    // reads the caller's prompt ids (as int32, placeholders and all) and the bad-word table
+    struct ProcScope {
+        vc_model* m;
+        ~ProcScope() { m->proc_on = false; }
+    } proc_scope{m};
+    std::vector<int> ids32;
+    if (g.proc) {
+        ensure_processor_buffers(m, B, T);
+        ids32.resize((size_t)B * T);
+        for (size_t i = 0; i < ids32.size(); ++i) ids32[i] = (int)std::max<int64_t>(std::min<int64_t>(ids[i], INT32_MAX), INT32_MIN);
+        HIPCHK(hipMemcpyAsync(m->proc_prompt.p, ids32.data(), ids32.size() * 4, hipMemcpyHostToDevice, m->st));
+        HIPCHK(hipMemcpyAsync(m->proc_bad.p, m->gproc_bad.data(), m->gproc_bad.size() * 4, hipMemcpyHostToDevice, m->st));
+        m->proc_on = true;   // (both host vectors live until the synchronize behind the step-0 selection)
+    }
     if (m->ev[2]) HIPCHK(hipEventRecord(m->ev[2], m->st));
     arm_session_rows(m, g, tail.data());
     const LoopView v = session_view(m);
     // token 0 comes from the prefill logits
     std::vector<int> fill((size_t)B * m->out_stride, g.pad);
     HIPCHK(hipMemcpyAsync(m->out_ids.p, fill.data(), fill.size() * 4, hipMemcpyHostToDevice, m->st));
-    launch_select_embed(select_args(m, v, v.logits, B, 1), m->st);  // step 0 -> 1; the position stays at S
+    launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, v.logits, B), B, 1), m->st);  // step 0 -> 1; the position stays at S
     enqueue_step_logprobs(m, v, v.logits, B);
     HIPCHK(hipStreamSynchronize(m->st));
     gate.unlock();
@@ -966,7 +981,20 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
     // vc_request_generate_logprobs: the call runs on the session's own loop, whose steps carry the log-prob launch
     REQUIRE(!m->glp_tok || m->glp_cap >= (size_t)B * max_new, VC_ERR_INVALID,
             "log-prob buffers hold %zu rows, the call yields [%d, %d]", m->glp_cap, B, max_new);
-    if (use_pool && m->precision != 1 && !m->glp_tok)
+    // vc_request_logits_processors: likewise (the pool's steps carry no processor launch)
+    if (m->gproc) {
+        REQUIRE(m->gproc_bad.size() == (size_t)VC_MAX_BAD_WORDS * (1 + VC_MAX_BAD_WORD_LEN), VC_ERR_STATE, "bad-word table of %zu ints",
+                m->gproc_bad.size());
+        g.proc = 1;
+        g.proc_penalty = m->gproc_penalty;
+        g.proc_ngram = m->gproc_ngram;
+        g.proc_minnew = m->gproc_minnew;
+        g.proc_nbad = m->gproc_nbad;
+        g.proc_neos = m->gproc_neos;
+        for (int e = 0; e < m->gproc_neos; ++e) g.proc_eos[e] = m->gproc_eos[e];
+        g.proc_T = T;
+    }
+    if (use_pool && m->precision != 1 && !m->glp_tok && !g.proc)
         generate_on_pool(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids, n_generated);
     else
         generate_on_session(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids,
@@ -995,6 +1023,7 @@ VC_API int vc_generate_beam(vc_model* m, const int64_t* ids, int B, int T, const
     REQUIRE(pad_id < m->c.vocab, VC_ERR_INDEX, "pad_token_id %d is outside the vocabulary (%d)", pad_id, m->c.vocab);
     REQUIRE(m->precision != 1, VC_ERR_STATE, "strict mode keeps beam search on the host loop (vc_decode_step + vc_reorder_cache)");
     REQUIRE(!m->glp_tok, VC_ERR_STATE, "per-token log-probs are not implemented for beam search: a vc_request_generate_logprobs is pending");
+    REQUIRE(!m->gproc, VC_ERR_STATE, "logits processors are not implemented in the device beam loop: a vc_request_logits_processors is pending");
     {   // the tail permute moves 16-byte chunks of a cache row: the element size the prefill below will give the session's cache
         const int es = m->precision == 2 ? split_kv_es() : step_kv_es(m);
         REQUIRE((m->hd * es) % 16 == 0, VC_ERR_STATE, "the tail permute moves 16-byte chunks: head_dim %d x %d bytes", m->hd, es);

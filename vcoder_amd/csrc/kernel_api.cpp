@@ -108,6 +108,11 @@ VCK_EXPORT void vck_kv_permute_tail(void* kcache, void* vcache, void* tmp, const
     launch_kv_permute_tail(kcache, vcache, tmp, perm, start, rows, R, H, (size_t)cap_positions * pos_bytes, pos_bytes,
                            (size_t)span_positions * pos_bytes, S(stream));
 }
+VCK_EXPORT void vck_logits_process(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
+                                   const int* out_ids, const int* bad_words, int nrows, int V, void* stream) {
+    LogitsProcessArgs a{logits, ldl, out, ldo, rows, prompt_ids, out_ids, bad_words, V};
+    launch_logits_process(a, nrows, S(stream));
+}
 VCK_EXPORT void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w,
                                      uint16_t* xg, int B, int D, int npart, void* stream) {
     launch_embed_tokens_ssq(tok, embed, x, ssq, xg_w, xg, B, D, npart, S(stream));

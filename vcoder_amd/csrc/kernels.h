@@ -366,11 +366,22 @@ enum RowStateField : int {
     RS_SEED_LO = 12,
     RS_SEED_HI = 13,
     RS_OUT_OFF = 14,  // offset (ints) of the row's out_ids inside SelectArgs::out_ids
+    RS_LP_PENALTY = 15,  // float bits: repetition penalty of logits_process_kernel (> 0; 1.0 — or the zero of a cleared record — off)
     RS_TAIL = 16,     // VC_MAX_STOP_LEN - 1 last prompt ids, right-aligned (suffix matches that reach into the prompt)
     RS_STOP = 24,     // VC_MAX_STOP x (length, VC_MAX_STOP_LEN ids)
+    // the logits processors of the row (logits_process_kernel); a zeroed record has every one of them off
+    RS_LP_NGRAM = 96,     // no-repeat n-gram size (0: off)
+    RS_LP_MINNEW = 97,    // while RS_STEP < this: the EOS ids of the row get -inf
+    RS_LP_HIST_OFF = 98,  // offset (ints) of the row's prompt ids inside LogitsProcessArgs::prompt_ids
+    RS_LP_HIST_LEN = 99,  // prompt ids of the row (the history is these, then out_ids[0 .. RS_STEP))
+    RS_LP_NBAD = 100,     // the first so many sequences of LogitsProcessArgs::bad_words apply to the row (<= VC_MAX_BAD_WORDS)
+    RS_LP_NEOS = 101,     // ids in RS_LP_EOS: the EOS ids beside RS_EOS (<= VC_MAX_EOS_EXTRA)
+    RS_LP_EOS = 102,
     RS_STRIDE = 128,
 };
-static_assert(RS_STOP + VC_MAX_STOP * (1 + VC_MAX_STOP_LEN) <= RS_STRIDE, "row record overflow");
+constexpr int VC_MAX_BAD_WORDS = 32, VC_MAX_BAD_WORD_LEN = 8, VC_MAX_EOS_EXTRA = 8;
+static_assert(RS_STOP + VC_MAX_STOP * (1 + VC_MAX_STOP_LEN) <= RS_LP_NGRAM, "row record overflow");
+static_assert(RS_LP_EOS + VC_MAX_EOS_EXTRA <= RS_STRIDE, "row record overflow");
 
 // selection (greedy / sampled) + EOS / stop bookkeeping + embedding of the selected token (fp32 residual row x, RMSNorm
 // partials ssq, first GEMV operand xg = bf16(x * xg_w)) + per-row step / position advance: one workgroup per row
@@ -428,6 +439,23 @@ struct TopkLogprobArgs {
 };
 // lds_floats < 0: stage the row in LDS when the device allows; 0 (or < V): every pass re-reads the row from global memory
 void launch_topk_logprob(const TopkLogprobArgs& a, int nrows, int lds_floats, hipStream_t s);
+// logits processors in front of the selection (select.hip logits_process_kernel): out[r, 0:V] = the raw row r with the row's
+// processors applied — HF's RepetitionPenaltyLogitsProcessor over the row's history (prompt ids, placeholders and all, then the
+// ids generated so far; ids outside [0, V) are skipped), then -inf for what NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor
+// and MinNewTokensLengthLogitsProcessor ban.  One workgroup per row; parameters in the row's record (RS_LP_*), so rows of one
+// launch may differ; a row with everything off is copied.  The raw row is only read; pad columns of `out` are not written.
+struct LogitsProcessArgs {
+    const float* logits;     // [nrows, ldl] fp32: the raw rows
+    int ldl;
+    float* out;              // [nrows, ldo] fp32: the processed rows
+    int ldo;
+    const int* rows;         // [nrows][RS_STRIDE]
+    const int* prompt_ids;   // the call's prompt ids; row r: prompt_ids[RS_LP_HIST_OFF .. + RS_LP_HIST_LEN)
+    const int* out_ids;      // base of the id store; row r: out_ids[RS_OUT_OFF .. + RS_STEP)
+    const int* bad_words;    // [VC_MAX_BAD_WORDS][1 + VC_MAX_BAD_WORD_LEN]: (length, ids); nullptr when no row has RS_LP_NBAD > 0
+    int V;
+};
+void launch_logits_process(const LogitsProcessArgs& a, int nrows, hipStream_t s);
 // one beam-search step of B sequences of n beams each (rows b * n .. b * n + n - 1; R = B * n <= 16) behind a launch_topk_logprob
 // with K = 2 n into cand_lp / cand_id [R, 2 n] (select.hip beam_step_kernel): what one iteration of HF's beam_search does between
 // `topk` and `_reorder_cache` — the 2 n best of a sequence's n * 2 n candidates (score = lp + beam_score[row], one fp32 add; ordered

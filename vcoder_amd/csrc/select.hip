@@ -650,6 +650,89 @@ void launch_topk_logprob(const TopkLogprobArgs& a0, int nrows, int lds_floats, h
     VC_LAUNCH(topk_logprob_kernel, dim3((unsigned)nrows), dim3(TOPK_THREADS), lds, s, a);
 }
 
+// ---- logits processors in front of the selection (generate(repetition_penalty=, no_repeat_ngram_size=, bad_words_ids=,
+// min_new_tokens= / min_length=); [HF] generation/logits_process.py of Transformers 4.31) ------------------------------------------
+// One workgroup of 1024 threads per row writes a processed copy of the raw fp32 row; the raw row is only read (the log-prob kernel
+// keeps scoring it).  Every processor touches a sparse set of entries chosen by the row's own history h = the caller's prompt ids
+// (placeholders and all: HF counts the un-spliced input_ids) followed by out_ids[0 .. RS_STEP), of length L.  Three phases, a
+// workgroup barrier between them:
+//   1. copy: 16-byte accesses over the part of the row where source and destination are both aligned, scalar elsewhere
+//   2. RepetitionPenaltyLogitsProcessor: out[t] = raw[t] < 0 ? raw[t] * p : raw[t] / p for every history id t in [0, V) — read from
+//      the RAW row, so the duplicates of a history write the same bits, and an IEEE division (no reciprocal): numpy float32
+//      reproduces it.  HF would raise an index error on the image placeholders (negative ids); they are skipped here.
+//   3. -inf setters, in any order (a token both penalised and banned ends as -inf: the barrier stands between the two writes):
+//      NoRepeatNGramLogitsProcessor (size n; L + 1 >= n): h[i + n - 1] for every start 0 <= i <= L - n whose n - 1 ids equal the
+//        last n - 1 of the history; the starts are spread over the threads; n = 1 bans every history id
+//      NoBadWordsLogitsProcessor: sequence q of the call's table (thread q): one id — always; longer — its last id when the
+//        history ends with the ids in front of it (a tail that may reach into the prompt)
+//      MinNewTokensLengthLogitsProcessor / MinLengthLogitsProcessor (folded on the host): RS_EOS and RS_LP_EOS while RS_STEP < m
+// Ids outside [0, V) are never written.  Rows are independent; pad columns V .. ldo are not touched.
+constexpr int LPROC_THREADS = 1024;
+__global__ __launch_bounds__(LPROC_THREADS) void logits_process_kernel(LogitsProcessArgs p) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int* rs = p.rows + (size_t)r * RS_STRIDE;
+    if (!rs[RS_ACTIVE]) return;
+    const int V = p.V;
+    const float* lg = p.logits + (size_t)r * p.ldl;
+    float* out = p.out + (size_t)r * p.ldo;
+    // ---- 1. copy ----------------------------------------------------------------------------------------------------------------
+    const int mis = (int)((reinterpret_cast<uintptr_t>(lg) >> 2) & 3);
+    const bool vec = ((reinterpret_cast<uintptr_t>(lg) ^ reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int head = vec ? min(V, (4 - mis) & 3) : V;   // columns [0, head) and [body_end, V) one float at a time
+    const int body_end = head + ((V - head) & ~3);
+    for (int i = tid; i < head; i += LPROC_THREADS) out[i] = lg[i];
+    for (int i = head + tid * 4; i < body_end; i += LPROC_THREADS * 4) st16f(out + i, ld16f(lg + i));
+    if (body_end + tid < V) out[body_end + tid] = lg[body_end + tid];
+    // ---- the row's history ------------------------------------------------------------------------------------------------------
+    const int P = max(rs[RS_LP_HIST_LEN], 0);
+    const int step = max(min(rs[RS_STEP], rs[RS_MAXNEW]), 0);
+    const int L = P + step;
+    const int* hp = p.prompt_ids + rs[RS_LP_HIST_OFF];
+    const int* hg = p.out_ids + rs[RS_OUT_OFF];
+    auto h = [&](int j) { return j < P ? hp[j] : hg[j - P]; };
+    const float pen = __builtin_bit_cast(float, rs[RS_LP_PENALTY]);
+    const int n = rs[RS_LP_NGRAM], nbad = p.bad_words != nullptr ? min(rs[RS_LP_NBAD], VC_MAX_BAD_WORDS) : 0;
+    __syncthreads();
+    // ---- 2. repetition penalty --------------------------------------------------------------------------------------------------
+    if (pen > 0.f && pen != 1.0f) {
+        for (int j = tid; j < L; j += LPROC_THREADS) {
+            const int t = h(j);
+            if ((unsigned)t >= (unsigned)V) continue;
+            const float v = lg[t];
+            out[t] = v < 0.f ? v * pen : v / pen;
+        }
+    }
+    __syncthreads();
+    // ---- 3. -inf setters --------------------------------------------------------------------------------------------------------
+    if (n >= 1 && L + 1 >= n) {
+        const int tail0 = L - n + 1;   // the last n - 1 ids: h[tail0 .. L)
+        for (int i = tid; i <= L - n; i += LPROC_THREADS) {
+            bool ok = true;
+            for (int k = 0; k < n - 1 && ok; ++k) ok = h(i + k) == h(tail0 + k);
+            const int t = h(i + n - 1);
+            if (ok && (unsigned)t < (unsigned)V) out[t] = -INFINITY;
+        }
+    }
+    if (tid < nbad) {
+        const int* e = p.bad_words + tid * (1 + VC_MAX_BAD_WORD_LEN);
+        const int len = e[0];
+        bool ok = len >= 1 && len <= VC_MAX_BAD_WORD_LEN && len - 1 <= L;
+        for (int k = 0; k < len - 1 && ok; ++k) ok = h(L - (len - 1) + k) == e[1 + k];
+        if (ok && (unsigned)e[len] < (unsigned)V) out[e[len]] = -INFINITY;
+    }
+    if (rs[RS_STEP] < rs[RS_LP_MINNEW]) {
+        const int neos = min(rs[RS_LP_NEOS], VC_MAX_EOS_EXTRA);
+        if (tid <= neos) {
+            const int t = tid == 0 ? rs[RS_EOS] : rs[RS_LP_EOS + tid - 1];
+            if ((unsigned)t < (unsigned)V) out[t] = -INFINITY;
+        }
+    }
+}
+void launch_logits_process(const LogitsProcessArgs& a, int nrows, hipStream_t s) {
+    if (nrows <= 0) return;
+    VC_LAUNCH(logits_process_kernel, dim3((unsigned)nrows), dim3(LPROC_THREADS), 0, s, a);
+}
+
 // ---- one beam-search step on the device (kernels.h BeamStepArgs; [HF] generation/utils.py beam_search + beam_search.py
 // BeamSearchScorer.process of Transformers 4.31) -----------------------------------------------------------------------------------
 // ONE workgroup, one wave per sequence (B * n <= 16 rows, so the launch holds at most 16 * 32 = 512 candidates): the lanes add

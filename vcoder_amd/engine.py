@@ -8,6 +8,7 @@ from typing import Sequence, Dict, Optional, Tuple
 import numpy as np
 
 from . import _lib, synth
+from . import logits_processors as _lp
 from .config import VCoderConfig
 
 _ERRORS = {_lib.VC_ERR_INVALID: ValueError, _lib.VC_ERR_HIP: RuntimeError, _lib.VC_ERR_STATE: RuntimeError,
@@ -580,7 +581,7 @@ class HipEngine:
                  stop_sequences: Optional[Sequence[Sequence[int]]] = None, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                  on_tokens=None, stream_every: int = 1, attention_mask=None, logprobs: bool = False,
-                 top_logprobs: int = 0) -> np.ndarray:
+                 top_logprobs: int = 0, processors=None, eos_extra: Sequence[int] = ()) -> np.ndarray:
         """generate() on the device (vc_generate): greedy, or temperature / top-k / top-p sampling with a counter-based
         generator (same seed -> same tokens).  on_tokens(first_step, ids [B, n]) is called with every `stream_every` new
         columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32.
@@ -588,9 +589,19 @@ class HipEngine:
         top_logprobs [B, n, K] float32, top_ids [B, n, K] int32) of the n columns returned — log_softmax of every step's fp32 logits,
         the model's own distribution before temperature / top-k / top-p; a row's finishing token is scored, positions behind it hold
         0.0 / 0.0 / -1.  The call then runs on the session's own loop (not in the decode pool); the ids are the same.  None when not
-        asked."""
+        asked.
+        processors (a logits_processors.LogitsProcessors; vc_request_logits_processors): repetition penalty, no-repeat n-gram, bad
+        words and min_new_tokens / min_length applied on the device in front of every selection, over the history input_ids +
+        generated ids (ids outside the vocabulary — the image placeholders — are skipped, where HF would raise); eos_extra: the
+        further ids of an EOS list, which min_new_tokens bans beside eos_token_id.  At most 32 bad words of at most 8 ids
+        (ValueError otherwise).  The call runs on the session's own loop; log-probs stay those of the raw logits."""
         ids = self._ids(input_ids)
         B, T = ids.shape
+        if processors is not None and not processors.active:
+            processors = None
+        if processors is not None and (not processors.fits_device() or len(eos_extra) > _lp.MAX_EOS_EXTRA):
+            raise ValueError(f"the device loop holds at most {_lp.MAX_BAD_WORDS} bad-word sequences of at most {_lp.MAX_BAD_WORD_LEN} "
+                             f"ids and {_lp.MAX_EOS_EXTRA} further EOS ids")
         K = self._top_k(top_logprobs)
         want_lp = bool(logprobs) or K > 0
         self.last_generate_logprobs = None
@@ -609,7 +620,7 @@ class HipEngine:
                                            max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                            pad_token_id=pad_token_id, stop_sequences=stop_sequences, do_sample=do_sample,
                                            temperature=temperature, top_k=top_k, top_p=top_p, seed=seed + b0,
-                                           logprobs=want_lp, top_logprobs=K))
+                                           logprobs=want_lp, top_logprobs=K, processors=processors, eos_extra=eos_extra))
                 lps.append(self.last_generate_logprobs)
                 lens.add(int(self.lib.vc_last_spliced_len(self._model)))
             if len(lens) > 1:
@@ -655,6 +666,22 @@ class HipEngine:
                                                                   top_id.ctypes.data_as(C.c_void_p) if K else None, C.c_size_t(rows)))
             except BaseException:
                 self.lib.vc_clear_attention_mask(self._model)
+                raise
+        if processors is not None:
+            bad = processors.bad_words_ids
+            bad_flat = np.ascontiguousarray([t for q in bad for t in q], dtype=np.int32)
+            bad_lens = np.ascontiguousarray([len(q) for q in bad], dtype=np.int32)
+            extra = np.ascontiguousarray([int(e) for e in eos_extra], dtype=np.int32)
+            req = _lib.LogitsProcessors(float(processors.repetition_penalty), int(processors.no_repeat_ngram_size),
+                                        int(processors.min_new_for(T)), len(bad),
+                                        bad_flat.ctypes.data_as(C.c_void_p) if bad else None,
+                                        bad_lens.ctypes.data_as(C.c_void_p) if bad else None, len(extra),
+                                        extra.ctypes.data_as(C.c_void_p) if len(extra) else None)
+            try:
+                self._check(self.lib.vc_request_logits_processors(self._model, C.byref(req)))
+            except BaseException:
+                self.lib.vc_clear_attention_mask(self._model)
+                self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
                 raise
         self._check(self.lib.vc_generate(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev,
                                          int(max_new_tokens), eos, pad,

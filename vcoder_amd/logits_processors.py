@@ -1,0 +1,110 @@
+"""The logits processors generate() serves (HF GenerationMixin arguments repetition_penalty, no_repeat_ngram_size, bad_words_ids,
+min_length, min_new_tokens): their validation, the form the engine takes (vc_request_logits_processors) and ONE torch restatement in
+the order of Transformers 4.31's `_get_logits_processor` — repetition penalty, no-repeat n-gram, bad words, min length, min new
+tokens — which the host fallback loop of generate() and the host beam search apply.  The device loop runs the same processors in
+logits_process_kernel (csrc/select.hip).
+
+A row's history is the caller's input_ids (image placeholders and all: HF counts the un-spliced ids) followed by the generated ids.
+History ids outside [0, vocab) are skipped: HF's RepetitionPenaltyLogitsProcessor would raise an index error on the negative image
+placeholders, and a banned id outside the vocabulary bans nothing."""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import List, Optional, Sequence
+
+MAX_BAD_WORDS = 32      # what the device kernel holds (csrc/kernels.h VC_MAX_BAD_WORDS / VC_MAX_BAD_WORD_LEN / VC_MAX_EOS_EXTRA)
+MAX_BAD_WORD_LEN = 8
+MAX_EOS_EXTRA = 8
+
+
+@dataclass
+class LogitsProcessors:
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
+    min_length: int = 0
+    bad_words_ids: List[List[int]] = field(default_factory=list)
+
+    @property
+    def active(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0 or self.min_new_tokens > 0 or self.min_length > 0
+                or bool(self.bad_words_ids))
+
+    def fits_device(self) -> bool:
+        return len(self.bad_words_ids) <= MAX_BAD_WORDS and all(len(q) <= MAX_BAD_WORD_LEN for q in self.bad_words_ids)
+
+    def min_new_for(self, T: int) -> int:
+        """min_length folded into min_new_tokens for a prompt of T ids (both ban the EOS ids, -inf twice is -inf once)"""
+        return max(int(self.min_new_tokens), int(self.min_length) - int(T), 0)
+
+
+def make(repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, min_length=None, bad_words_ids=None,
+         eos_ids: Sequence[int] = ()) -> LogitsProcessors:
+    """validates generate()'s arguments (ValueError, as HF's processors raise it) -> LogitsProcessors.  None = the default (off).
+    Bad words that are exactly one EOS id are dropped, as NoBadWordsLogitsProcessor drops them."""
+    import math
+
+    p = 1.0 if repetition_penalty is None else repetition_penalty
+    if not isinstance(p, (int, float)) or isinstance(p, bool) or not (p > 0) or not math.isfinite(p):
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty}")
+
+    def count(name, v):
+        v = 0 if v is None else v
+        if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+            raise ValueError(f"`{name}` has to be a non-negative integer, but is {v}")
+        return v
+
+    n = count("no_repeat_ngram_size", no_repeat_ngram_size)
+    m = count("min_new_tokens", min_new_tokens)
+    ml = count("min_length", min_length)
+    bad = []
+    if bad_words_ids is not None:
+        if not isinstance(bad_words_ids, (list, tuple)) or len(bad_words_ids) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bad_words_ids}.")
+        for q in bad_words_ids:
+            if not isinstance(q, (list, tuple)) or len(q) == 0:
+                raise ValueError(f"`bad_words_ids` has to be a list of non-empty lists, but is {bad_words_ids}.")
+            if any(not isinstance(t, int) or isinstance(t, bool) or t < 0 for t in q):
+                raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bad_words_ids}.")
+        eos = {int(e) for e in eos_ids}
+        bad = [[int(t) for t in q] for q in bad_words_ids if not (len(q) == 1 and int(q[0]) in eos)]
+    return LogitsProcessors(float(p), n, m, ml, bad)
+
+
+def apply_torch(proc: LogitsProcessors, history, scores, prompt_len: int, eos_ids: Sequence[int]):
+    """`scores` [R, V] float32 of the next token behind `history` [R, L] int64 (prompt_len prompt ids, then the generated ones)
+    -> the processed scores (a new tensor).  HF 4.31's order; fp32 arithmetic (the penalty's division is torch's IEEE division)."""
+    import torch
+
+    out = scores.clone()
+    R, V = out.shape
+    L = history.shape[1]
+    hist = [[int(t) for t in row] for row in history.tolist()]
+    if proc.repetition_penalty != 1.0:
+        for r in range(R):
+            ids = sorted({t for t in hist[r] if 0 <= t < V})
+            if not ids:
+                continue
+            idx = torch.tensor(ids, dtype=torch.long)
+            s = scores[r, idx]
+            out[r, idx] = torch.where(s < 0, s * proc.repetition_penalty, s / proc.repetition_penalty)
+    ninf = float("-inf")
+    n = proc.no_repeat_ngram_size
+    if n > 0 and L + 1 >= n:
+        for r in range(R):
+            h = hist[r]
+            tail = h[L - n + 1:] if n > 1 else []
+            for i in range(L - n + 1):
+                if h[i:i + n - 1] == tail and 0 <= h[i + n - 1] < V:
+                    out[r, h[i + n - 1]] = ninf
+    for q in proc.bad_words_ids:
+        if not 0 <= q[-1] < V:
+            continue
+        pre = q[:-1]
+        for r in range(R):
+            if not pre or (len(pre) <= L and hist[r][L - len(pre):] == pre):
+                out[r, q[-1]] = ninf
+    eos = [int(e) for e in eos_ids if 0 <= int(e) < V]
+    if eos and (L < proc.min_length or L - prompt_len < proc.min_new_tokens):
+        out[:, eos] = ninf
+    return out

@@ -16,6 +16,7 @@ from typing import Optional
 import numpy as np
 
 from ..config import VCoderConfig
+from .. import logits_processors as _lp
 from ..engine import HipEngine
 from .projector import build_depth_projector, build_seg_projector, build_vision_projector
 from .vision_tower import build_vision_tower
@@ -447,7 +448,9 @@ class _HipCausalLMBase:
                  max_new_tokens: Optional[int] = None, max_length: Optional[int] = None, streamer=None,
                  use_cache: bool = True, stopping_criteria=None, eos_token_id=None, pad_token_id=None,
                  attention_mask=None, generator=None, seed: Optional[int] = None, return_dict_in_generate: bool = False,
-                 output_logprobs: bool = False, top_logprobs: int = 0, **kwargs):
+                 output_logprobs: bool = False, top_logprobs: int = 0, repetition_penalty: Optional[float] = None,
+                 no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
+                 bad_words_ids=None, processors_on_device: bool = True, **kwargs):
         """Returns cat(input_ids, new_ids) [B, T+n] int64 — the prompt part keeps its negative placeholder ids,
         callers slice `[:, T:]` (serve/cli.py:135).
 
@@ -461,6 +464,20 @@ class _HipCausalLMBase:
         a kernel behind every selection of the device loop (the call then runs on the session's own loop, not in the decode pool);
         the host fallback loop computes the same from its logits.  HF's full-vocabulary `output_scores` is not implemented: with
         return_dict_in_generate it raises, alone it is ignored as before.
+
+        repetition_penalty (1.0) / no_repeat_ngram_size (0) / bad_words_ids (None) / min_length (0) / min_new_tokens (0): HF's logits
+        processors, in 4.31's order, over the history input_ids + generated ids — RepetitionPenaltyLogitsProcessor
+        (score < 0 ? score * p : score / p), NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor (sequences that are one EOS id
+        are dropped), MinLengthLogitsProcessor (counts the un-spliced input_ids, like HF) and MinNewTokensLengthLogitsProcessor (every
+        EOS id is -inf; stop sequences are unaffected).  History ids outside the vocabulary — the negative image placeholders — are
+        skipped; HF itself would raise an index error on them in the repetition penalty.  With the defaults nothing changes (the
+        call takes the path it took, decode pool included).  Otherwise a kernel in front of every selection of the device loop
+        applies them (greedy and sampled calls; the call runs on the session's own loop); more than 32 bad words, one longer than 8
+        ids, more than 9 EOS ids or processors_on_device=False take the host loop, which applies the same processors in torch in
+        front of the warpers and returns the same ids.  Beam search with a processor set runs on the host loop, which applies them to
+        log_softmax(logits) before the beam scores are added, as 4.31's beam_search.  Log-probs (output_logprobs / top_logprobs)
+        stay those of the model's own distribution: the raw logits, before processors as well as before warpers.  Invalid values
+        raise ValueError before the engine is touched.
 
         num_beams = n > 1: beam search (HF 4.31's beam_search + BeamSearchScorer; `length_penalty`, `early_stopping` as keyword
         arguments).  Without sampling and stopping criteria, outside strict mode and with B * n <= 16 rows it runs inside the device
@@ -493,6 +510,11 @@ class _HipCausalLMBase:
                                       "output_logprobs=True / top_logprobs=K instead")
         if num_beams != 1 and want_lp:
             raise NotImplementedError("per-token log-probs (output_logprobs / top_logprobs) are not implemented for num_beams != 1")
+        eos_all = self.config.eos_token_id if eos_token_id is None else eos_token_id
+        eos_all = [int(e) for e in (eos_all if isinstance(eos_all, (list, tuple)) else ([] if eos_all is None else [eos_all]))]
+        proc = _lp.make(repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, bad_words_ids, eos_all)
+        if not proc.active:
+            proc = None
         if num_beams != 1:
             if streamer is not None:
                 raise ValueError("`streamer` cannot be used with beam search")   # HF's own check
@@ -508,12 +530,13 @@ class _HipCausalLMBase:
                        kwargs.get("_beam_len_counts_prompt", True))
             # plain beam search (what the reference's eval loaders ask for) runs inside the device loop; beam-sample, stopping
             # criteria, strict mode and more rows than a replica decodes keep the host loop
-            on_device = (kwargs.get("beam_on_device", True) and sample is None and not stopping_criteria
+            # (logits processors too: the device beam loop does not carry them)
+            on_device = (kwargs.get("beam_on_device", True) and sample is None and not stopping_criteria and proc is None
                          and self.engine.precision != "strict" and input_ids.shape[0] * int(num_beams) <= self.engine.MAX_BATCH)
             if on_device:
                 seqs, scores = self._beam_search_device(*beam_args, *beam_kw)
             else:
-                seqs, scores = self._beam_search(*beam_args, stopping_criteria, *beam_kw, sample, return_scores=True)
+                seqs, scores = self._beam_search(*beam_args, stopping_criteria, *beam_kw, sample, return_scores=True, processors=proc)
             return GenerateOutput(sequences=seqs, sequences_scores=scores) if as_dict else seqs
         T = input_ids.shape[1]
         B = input_ids.shape[0]
@@ -549,6 +572,8 @@ class _HipCausalLMBase:
         if stops is not None:
             stops = stops + [[e] for e in eos_more]
         on_device = stops is not None and len(stops) <= 8
+        if proc is not None:   # what the device kernel does not hold, or the caller's wish: the host loop applies them
+            on_device = on_device and bool(processors_on_device) and proc.fits_device() and len(eos_more) <= _lp.MAX_EOS_EXTRA
         if streamer is not None:
             streamer.put(ids_cpu)
         if on_device:
@@ -562,7 +587,8 @@ class _HipCausalLMBase:
                                        do_sample=bool(do_sample), temperature=float(temperature or 1.0),
                                        top_k=top_k or 0, top_p=1.0 if top_p is None else top_p, seed=seed or 0,
                                        on_tokens=on_tokens, stream_every=kwargs.get("stream_every", 1),
-                                       attention_mask=attention_mask, logprobs=want_lp, top_logprobs=K)
+                                       attention_mask=attention_mask, logprobs=want_lp, top_logprobs=K, processors=proc,
+                                       eos_extra=eos_more if proc is not None else ())
             self._generation += 1
             out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
             if want_lp:
@@ -585,6 +611,8 @@ class _HipCausalLMBase:
             for step in range(max_new_tokens):
                 scores = logits.float()
                 raw = scores
+                if proc is not None:   # in front of the warpers, as HF; the log-probs below stay those of `raw`
+                    scores = _lp.apply_torch(proc, cur, scores, T, ([] if eos is None else [int(eos)]) + eos_more)
                 if do_sample:
                     scores = scores / float(temperature)
                     if top_k and 0 < top_k < scores.shape[-1]:
@@ -677,7 +705,7 @@ class _HipCausalLMBase:
 
     def _beam_search(self, input_ids, images, segs, depths, num_beams, max_new_tokens, max_length, eos_token_id, pad_token_id,
                      attention_mask, stopping_criteria, length_penalty, early_stopping, len_counts_prompt, sample=None,
-                     return_scores=False):
+                     return_scores=False, processors=None):
         """`generate(num_beams=n)` as the reference's eval loaders can ask for it (eval/model_seg_loader.py:129-139 forwards
         args.num_beams): every sequence is expanded to n beams (rows b*n .. b*n+n-1, as `_expand_inputs_for_generation`), the
         prefill and one cached decode step per token run on the engine, scoring is HF's — log-softmax of the fp32 logits plus
@@ -691,7 +719,10 @@ class _HipCausalLMBase:
         them, `torch.multinomial(softmax(.), 2n)` over the n * V continuations, the draws sorted by score — everything behind it
         (EOS handling, hypotheses, cache reorder) is the beam search's.  The draws come from the caller's torch generator
         (or `seed`), so a seed reproduces them; bit-equality with a given HF version's stream is not defined (its warper
-        order changed after 4.31)."""
+        order changed after 4.31).
+
+        processors (logits_processors.LogitsProcessors): applied to log_softmax(logits) over every beam row's ids before the running
+        beam score is added, as 4.31's beam_search / beam_sample apply their logits_processor."""
         import torch
 
         ids_cpu = input_ids.detach().cpu() if hasattr(input_ids, "detach") else torch.as_tensor(np.asarray(input_ids))
@@ -761,7 +792,10 @@ class _HipCausalLMBase:
         logits = torch.from_numpy(last).float()
         n_steps = 0
         for step in range(max_new_tokens):
-            scores = torch.log_softmax(logits, dim=-1) + beam_scores[:, None]
+            scores = torch.log_softmax(logits, dim=-1)
+            if processors is not None:
+                scores = _lp.apply_torch(processors, seqs, scores, T, eos_list)
+            scores = scores + beam_scores[:, None]
             if sample is not None:
                 w = scores / sample["temperature"]
                 if 0 < sample["top_k"] < V:
