@@ -125,6 +125,9 @@ int vc_model_set_layer_limit(vc_model* m, int n_layers);
  * = the residual stream behind layer l1 - 1.  Every layer can be fed the oracle's own input, so that rounding / quantisation
  * noise of the layers in front of it does not compound (tests/test_gpu_e2e.py: fp8 formats per layer). */
 int vc_debug_prefill_layers(vc_model* m, int l0, int l1, const float* x_in, int B, int S, float* x_out);
+/* Test hook: captures of a decode step (hipGraph) the session's own loop has performed so far — vc_decode_step, vc_generate* on the
+ * session, vc_generate_beam; the shared pool's are not counted.  A call that replays the step it finds adds 0. */
+int vc_debug_step_captures(vc_model* m);
 
 /* decoder weight storage: 0 = bf16 (default); 1 = W8A16 — the seven linears of every decoder layer are quantised at
  * vc_model_finalize to OCP fp8 e4m3 with one power-of-two scale per output row and streamed as bytes by the decode

@@ -348,6 +348,16 @@ def check_followed_by_plain(model, mode="bf16", B=2):
         # a larger max_new than any call before (the slabs grow) and another K (another captured step)
         more = eng.generate(*args, max_new_tokens=N_NEW + 3, logprobs=True, top_logprobs=2)
         assert np.array_equal(more[:, :N_NEW], plain) and eng.last_generate_logprobs[1].shape == (B, N_NEW + 3, 2)
+        # decode_step(None) directly behind a call with log-probs AND a processor: the plain step (raw logits, greedy choice), from the
+        # token that call selected on the device
+        from vcoder_amd import logits_processors
+        proc = logits_processors.make(repetition_penalty=1.3, bad_words_ids=[[int(plain[0, 1])]])
+        new = eng.generate(*args, max_new_tokens=4, logprobs=True, top_logprobs=2, processors=proc)
+        assert new.shape == (B, 4) and new[0, 1] != plain[0, 1], "the processors change nothing: the case shows nothing"
+        got3, nxt3 = eng.decode_step(None)
+        want3 = replay_logits(model, ids, px, np.concatenate([new, new[:, :1]], axis=1))[-1]   # the logits behind tokens 0 .. 3
+        assert np.array_equal(got3, want3), "a plain decode_step behind a log-prob + processor generate differs"
+        assert np.array_equal(nxt3, np.argmax(want3, axis=1)), "the plain step behind a processed call ran the processors"
     finally:
         eng.set_precision("bf16")
 

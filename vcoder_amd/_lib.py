@@ -103,6 +103,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_model_set_layer_limit.restype = C.c_int
     lib.vc_debug_prefill_layers.argtypes = [vp, i32, i32, vp, i32, i32, vp]
     lib.vc_debug_prefill_layers.restype = C.c_int
+    lib.vc_debug_step_captures.argtypes = [vp]
+    lib.vc_debug_step_captures.restype = C.c_int
     lib.vc_reorder_cache.argtypes = [vp, vp, i32]
     lib.vc_reorder_cache.restype = C.c_int
     lib.vc_generate_beam.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, i32, i32, C.c_float, i32, i32, vp, vp, vp,

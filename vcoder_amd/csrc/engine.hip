@@ -123,6 +123,116 @@ struct Projector {
     std::vector<float*> b;
 };
 
+// Everything one decode step touches besides the weights: the buffers of a session's own loop or of the shared pool.
+struct LoopView {
+    hipStream_t st;
+    bf16_t *kc, *vc;   // [L][capR][H][capS][hd]: K and V, both key-major (fp32 elements when es == 4)
+    int es;            // bytes per cache element: 2 (bf16); precision mode "split": 3 (fp24) or 4 (fp32)
+    int split_G;       // 0: bf16 decode step.  G = 8 / 16: split decode step — xg_dec / attn_dec / h_dec hold stacked groups of
+                       // G bf16 hi rows + G lo rows (row r -> group r / G), qkv_dec is fp32
+    int capR, capS;
+    int* rows;         // RowState records
+    const uint8_t* kmask;  // keys hidden from the rows' decode steps ([rows][kmask_stride] bytes, 0 = hidden), or nullptr
+    int kmask_stride;      // (4 bytes of padding follow: a new 4-byte member here keeps sizeof — extend operator== below yourself)
+    float* x_dec;
+    bf16_t *xg_dec, *qkv_dec, *attn_dec, *h_dec;
+    float* logits;
+    int *next_tok, *out_ids;
+    float *ssq, *sk_scratch;
+    unsigned* sk_counters;
+    // in-situ timing (vc_pool_profile): slot s of the step = stamps + s * STAMP_SLOT_WORDS; *stamp_next = the next free slot while
+    // the step is being enqueued; prof_acc = this span's accumulators.  All nullptr when off.
+    unsigned* stamps;
+    int* stamp_next;
+    unsigned long long* prof_acc;
+    unsigned* stamp_scratch;
+    // per-token log-probs of a generate() call (vc_request_generate_logprobs): slabs laid out like out_ids — the chosen token's
+    // log-prob [slots], the lp_k most likely tokens [slots, lp_k].  lp_tok == nullptr (every view but the one such a call makes for
+    // itself): the step has no log-prob launch.
+    float *lp_tok, *lp_top;
+    int* lp_ids;
+    int lp_k;              // (padding follows, as behind kmask_stride)
+    // logits processors of a generate() call (vc_request_logits_processors): the call's prompt ids and bad-word table, and the
+    // processed rows the selection then reads.  proc_logits == nullptr (every view but the one such a call makes for itself): no
+    // processor launch, the selection reads the raw rows.
+    const int *proc_prompt, *proc_bad;
+    float* proc_logits;
+};
+inline bool operator==(const LoopView& a, const LoopView& b) {
+    static_assert(sizeof(LoopView) == 240, "LoopView changed: compare the new member here");
+    return a.st == b.st && a.kc == b.kc && a.vc == b.vc && a.es == b.es && a.split_G == b.split_G && a.capR == b.capR &&
+           a.capS == b.capS && a.rows == b.rows && a.kmask == b.kmask && a.kmask_stride == b.kmask_stride && a.x_dec == b.x_dec &&
+           a.xg_dec == b.xg_dec && a.qkv_dec == b.qkv_dec && a.attn_dec == b.attn_dec && a.h_dec == b.h_dec && a.logits == b.logits &&
+           a.next_tok == b.next_tok && a.out_ids == b.out_ids && a.ssq == b.ssq && a.sk_scratch == b.sk_scratch &&
+           a.sk_counters == b.sk_counters && a.stamps == b.stamps && a.stamp_next == b.stamp_next && a.prof_acc == b.prof_acc &&
+           a.stamp_scratch == b.stamp_scratch && a.lp_tok == b.lp_tok && a.lp_top == b.lp_top && a.lp_ids == b.lp_ids &&
+           a.lp_k == b.lp_k && a.proc_prompt == b.proc_prompt && a.proc_bad == b.proc_bad && a.proc_logits == b.proc_logits;
+}
+
+// The buffers of the device beam loop (vc_generate_beam): the fixed-size part carved from m->bm_state, the tables from m->bm_tab /
+// m->bm_den, the staging of the tail permute (ensure_beam sizes them; beam_view fills this in).
+struct BeamLoop {
+    float* cand_lp;   // [16, 32]
+    int* cand_id;
+    float* score;     // [16]
+    int *perm, *start, *seq, *hyp, *params, *flags;
+    int *tok_tab, *parent_tab;   // [cap_new][R]
+    float *hyp_den, *done_den;   // [cap_new + 1]
+    void* tmp;                   // the tail permute's staging: 2 R heads spans of span_cap bytes
+    size_t span_cap;             // bytes one (row, head) of the staging holds: the cache rows of cap_new positions
+    int B, n, cap_new;           // (4 bytes of padding follow: a new 4-byte member here keeps sizeof — extend operator== yourself)
+};
+inline bool operator==(const BeamLoop& a, const BeamLoop& b) {
+    static_assert(sizeof(BeamLoop) == 136, "BeamLoop changed: compare the new member here");
+    return a.cand_lp == b.cand_lp && a.cand_id == b.cand_id && a.score == b.score && a.perm == b.perm && a.start == b.start &&
+           a.seq == b.seq && a.hyp == b.hyp && a.params == b.params && a.flags == b.flags && a.tok_tab == b.tok_tab &&
+           a.parent_tab == b.parent_tab && a.hyp_den == b.hyp_den && a.done_den == b.done_den && a.tmp == b.tmp &&
+           a.span_cap == b.span_cap && a.B == b.B && a.n == b.n && a.cap_new == b.cap_new;
+}
+
+// What a captured decode step of a session was enqueued from, and so the condition under which its hipGraphExec_t may be replayed:
+// a step is replayed iff the key of the step the caller asks for equals the key it was captured from (step_graph).
+//
+// Audit of what enqueue_decode_step / enqueue_selection / enqueue_beam_tail hand to a launch.  Every value is
+//   (a) fixed after vc_model_finalize: the weights, their scales and lo planes (lo_of), embed, the norm weights, the RoPE tables, the
+//       config (hidden, ffn, heads, layers, vocab, rms_eps, max_positions), hd, npart, the weight format, sk_floats / sk_counters_n
+//       (functions of the config), the RS_* / B?_* record layouts, the `advance` constant of a captured step (3);
+//   (b) a member of the key: every LoopView member (the stream, the caches with es / capR / capS, the RowState records, the key mask
+//       pointer — nullptr for an unmasked step — and its stride, the per-step buffers, out_ids, the split-K scratch and counters, the
+//       timing pointers, the log-prob slabs with lp_k, the processor buffers), nrows, and for a beam step every BeamLoop member (the
+//       state pointers, the tables, the staging with its span capacity, B, n, cap_new); or
+//   (c) derived from (a) and (b) alone: the per-layer cache addresses (kc / vc, capR, capS, es, heads, hd), the attention's cache
+//       format (split_G, es), the GEMV pass layout (split_G, nrows), which launches the tail holds (lp_tok, proc_logits, has_beam),
+//       the beam rows R = B n.
+// Two things a step bakes in are none of these and keep an explicit drop_graph:
+//   - m->precision, which select_args and the beam tail read for the embedding's lo plane: vc_model_set_precision drops the steps
+//     (the strict mode, 1, never captures one);
+//   - the model's life: vc_model_destroy.
+// Sizes matter as much as addresses: a buffer freed and allocated again may come back at the same address (B 2 -> 3 keeps the
+// 16-row-padded step buffers and re-allocates the KV cache), so every capacity a launch bakes in — capR, capS, es, cap_new and the
+// span capacity, lp_k — is a key member as well.  Capacities no launch bakes in are not: the rows' slots in out_ids and the slabs
+// come from RS_OUT_OFF of the records, so out_stride is not part of a step.
+// Baked in and NOT keyed, as before: the process-wide kernel-selection knobs of kernel_api.cpp that a decode step's launchers read —
+// vck_set_gemv_variant and vck_set_gemv_wide (the third, vck_set_gemm_force_8phase, concerns the prefill GEMMs only) — and the
+// VC_SPLIT_KV environment switch (read once per process; it shows in es anyway).  A step captured before one of the knobs is turned stays
+// on the kernels it was captured with.
+struct StepKey {
+    LoopView view;
+    int nrows;
+    bool has_beam;
+    BeamLoop beam;   // zeroes without one
+};
+inline bool operator==(const StepKey& a, const StepKey& b) {
+    static_assert(sizeof(StepKey) == sizeof(LoopView) + 8 + sizeof(BeamLoop), "StepKey changed: compare the new member here");
+    return a.view == b.view && a.nrows == b.nrows && a.has_beam == b.has_beam && a.beam == b.beam;
+}
+// one captured step per kind, so that a plain vc_decode_step behind a log-prob or a beam call replays without a re-capture
+enum StepKind { STEP_PLAIN = 0, STEP_CALL = 1 /* a generate() call's own: log-probs and / or processors */, STEP_BEAM = 2, STEP_KINDS = 3 };
+struct StepGraph {
+    StepKey key{};
+    hipGraphExec_t exec = nullptr;
+};
+
 }  // namespace
 
 struct vc_model {
@@ -177,7 +287,6 @@ struct vc_model {
     Buf kmask;
     bool has_kmask = false;         // the current prefill hides keys
     bool kmask_in_decode = false;   // ... and the session's decode steps keep hiding them (vc_decode_step loops)
-    bool graph_masked = false;      // what the captured decode graph was built for
     // output_hidden_states of the NEXT vc_prefill (vc_request_hidden_states; one-shot): host buffer [(L + 1), B, S, hidden]
     float* hidden_out = nullptr;
     size_t hidden_cap = 0;        // floats
@@ -204,26 +313,23 @@ struct vc_model {
     size_t stk_cap = 0;
     Buf sc_tlp, sc_tid;           // scored rows x top_k: log-probs and ids of one call
     // per-token log-probs of the NEXT vc_generate* (vc_request_generate_logprobs; one-shot): the host buffers [B, max_new] and
-    // [B, max_new, top_k] (cap_rows rows each), and — while that call runs on the session's loop — lp_on: the loop's steps then
-    // carry a topk_logprob launch behind their selection, writing the slabs below (laid out like out_ids: row stride out_stride)
+    // [B, max_new, top_k] (cap_rows rows each).  A call that runs on the session's loop attaches the slabs below (laid out like
+    // out_ids: row stride out_stride) to its own copy of the loop's view: its steps then carry a topk_logprob launch behind their selection
     int glp_k = 0;
     float* glp_tok = nullptr;
     float* glp_top = nullptr;
     int32_t* glp_ids = nullptr;
     size_t glp_cap = 0;
-    bool lp_on = false;
-    int lp_k = 0;
     Buf lp_tok, lp_top, lp_ids;
     // logits processors of the NEXT vc_generate* (vc_request_logits_processors; one-shot), copied from the caller's struct: the
-    // bad-word table as the kernel reads it ([VC_MAX_BAD_WORDS][1 + VC_MAX_BAD_WORD_LEN]: length, ids).  While that call runs on
-    // the session's loop — proc_on — every selection is preceded by logits_process_kernel: the call's prompt ids and table in
-    // proc_prompt / proc_bad, the processed rows in proc_logits [B, V]
+    // bad-word table as the kernel reads it ([VC_MAX_BAD_WORDS][1 + VC_MAX_BAD_WORD_LEN]: length, ids).  A call that runs on the
+    // session's loop attaches proc_prompt / proc_bad (its prompt ids and table) and proc_logits (the processed rows [B, V]) to its own
+    // copy of the loop's view: every selection is then preceded by logits_process_kernel
     bool gproc = false;
     float gproc_penalty = 1.f;
     int gproc_ngram = 0, gproc_minnew = 0, gproc_nbad = 0, gproc_neos = 0;
     int gproc_eos[VC_MAX_EOS_EXTRA] = {};
     std::vector<int> gproc_bad;
-    bool proc_on = false;
     Buf proc_prompt, proc_bad, proc_logits;
     bool tok_stale = false;       // vc_rewind ran: the token the last step selected on the device no longer continues the sequence
     bool plan_only = false;       // do_prefill stops behind the splice plan (vc_plan_spliced_len): no tower pass, no state change
@@ -243,20 +349,16 @@ struct vc_model {
     Buf gemm_ws;                  // fp32 workspace of the GEMM's split-K remainder round (64 MiB)
     int out_stride = 0;           // out_ids ints per row
     int last_S = 0;               // spliced prompt length of the last prefill / generate
-    hipGraphExec_t graph = nullptr;  // one decode step over graph_rows rows (parameters live in the RowState records)
-    int graph_rows = 0;
-    hipGraphExec_t graph_lp = nullptr;   // the same step with the log-prob launch (lp_on), for graph_lp_k alternatives
-    int graph_lp_rows = 0, graph_lp_k = 0;
-    bool graph_lp_masked = false, graph_lp_proc = false;   // (graph_lp also serves proc_on: with the processor launch in front of the selection)
-    // the device beam loop (vc_generate_beam; engine_llm.inc BeamLoop): bm_state holds the fixed-size part (candidates, beam scores,
-    // perm, prompt lengths, sequence records, hypotheses, parameters, flags), bm_tab the tok / parent tables, bm_den the two
-    // denominator tables, bm_tmp the staging of the tail permute — the last three sized for bm_cap_new steps.  graph_beam is one
-    // captured beam step over graph_beam_rows rows of graph_beam_n beams, kept beside the plain and the log-prob step.
+    // the captured decode steps of the session's loop, one per kind (StepKind above): each is replayed while the description
+    // of the step a caller asks for equals the one it was captured from (StepKey: every address and size the launches bake in), and
+    // re-captured otherwise.  The per-row parameters live in the RowState records, not in the graph.
+    StepGraph step[STEP_KINDS];
+    int step_captures = 0;        // captures of this session so far (vc_debug_step_captures)
+    // the device beam loop (vc_generate_beam; BeamLoop): bm_state holds the fixed-size part (candidates, beam scores, perm, prompt
+    // lengths, sequence records, hypotheses, parameters, flags), bm_tab the tok / parent tables, bm_den the two denominator tables,
+    // bm_tmp the staging of the tail permute — the last three sized for bm_cap_new steps
     Buf bm_state, bm_tab, bm_den, bm_tmp;
     int bm_cap_new = 0;
-    hipGraphExec_t graph_beam = nullptr;
-    int graph_beam_rows = 0, graph_beam_n = 0, graph_beam_cap_new = 0;
-    bool graph_beam_masked = false;
     struct vc_pool* pool = nullptr;  // the root model's shared decode pool (created on first use; sessions point at it)
     bool pool_profile = false;       // root model: the pool's step graphs carry in-situ timing stamps (vc_pool_profile)
     bool fp8_kv = true;              // weight format 2: the KV cache of the bf16-step modes in e4m3 (vc_model_set_fp8_kv)

@@ -176,7 +176,7 @@ VC_API void vc_model_destroy(vc_model* m) {
         pool_destroy(m->pool);
         m->pool = nullptr;
     }
-    drop_graph(m);
+    drop_graph(m);   // (StepKey: the model's life is no key member)
     if (m->owns_weights)
         for (void* p : m->owned) (void)hipFree(p);
     for (Buf* b : {&m->stage, &m->stage2, &m->v_pixels, &m->v_cols, &m->v_patches, &m->v_x, &m->v_xn, &m->v_qkv, &m->v_q,
@@ -281,7 +281,7 @@ VC_API int vc_model_set_precision(vc_model* m, int mode) {
             return VC_ERR_STATE;
         }
     }
-    if (mode != m->precision) {  // the decode graph bakes the step's kernels and buffers in
+    if (mode != m->precision) {  // the captured steps bake m->precision in without it being a member of their key (StepKey)
         (void)hipSetDevice(m->ctx->device);
         (void)hipStreamSynchronize(m->st);
         drop_graph(m);
@@ -722,7 +722,7 @@ VC_API int vc_prefill(vc_model* m, const int64_t* ids, int B, int T, const float
     GenParams g;
     arm_session_rows(m, g, nullptr);
     const LoopView v = session_view(m);
-    launch_select_embed(select_args(m, v, v.logits, B, 0), m->st);
+    enqueue_selection(m, v, v.logits, B, 0);
     HIPCHK(hipStreamSynchronize(m->st));
     if (logits_last) {
         HIPCHK(hipMemcpyAsync(logits_last, m->logits.p, (size_t)B * m->c.vocab * 4, hipMemcpyDeviceToHost, m->st));
@@ -800,6 +800,10 @@ VC_API int vc_debug_prefill_layers(vc_model* m, int l0, int l1, const float* x_i
     GUARD_END(m->ctx)
 }
 
+/* Captures of a decode step this session has performed so far (the session's own loop: vc_decode_step, vc_generate* with the pool
+ * off, vc_generate_beam; not the pool's).  A test hook: a call that replays a captured step adds 0. */
+VC_API int vc_debug_step_captures(vc_model* m) { return m ? m->step_captures : VC_ERR_INVALID; }
+
 /* Beam search support: the KV rows of the session's current loop are permuted, row r <- old row src_rows[r] (live prefix only) —
  * `past_key_values` reordered by beam_idx ([HF] generation/utils.py: _reorder_cache after every beam step). */
 VC_API int vc_reorder_cache(vc_model* m, const int32_t* src_rows, int B) {
@@ -861,12 +865,13 @@ void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* n
             "vc_decode_step(tok = NULL) after vc_rewind: the token selected on the device belongs to the rows that were dropped");
     if (m->cur_pos + 1 > m->capS) grow_kv(m, m->cur_pos + 1);
     const int B = m->curB;
+    const LoopView v = session_view(m);   // the plain step, whatever call ran before
     if (tok) {
         for (int b = 0; b < B; ++b)
             REQUIRE(tok[b] >= 0 && tok[b] < m->c.vocab, VC_ERR_INDEX, "index out of range in self (token id %d)", tok[b]);
         HIPCHK(hipMemcpyAsync(m->next_tok.p, tok, B * 4, hipMemcpyHostToDevice, m->st));
         launch_embed_tokens_ssq(m->next_tok.as<int>(), m->embed, m->x_dec.as<float>(), m->ssq.as<float>(), m->llm[0].in_norm,
-                                m->xg_dec.as<bf16_t>(), B, m->c.hidden, m->npart, m->st, session_view(m).split_G,
+                                m->xg_dec.as<bf16_t>(), B, m->c.hidden, m->npart, m->st, v.split_G,
                                 m->precision ? lo_plane(m, m->embed) : nullptr);
     }
     struct StepRequests {   // one-shot, also when the step fails
@@ -880,11 +885,11 @@ void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* n
         }
     } step_requests{m};
     if (m->precision == 1) {
-        enqueue_decode_step_strict(m, B);
+        enqueue_decode_step_strict(m, v, B);
     } else if (m->hidden_out || m->attn_out) {
-        enqueue_decode_step(m, session_view(m), B, m->cur_pos);
+        enqueue_decode_step(m, v, B, m->cur_pos);
     } else {
-        HIPCHK(hipGraphLaunch(ensure_graph(m, B), m->st));
+        HIPCHK(hipGraphLaunch(step_graph(m, STEP_PLAIN, v, B), m->st));
     }
     m->cur_pos += 1;
     m->tok_stale = false;
@@ -1037,7 +1042,7 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
     for (int b = 0; b < B; ++b) rec[(size_t)b * RS_STRIDE + RS_POS] += n;
     HIPCHK(hipMemcpyAsync(m->rows.p, rec.data(), rec.size() * 4, hipMemcpyHostToDevice, m->st));
     const LoopView v = session_view(m);
-    launch_select_embed(select_args(m, v, v.logits, B, 0), m->st);
+    enqueue_selection(m, v, v.logits, B, 0);
     m->cur_pos = P + n;
     m->tok_stale = false;
     if (logits_all)

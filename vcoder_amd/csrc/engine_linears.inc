@@ -1,5 +1,5 @@
 // engine_linears.inc — part of the host engine (textually included by engine.hip inside its anonymous namespace; one translation unit).
-// GEMM / GEMV call helpers of the engine (split-K workspace, folded RMSNorm, the fused QKV epilogue's arguments), LoopView, the GEMVs of one decode step.
+// GEMM / GEMV call helpers of the engine (split-K workspace, folded RMSNorm, the fused QKV epilogue's arguments), the GEMVs of one decode step.
 
 // ------------------------------------------------------------------------------------------------
 // GEMM helpers
@@ -98,42 +98,6 @@ inline int step_kv_es(const vc_model* m) {
     const vc_model* r = root_of(m);
     return (r->weight_format == 2 && r->fp8_kv) ? 1 : 2;
 }
-
-// Everything one decode step touches besides the weights: the buffers of a session's own loop or of the shared pool.
-struct LoopView {
-    hipStream_t st;
-    bf16_t *kc, *vc;   // [L][capR][H][capS][hd]: K and V, both key-major (fp32 elements when es == 4)
-    int es;            // bytes per cache element: 2 (bf16); precision mode "split": 3 (fp24) or 4 (fp32)
-    int split_G;       // 0: bf16 decode step.  G = 8 / 16: split decode step — xg_dec / attn_dec / h_dec hold stacked groups of
-                       // G bf16 hi rows + G lo rows (row r -> group r / G), qkv_dec is fp32
-    int capR, capS;
-    int* rows;         // RowState records
-    const uint8_t* kmask;  // keys hidden from the rows' decode steps ([rows][kmask_stride] bytes, 0 = hidden), or nullptr
-    int kmask_stride;
-    float* x_dec;
-    bf16_t *xg_dec, *qkv_dec, *attn_dec, *h_dec;
-    float* logits;
-    int *next_tok, *out_ids;
-    float *ssq, *sk_scratch;
-    unsigned* sk_counters;
-    // in-situ timing (vc_pool_profile): slot s of the step = stamps + s * STAMP_SLOT_WORDS; *stamp_next = the next free slot while
-    // the step is being enqueued; prof_acc = this span's accumulators.  All nullptr when off.
-    unsigned* stamps;
-    int* stamp_next;
-    unsigned long long* prof_acc;
-    unsigned* stamp_scratch;
-    // per-token log-probs of a generate() call (vc_request_generate_logprobs): slabs laid out like out_ids — the chosen token's
-    // log-prob [slots], the lp_k most likely tokens [slots, lp_k].  lp_tok == nullptr (every loop but a session's while such a call
-    // runs): the step has no log-prob launch.
-    float *lp_tok, *lp_top;
-    int* lp_ids;
-    int lp_k;
-    // logits processors of a generate() call (vc_request_logits_processors): the call's prompt ids and bad-word table, and the
-    // processed rows the selection then reads.  proc_logits == nullptr (every loop but a session's while such a call runs): no
-    // processor launch, the selection reads the raw rows.
-    const int *proc_prompt, *proc_bad;
-    float* proc_logits;
-};
 
 // the next timing slot of the step being enqueued (nullptr: profiling off)
 inline unsigned* next_stamp(const LoopView& v) {

@@ -125,10 +125,13 @@ void ensure_prefill_ws(vc_model* m, int B, int Scap) {
     m->logits.ensure((size_t)Bp * c.vocab * 4, true);
 }
 
+// every captured step of the session goes: for what a step bakes in without it showing in its StepKey (see there)
 void drop_graph(vc_model* m) {
-    if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
-    if (m->graph_lp) { (void)hipGraphExecDestroy(m->graph_lp); m->graph_lp = nullptr; }
-    if (m->graph_beam) { (void)hipGraphExecDestroy(m->graph_beam); m->graph_beam = nullptr; }
+    for (StepGraph& s : m->step)
+        if (s.exec) {
+            (void)hipGraphExecDestroy(s.exec);
+            s.exec = nullptr;
+        }
 }
 
 // the session's own decode loop: KV cache for B sequences of S_total positions + the per-step buffers
@@ -151,10 +154,7 @@ void ensure_llm(vc_model* m, int B, int S_total) {
         m->capB = B;
         m->capS = newS;
         m->kv_es = es;
-        drop_graph(m);
     }
-    const void* before[] = {m->x_dec.p, m->xg_dec.p, m->qkv_dec.p, m->attn_dec.p, m->h_dec.p, m->next_tok.p, m->rows.p, m->ssq.p,
-                            m->logits.p};
     ensure_prefill_ws(m, B, Scap);
     const int Bp = (int)rup(B, 16);
     // (sized for the split step as well: hi + lo row groups double the bf16 operands, qkv_dec is fp32 there)
@@ -168,12 +168,9 @@ void ensure_llm(vc_model* m, int B, int S_total) {
     m->ssq.ensure((size_t)Bp * m->npart * 4, true);
     m->sk_scratch.ensure(sk_floats(c) * 4);   // [K-slices][tiles][2 row groups][256]
     m->sk_counters.ensure((size_t)sk_counters_n(c) * 4, true);
-    const void* after[] = {m->x_dec.p, m->xg_dec.p, m->qkv_dec.p, m->attn_dec.p, m->h_dec.p, m->next_tok.p, m->rows.p, m->ssq.p,
-                           m->logits.p};
-    for (size_t i = 0; i < sizeof(before) / sizeof(before[0]); ++i)
-        if (before[i] != after[i]) drop_graph(m);  // the decode graph bakes these pointers in
 }
 
+// the plain step of the session's loop: no log-prob slabs, no processor buffers (a generate() call attaches its own to a copy)
 LoopView session_view(vc_model* m) {
     LoopView v{};
     v.st = m->st;
@@ -197,17 +194,6 @@ LoopView session_view(vc_model* m) {
     v.ssq = m->ssq.as<float>();
     v.sk_scratch = m->sk_scratch.as<float>();
     v.sk_counters = m->sk_counters.as<unsigned>();
-    if (m->lp_on) {
-        v.lp_tok = m->lp_tok.as<float>();
-        v.lp_top = m->lp_top.as<float>();
-        v.lp_ids = m->lp_ids.as<int>();
-        v.lp_k = m->lp_k;
-    }
-    if (m->proc_on) {
-        v.proc_prompt = m->proc_prompt.as<int>();
-        v.proc_bad = m->proc_bad.as<int>();
-        v.proc_logits = m->proc_logits.as<float>();
-    }
     return v;
 }
 
@@ -229,7 +215,7 @@ KvTarget loop_kv(const LoopView& v) { return KvTarget{v.kc, v.vc, v.capR, v.capS
 
 // The decode loop outran the cache (a host-driven vc_decode_step loop past the reserve of its prefill): re-allocate with
 // room for `need` positions and move the live prefix — K and V rows are contiguous per (layer, sample, head), so each is
-// one strided 2-D copy.  The decode graph bakes the cache pointers in and is re-captured.
+// one strided 2-D copy.  (The captured steps are keyed on the cache pointers and capS: the next one is re-captured.)
 void grow_kv(vc_model* m, int need) {
     const vc_model_cfg& c = m->c;
     const int oldS = m->capS, live = m->cur_pos;
@@ -266,7 +252,6 @@ void grow_kv(vc_model* m, int need) {
         m->s_capS = newS;
     }
     m->capS = newS;
-    drop_graph(m);
 }
 
 // output_hidden_states ([HF] LlamaModel.forward: the tuple (inputs_embeds, layer 1 output, ..., layer L-1 output,
@@ -516,19 +501,18 @@ const float* enqueue_step_processors(vc_model* m, const LoopView& v, const float
     return v.proc_logits;
 }
 
+// the selection tail of a step on `logits`: the processors (a view with their buffers), the selection + embedding of the chosen
+// tokens (K19/K20+K10), the log-probs (a view with slabs).  advance 3: a cached step; 1: step 0 on the prefill logits.
+void enqueue_selection(vc_model* m, const LoopView& v, const float* logits, int nrows, int advance) {
+    launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, logits, nrows), nrows, advance), v.st);
+    enqueue_step_logprobs(m, v, logits, nrows);
+}
+
 // ---- the device beam loop (vc_generate_beam) -----------------------------------------------------------------------------------
-// Its buffers: the fixed-size part carved from m->bm_state, the tables from m->bm_tab / m->bm_den (ensure_beam sizes them).
-struct BeamLoop {
-    float* cand_lp;   // [16, 32]
-    int* cand_id;
-    float* score;     // [16]
-    int *perm, *start, *seq, *hyp, *params, *flags;
-    int *tok_tab, *parent_tab;   // [cap_new][R]
-    float *hyp_den, *done_den;   // [cap_new + 1]
-    int B, n, cap_new;
-};
 constexpr int BEAM_CAND = VC_BEAM_MAX_ROWS * VC_MAX_TOP_LOGPROBS;
 constexpr int BEAM_STATE_INTS = 2 * BEAM_CAND + 3 * VC_BEAM_MAX_ROWS + VC_BEAM_MAX_ROWS * (BQ_STRIDE + BH_STRIDE) + BP_STRIDE + 4;
+// bytes one (row, head) of the tail-permute staging holds: the cache rows of cap_new positions
+size_t beam_span_cap(const vc_model* m, int cap_new) { return (size_t)cap_new * m->hd * m->kv_es; }
 BeamLoop beam_view(vc_model* m, int B, int n) {
     BeamLoop bl{};
     int* p = m->bm_state.as<int>();
@@ -543,6 +527,8 @@ BeamLoop beam_view(vc_model* m, int B, int n) {
     bl.params = bl.hyp + VC_BEAM_MAX_ROWS * BH_STRIDE;
     bl.flags = bl.params + BP_STRIDE;
     bl.cap_new = m->bm_cap_new;
+    bl.tmp = m->bm_tmp.p;
+    bl.span_cap = beam_span_cap(m, bl.cap_new);
     bl.tok_tab = m->bm_tab.as<int>();
     bl.parent_tab = bl.tok_tab + (size_t)bl.cap_new * VC_BEAM_MAX_ROWS;
     bl.hyp_den = m->bm_den.as<float>();
@@ -551,23 +537,14 @@ BeamLoop beam_view(vc_model* m, int B, int n) {
     bl.n = n;
     return bl;
 }
-// bytes one (row, head) of the tail-permute staging holds: the cache rows of cap_new positions
-size_t beam_span_cap(const vc_model* m, int cap_new) { return (size_t)cap_new * m->hd * m->kv_es; }
-// the buffers of a call of R rows and max_new steps; the captured beam step bakes their pointers and the capacity in
+// the buffers of a call of R rows and max_new steps (beam_view hands their pointers and the capacity to the step)
 void ensure_beam(vc_model* m, int R, int max_new) {
     m->bm_state.ensure((size_t)BEAM_STATE_INTS * 4, true);
     const int cap_new = std::max((int)rup(max_new, 64), m->bm_cap_new);
-    const void* before[] = {m->bm_tab.p, m->bm_den.p, m->bm_tmp.p};
     m->bm_tab.ensure((size_t)2 * cap_new * VC_BEAM_MAX_ROWS * 4);
     m->bm_den.ensure((size_t)2 * (cap_new + 1) * 4);
     m->bm_tmp.ensure((size_t)2 * R * m->c.heads * beam_span_cap(m, cap_new));
     m->bm_cap_new = cap_new;
-    const void* after[] = {m->bm_tab.p, m->bm_den.p, m->bm_tmp.p};
-    for (int i = 0; i < 3; ++i)
-        if (before[i] != after[i] && m->graph_beam) {
-            (void)hipGraphExecDestroy(m->graph_beam);
-            m->graph_beam = nullptr;
-        }
 }
 // the tail of a beam step on `logits`: the 2 n best log-probs of every row, the selection / bookkeeping kernel, the tail permute of
 // every layer's K and V (`permute`; nothing to move behind the prefill) and the embedding of the chosen tokens
@@ -583,8 +560,8 @@ void enqueue_beam_tail(vc_model* m, const LoopView& v, const BeamLoop& bl, const
         const KvTarget kv = loop_kv(v);
         const int pos_bytes = m->hd * v.es;
         for (int l = 0; l < c.layers; ++l)
-            launch_kv_permute_tail(kcache(m, kv, l), vcache(m, kv, l), m->bm_tmp.p, bl.perm, bl.start, v.rows, R, c.heads,
-                                   (size_t)v.capS * pos_bytes, pos_bytes, beam_span_cap(m, bl.cap_new), v.st);
+            launch_kv_permute_tail(kcache(m, kv, l), vcache(m, kv, l), bl.tmp, bl.perm, bl.start, v.rows, R, c.heads,
+                                   (size_t)v.capS * pos_bytes, pos_bytes, bl.span_cap, v.st);
     }
     launch_embed_tokens_ssq(v.next_tok, m->embed, v.x_dec, v.ssq, m->llm[0].in_norm, v.xg_dec, R, c.hidden, m->npart, v.st, v.split_G,
                             (m->precision || v.split_G) ? lo_plane(m, m->embed) : nullptr);
@@ -638,25 +615,19 @@ void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_
         [&](int l) {
             if (hooks) emit_hidden(m, l + 1, nrows, 1, v.x_dec);
         });
-    if (beam) {
-        enqueue_beam_tail(m, v, *beam, v.logits, 3, true);
-    } else {
-        launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, v.logits, nrows), nrows, 3), v.st);   // K19/K20+K10
-        enqueue_step_logprobs(m, v, v.logits, nrows);
-    }
+    if (beam) enqueue_beam_tail(m, v, *beam, v.logits, 3, true);
+    else enqueue_selection(m, v, v.logits, nrows, 3);
     // in-situ timing: fold the step's slots (5 per layer: qkv, attention, o, gate/up, down; then lm_head) into the span's sums
     if (v.stamps && v.stamp_next && v.prof_acc)
         launch_stamp_accumulate(v.stamps, *v.stamp_next, m->c.layers, v.prof_acc, v.stamp_scratch, v.st);
 }
 
 // strict mode: the rows of a session advance in lockstep, so row 0's position serves every row of the fp32 kernels
-void enqueue_decode_step_strict(vc_model* m, int B) {
-    const LoopView v = session_view(m);
+void enqueue_decode_step_strict(vc_model* m, const LoopView& v, int B) {
     emit_hidden(m, 0, B, 1, m->x_dec.as<float>());
     run_llm_layers_strict(m, m->x_dec.as<float>(), B, 1, v.rows + RS_POS, false);
     logits_strict(m, m->x_dec.as<float>(), nullptr, B);
-    launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, v.logits, B), B, 3), v.st);
-    enqueue_step_logprobs(m, v, v.logits, B);
+    enqueue_selection(m, v, v.logits, B, 3);
 }
 
 // ---- logits of precision mode 0 from the residual rows x (B sequences of rows_per_seq rows) --------------------------------------
@@ -785,45 +756,20 @@ hipGraphExec_t capture_step(vc_model* m, const LoopView& v, int nrows, const Bea
     return exec;
 }
 
-// the session's captured step: the plain one, or — while a generate() call with log-probs (lp_on) and / or logits processors (proc_on)
-// runs — the one that carries the log-prob launch for lp_k alternatives and / or the processor launch.  Both stay instantiated side by
-// side: a vc_decode_step behind such a call replays the plain step.
-hipGraphExec_t ensure_graph(vc_model* m, int B) {
-    if (m->lp_on || m->proc_on) {
-        const int k = m->lp_on ? m->lp_k : -1;
-        if (m->graph_lp && m->graph_lp_rows == B && m->graph_lp_masked == m->kmask_in_decode && m->graph_lp_k == k &&
-            m->graph_lp_proc == m->proc_on)
-            return m->graph_lp;
-        if (m->graph_lp) { (void)hipGraphExecDestroy(m->graph_lp); m->graph_lp = nullptr; }
-        m->graph_lp = capture_step(m, session_view(m), B);
-        m->graph_lp_rows = B;
-        m->graph_lp_masked = m->kmask_in_decode;
-        m->graph_lp_k = k;
-        m->graph_lp_proc = m->proc_on;
-        return m->graph_lp;
+// the session's captured step of `kind` for this view, row count and (a beam step) beam loop: the one it holds if it was captured from
+// an equal description (StepKey), else a new capture in its place
+hipGraphExec_t step_graph(vc_model* m, StepKind kind, const LoopView& view, int nrows, const BeamLoop* beam = nullptr) {
+    StepGraph& s = m->step[kind];
+    const StepKey key{view, nrows, beam != nullptr, beam ? *beam : BeamLoop{}};
+    if (s.exec && s.key == key) return s.exec;
+    if (s.exec) {
+        (void)hipGraphExecDestroy(s.exec);
+        s.exec = nullptr;
     }
-    if (m->graph && m->graph_rows == B && m->graph_masked == m->kmask_in_decode) return m->graph;
-    if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
-    m->graph = capture_step(m, session_view(m), B);
-    m->graph_rows = B;
-    m->graph_masked = m->kmask_in_decode;
-    return m->graph;
-}
-
-// the captured beam step of B sequences of n beams (after ensure_beam), kept beside the plain and the log-prob step
-hipGraphExec_t ensure_beam_graph(vc_model* m, int B, int n) {
-    const int R = B * n;
-    if (m->graph_beam && m->graph_beam_rows == R && m->graph_beam_n == n && m->graph_beam_masked == m->kmask_in_decode &&
-        m->graph_beam_cap_new == m->bm_cap_new)
-        return m->graph_beam;
-    if (m->graph_beam) { (void)hipGraphExecDestroy(m->graph_beam); m->graph_beam = nullptr; }
-    const BeamLoop bl = beam_view(m, B, n);
-    m->graph_beam = capture_step(m, session_view(m), R, &bl);
-    m->graph_beam_rows = R;
-    m->graph_beam_n = n;
-    m->graph_beam_masked = m->kmask_in_decode;
-    m->graph_beam_cap_new = m->bm_cap_new;
-    return m->graph_beam;
+    s.exec = capture_step(m, view, nrows, beam);
+    s.key = key;
+    m->step_captures += 1;
+    return s.exec;
 }
 
 void ensure_out_ids(vc_model* m, int B, int max_new) {
@@ -831,36 +777,21 @@ void ensure_out_ids(vc_model* m, int B, int max_new) {
     if (stride > m->out_stride || m->out_ids.cap < (size_t)rup(B, 16) * stride * 4) {
         m->out_stride = std::max(stride, m->out_stride);
         m->out_ids.ensure((size_t)rup(B, 16) * m->out_stride * 4);
-        drop_graph(m);  // pointer baked into the graph
     }
 }
 // the log-prob slabs of a generate() call, sized like out_ids (after ensure_out_ids): [rows, out_stride] (x K)
 void ensure_logprob_slabs(vc_model* m, int B, int K) {
     const size_t slots = (size_t)rup(B, 16) * m->out_stride;
-    const void* before[] = {m->lp_tok.p, m->lp_top.p, m->lp_ids.p};
     m->lp_tok.ensure(slots * 4);
     m->lp_top.ensure(slots * std::max(K, 1) * 4);
     m->lp_ids.ensure(slots * std::max(K, 1) * 4);
-    const void* after[] = {m->lp_tok.p, m->lp_top.p, m->lp_ids.p};
-    for (int i = 0; i < 3; ++i)
-        if (before[i] != after[i] && m->graph_lp) {   // pointers baked into the step that carries the launch
-            (void)hipGraphExecDestroy(m->graph_lp);
-            m->graph_lp = nullptr;
-        }
 }
 
 // the buffers of a generate() call with logits processors: the prompt ids [B, T], the bad-word table, the processed rows [B, V]
 void ensure_processor_buffers(vc_model* m, int B, int T) {
-    const void* before[] = {m->proc_prompt.p, m->proc_bad.p, m->proc_logits.p};
     m->proc_prompt.ensure((size_t)B * T * 4);
     m->proc_bad.ensure((size_t)VC_MAX_BAD_WORDS * (1 + VC_MAX_BAD_WORD_LEN) * 4);
     m->proc_logits.ensure((size_t)rup(B, 16) * m->c.vocab * 4);
-    const void* after[] = {m->proc_prompt.p, m->proc_bad.p, m->proc_logits.p};
-    for (int i = 0; i < 3; ++i)
-        if (before[i] != after[i] && m->graph_lp) {   // pointers baked into the step that carries the launch
-            (void)hipGraphExecDestroy(m->graph_lp);
-            m->graph_lp = nullptr;
-        }
 }
 
 // ---- host-side RowState records ---------------------------------------------------------------------------------

@@ -419,6 +419,14 @@ void pool_release(vc_pool* p) {
     } while (0)
 const bool g_dbg_hip = getenv("VC_DEBUG_HIP") != nullptr;
 
+// the epilogue of every generate call: the phase times of the call that just ended, its decode phase between the two events given
+void read_phase_times(vc_model* m, hipEvent_t decode_begin, hipEvent_t decode_end) {
+    if (!m->ev[0]) return;
+    (void)hipEventElapsedTime(&m->t_encode, m->ev[0], m->ev[1]);
+    (void)hipEventElapsedTime(&m->t_prefill, m->ev[1], m->ev[2]);
+    (void)hipEventElapsedTime(&m->t_decode, decode_begin, decode_end);
+}
+
 void generate_on_pool(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
                       int on_dev, const GenParams& g, const std::vector<int>& tail, vc_token_cb cb, void* cb_user,
                       int cb_every, int32_t* out_ids, int* n_generated) {
@@ -547,11 +555,7 @@ void generate_on_pool(vc_model* m, const int64_t* ids, int B, int T, const float
             cb(cb_user, reported, produced - reported, B, part.data());
         }
         if (n_generated) *n_generated = produced;
-        if (m->ev[0]) {
-            (void)hipEventElapsedTime(&m->t_encode, m->ev[0], m->ev[1]);
-            (void)hipEventElapsedTime(&m->t_prefill, m->ev[1], m->ev[2]);
-            (void)hipEventElapsedTime(&m->t_decode, rq.join_ev, rq.done_ev);
-        }
+        read_phase_times(m, rq.join_ev, rq.done_ev);
         DBG_HIP("pool timings");
     } catch (...) {
         {   // a request that is still queued / active must not outlive this frame
@@ -575,11 +579,11 @@ void generate_on_pool(vc_model* m, const int64_t* ids, int B, int T, const float
 }
 
 
-// generate() on the session's own loop: prefill, then max_new - 1 graph-replayed (strict: eagerly enqueued) decode steps
-void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
-                         int on_dev, const GenParams& g, const std::vector<int>& tail, vc_token_cb cb, void* cb_user,
-                         int cb_every, int32_t* out_ids, int* n_generated) {
-    const int max_new = g.max_new;
+// The prologue of a generate call on the session's own loop: encode + splice + prefill with room for max_new steps, the loop's
+// decode steps under an all-ones mask, the end of the prefill phase recorded (ev[2]).  -> the prefill gate, still held: the caller
+// releases it behind its step-0 selection.  m->last_S = the spliced length.
+std::unique_lock<std::mutex> prefill_on_session(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg,
+                                                const float* depth, int on_dev, int max_new) {
     m->cur_pos = -1;
     int S = 0;
     // Sessions of one process take turns in the MFMA-bound encode+prefill phase: two prefills side by side only slow
@@ -588,30 +592,38 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     do_prefill(m, ids, B, T, img, seg, depth, on_dev, 1, max_new, true, &S);  // generate() always builds a mask
     m->last_S = S;
     REQUIRE(S + max_new <= m->capS, VC_ERR_INVALID, "prompt %d + max_new %d exceeds the KV capacity %d", S, max_new, m->capS);
-    ensure_out_ids(m, B, max_new);
     finish_prefill(m, session_kv(m), nullptr);
     m->kmask_in_decode = false;   // generate(): the cached steps run under an all-ones mask (vcoder_ds_llava_arch.py:130-133)
-    // vc_request_generate_logprobs: every selection of this call is followed by the log-prob launch (session_view: lp_on)
+    if (m->ev[2]) HIPCHK(hipEventRecord(m->ev[2], m->st));
+    return gate;
+}
+
+// generate() on the session's own loop: prefill, then max_new - 1 graph-replayed (strict: eagerly enqueued) decode steps
+void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
+                         int on_dev, const GenParams& g, const std::vector<int>& tail, vc_token_cb cb, void* cb_user,
+                         int cb_every, int32_t* out_ids, int* n_generated) {
+    const int max_new = g.max_new;
+    std::unique_lock<std::mutex> gate = prefill_on_session(m, ids, B, T, img, seg, depth, on_dev, max_new);
+    ensure_out_ids(m, B, max_new);
+    // the steps of this call: the session's plain view, plus what the call asked for — the view goes to the step-0 selection, to the
+    // captured step (STEP_CALL with either request, else the plain one) and, in strict mode, to the eager step
+    LoopView v = session_view(m);
+    // vc_request_generate_logprobs: every selection of this call is followed by the log-prob launch
     const bool want_lp = m->glp_tok != nullptr;
-    struct LpScope {
-        vc_model* m;
-        ~LpScope() { m->lp_on = false; }
-    } lp_scope{m};
+    const int K = m->glp_k;
     if (want_lp) {
-        m->lp_k = m->glp_k;
-        ensure_logprob_slabs(m, B, m->lp_k);
-        m->lp_on = true;
+        ensure_logprob_slabs(m, B, K);
+        v.lp_tok = m->lp_tok.as<float>();
+        v.lp_top = m->lp_top.as<float>();
+        v.lp_ids = m->lp_ids.as<int>();
+        v.lp_k = K;
         // positions nothing writes (behind max_new, or never reached) read 0.0 / 0.0 / -1
         HIPCHK(hipMemsetAsync(m->lp_tok.p, 0, m->lp_tok.cap, m->st));
         HIPCHK(hipMemsetAsync(m->lp_top.p, 0, m->lp_top.cap, m->st));
         HIPCHK(hipMemsetAsync(m->lp_ids.p, 0xFF, m->lp_ids.cap, m->st));
     }
-    // vc_request_logits_processors: every selection of this call is preceded by the processor launch (session_view: proc_on), which
-    // reads the caller's prompt ids (as int32, placeholders and all) and the bad-word table
-    struct ProcScope {
-        vc_model* m;
-        ~ProcScope() { m->proc_on = false; }
-    } proc_scope{m};
+    // vc_request_logits_processors: every selection of this call is preceded by the processor launch, which reads the caller's
+    // prompt ids (as int32, placeholders and all) and the bad-word table
     std::vector<int> ids32;
     if (g.proc) {
         ensure_processor_buffers(m, B, T);
@@ -619,16 +631,16 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
         for (size_t i = 0; i < ids32.size(); ++i) ids32[i] = (int)std::max<int64_t>(std::min<int64_t>(ids[i], INT32_MAX), INT32_MIN);
         HIPCHK(hipMemcpyAsync(m->proc_prompt.p, ids32.data(), ids32.size() * 4, hipMemcpyHostToDevice, m->st));
         HIPCHK(hipMemcpyAsync(m->proc_bad.p, m->gproc_bad.data(), m->gproc_bad.size() * 4, hipMemcpyHostToDevice, m->st));
-        m->proc_on = true;   // (both host vectors live until the synchronize behind the step-0 selection)
+        // (both host vectors live until the synchronize behind the step-0 selection)
+        v.proc_prompt = m->proc_prompt.as<int>();
+        v.proc_bad = m->proc_bad.as<int>();
+        v.proc_logits = m->proc_logits.as<float>();
     }
-    if (m->ev[2]) HIPCHK(hipEventRecord(m->ev[2], m->st));
     arm_session_rows(m, g, tail.data());
-    const LoopView v = session_view(m);
     // token 0 comes from the prefill logits
     std::vector<int> fill((size_t)B * m->out_stride, g.pad);
     HIPCHK(hipMemcpyAsync(m->out_ids.p, fill.data(), fill.size() * 4, hipMemcpyHostToDevice, m->st));
-    launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, v.logits, B), B, 1), m->st);  // step 0 -> 1; the position stays at S
-    enqueue_step_logprobs(m, v, v.logits, B);
+    enqueue_selection(m, v, v.logits, B, 1);   // step 0 -> 1; the position stays at S
     HIPCHK(hipStreamSynchronize(m->st));
     gate.unlock();
     int produced = 1, reported = 0;
@@ -654,10 +666,10 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     const int every = cb ? std::max(cb_every, 1) : 8;
     if (cb && every == 1) report(1);
     if (max_new > 1 && !all_finished()) {
-        const hipGraphExec_t step_graph = m->precision != 1 ? ensure_graph(m, B) : nullptr;
+        const hipGraphExec_t exec = m->precision != 1 ? step_graph(m, want_lp || g.proc ? STEP_CALL : STEP_PLAIN, v, B) : nullptr;
         for (int step = 1; step < max_new; ++step) {
-            if (m->precision == 1) enqueue_decode_step_strict(m, B);
-            else HIPCHK(hipGraphLaunch(step_graph, m->st));
+            if (m->precision == 1) enqueue_decode_step_strict(m, v, B);
+            else HIPCHK(hipGraphLaunch(exec, m->st));
             m->cur_pos += 1;
             produced = step + 1;
             // the reference checks its stopping criteria on the host every token; checking every few tokens only
@@ -675,7 +687,6 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, m->out_ids.p, (size_t)m->out_stride * 4, (size_t)max_new * 4, B,
                             hipMemcpyDeviceToHost, m->st));
     if (want_lp) {   // the slabs come back once, beside out_ids
-        const int K = m->lp_k;
         HIPCHK(hipMemcpy2DAsync(m->glp_tok, (size_t)max_new * 4, m->lp_tok.p, (size_t)m->out_stride * 4, (size_t)max_new * 4, B,
                                 hipMemcpyDeviceToHost, m->st));
         if (K > 0) {
@@ -689,7 +700,6 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     if (want_lp) {
         // a row's finishing token (its EOS, or the token completing a stop sequence) is scored; behind it the row emitted pad: those
         // positions, and the columns the loop never reached, hold 0.0 / 0.0 / -1
-        const int K = m->lp_k;
         for (int b = 0; b < B; ++b) {
             const int e = row_finish_end(g, out_ids + (size_t)b * max_new, tail.data() + (size_t)b * (VC_MAX_STOP_LEN - 1), produced);
             for (int s_ = e; s_ < max_new; ++s_) {
@@ -705,11 +715,7 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     produced = trim_columns(g, out_ids, max_new, tail.data(), B, produced);
     if (cb) report(produced);
     if (n_generated) *n_generated = produced;
-    if (m->ev[0]) {
-        (void)hipEventElapsedTime(&m->t_encode, m->ev[0], m->ev[1]);
-        (void)hipEventElapsedTime(&m->t_prefill, m->ev[1], m->ev[2]);
-        (void)hipEventElapsedTime(&m->t_decode, m->ev[2], m->ev[3]);
-    }
+    read_phase_times(m, m->ev[2], m->ev[3]);
 }
 
 // ---- beam search inside the device loop (vc_generate_beam) -----------------------------------------------------------------------
@@ -794,19 +800,12 @@ void generate_beam_on_session(vc_model* m, const int64_t* ids, int B, int T, con
         }
         px[k] = dst;
     }
-    m->cur_pos = -1;
-    int S = 0;
-    std::unique_lock<std::mutex> gate(g_prefill_gate);
-    do_prefill(m, ids_x.data(), R, T, px[0], px[1], px[2], on_dev, 1, max_new, true, &S);
-    m->last_S = S;
-    REQUIRE(S + max_new <= m->capS, VC_ERR_INVALID, "prompt %d + max_new %d exceeds the KV capacity %d", S, max_new, m->capS);
-    finish_prefill(m, session_kv(m), nullptr);
-    m->kmask_in_decode = false;   // generate(): the cached steps run under an all-ones mask (vcoder_ds_llava_arch.py:130-133)
+    std::unique_lock<std::mutex> gate = prefill_on_session(m, ids_x.data(), R, T, px[0], px[1], px[2], on_dev, max_new);
+    const int S = m->last_S;
     ensure_beam(m, R, max_new);
     // the tail permute cuts a tail at the span its grid and staging are sized for: the whole call must fit (it does: cap_new >= max_new)
     REQUIRE(max_new <= m->bm_cap_new && m->bm_tmp.cap >= (size_t)2 * R * c.heads * beam_span_cap(m, m->bm_cap_new), VC_ERR_STATE,
             "beam buffers hold %d steps, the call asks for %d", m->bm_cap_new, max_new);
-    if (m->ev[2]) HIPCHK(hipEventRecord(m->ev[2], m->st));
     GenParams none;   // nothing is recorded in out_ids, no EOS bookkeeping in the records: the beam kernel keeps its own
     arm_session_rows(m, none, nullptr);
     const LoopView v = session_view(m);
@@ -850,9 +849,9 @@ void generate_beam_on_session(vc_model* m, const int64_t* ids, int B, int T, con
     };
     int produced = 1;
     if (!poll() && max_new > 1) {
-        const hipGraphExec_t step_graph = ensure_beam_graph(m, B, n);
+        const hipGraphExec_t exec = step_graph(m, STEP_BEAM, v, R, &bl);
         for (int step = 1; step < max_new; ++step) {
-            HIPCHK(hipGraphLaunch(step_graph, m->st));
+            HIPCHK(hipGraphLaunch(exec, m->st));
             m->cur_pos += 1;
             produced = step + 1;
             // a done sequence emits pad and changes nothing: polling every few steps only ends the loop later
@@ -924,11 +923,7 @@ void generate_beam_on_session(vc_model* m, const int64_t* ids, int B, int T, con
         std::copy(best_ids[b].begin(), best_ids[b].end(), row);
         if ((int)best_ids[b].size() < L_out && q.n_eos > 0) row[best_ids[b].size()] = q.eos[0];
     }
-    if (m->ev[0]) {
-        (void)hipEventElapsedTime(&m->t_encode, m->ev[0], m->ev[1]);
-        (void)hipEventElapsedTime(&m->t_prefill, m->ev[1], m->ev[2]);
-        (void)hipEventElapsedTime(&m->t_decode, m->ev[2], m->ev[3]);
-    }
+    read_phase_times(m, m->ev[2], m->ev[3]);
 }
 
 }  // namespace

@@ -192,6 +192,10 @@ class HipEngine:
                                                      out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def step_captures(self) -> int:
+        """test hook: decode-step graph captures this session's own loop has performed so far (vc_debug_step_captures)"""
+        return self._check(self.lib.vc_debug_step_captures(self._model))
+
     def inexact_tensors(self) -> int:
         """loaded tensors whose values bf16 cannot hold (an fp16 / fp32 checkpoint): each keeps a bf16 lo plane that the 'strict' and
         'split' precision modes add back (w = hi + lo); the bf16 fast path runs on the rounded weights (vc_model_inexact_tensors)"""
