@@ -137,7 +137,11 @@ int vc_debug_step_captures(vc_model* m);
  * power-of-two scale per token row) and run e4m3 x e4m3 on v_mfma_scale_f32_16x16x128_f8f6f4 (W8A8, twice the bf16
  * MFMA rate), and the KV cache holds e4m3 rows (no scale, saturating; vc_model_set_fp8_kv(m, 0) before vc_model_finalize: bf16 rows) — half the bytes of the stream
  * that dominates the pooled 13b decode step.  The reference's counterpart is `load_8bit` (builder.py:31-33, bitsandbytes LLM.int8 — also 8-bit
- * weights x 8-bit activations).  Call before vc_model_finalize. */
+ * weights x 8-bit activations).  3 = W4A16: the same seven linears as MXFP4 — OCP e2m1 elements with one power-of-two (E8M0) scale per
+ * 32 consecutive k of a row — streamed as nibbles + scale bytes by the decode GEMV (0.53 bytes per weight) and widened exactly in
+ * registers; as with 1, the row-major matrices are rewritten with the effective weights q * 2^e (exact in bf16 and in fp16), so every other
+ * path computes with what decode sees.  Needs hidden_size and intermediate_size divisible by 128 (refused at vc_model_finalize otherwise).
+ * This is not the reference's `load_4bit` (bitsandbytes NF4).  Call before vc_model_finalize. */
 int vc_model_set_weight_format(vc_model* m, int fmt);
 
 /* ---- hot path ------------------------------------------------------------------------------ */

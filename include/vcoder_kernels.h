@@ -252,6 +252,24 @@ unsigned long long vck_gemv_wg_launches(void);   /* launches the workgroup-share
  * workgroups}, or -1 where the launcher refuses the call (tests: tests/golden/gemv_plan.npz pins the table) */
 int vck_gemv_plan(int M, int N, int K, int epi, int fp8, int split_rows, int ksplit, int has_sk, unsigned long long sk_scratch_floats,
                   int sk_counters_n, int has_wlo, int out[10]);
+/* W4A16 decode weights: MXFP4.  Per output row and per block of 32 consecutive k: e = the smallest integer with max|block| <= 6 * 2^e
+ * (>= -13; 0 for an all-zero block), stored as the E8M0 byte e + 127 in scale [N/16][K/128][64 lanes]; elements q = e2m1(W / 2^e)
+ * (nearest, ties to the even code) as nibbles in Wq [N/16][K/128][64 lanes][16 B], lane = n%16 + 16*((k%128)/32), k even in the low
+ * nibble of a byte; W [N,K] is overwritten with the effective weights q * 2^e (exact in bf16 and in fp16).  K % 128 == 0, N % 16 == 0.
+ * vcoder_amd/quant.py (quantize_blocks_mxfp4, pack_w4) states the same on the host. */
+void vck_quantize_mxfp4(uint16_t* W, uint8_t* Wq, uint8_t* scale, int N, int K, void* stream);
+/* vck_gemv_ex over those nibbles and scale bytes (a kernel of its own: four waves split K in 128-wide super-tiles); ksplit > 1 needs
+ * the hand-off buffers.  vck_gemv_w4_split: precision mode "split", X = [G + M, K] hi rows then lo rows (G = 8: M <= 8, 16: M <= 16). */
+void vck_gemv_w4(const uint16_t* X, const void* Wq, const uint8_t* w4scale, void* out, const float* ssq_in, float* ssq_out,
+                 const float* xg_w, uint16_t* xg_out, int npart, float eps, float* sk_scratch, unsigned* sk_counters, int ksplit, int M,
+                 int N, int K, int ldo, int epi, void* stream);
+void vck_gemv_w4_split(const uint16_t* X, const void* Wq, const uint8_t* w4scale, void* out, const float* ssq_in, float* ssq_out,
+                       const float* xg_w, uint16_t* xg_out, int npart, float eps, int M, int N, int K, int ldo, int epi, int G, void* stream);
+/* what those would launch: 0 and out = {form (3), waves, tiles per workgroup, ring slots, 8-row activation pieces, K-slices,
+ * workgroups}, or -1 where the launcher refuses the call.  vck_set_gemv_w4_nt: 0 = tiles per workgroup by the tile count (default),
+ * 1 / 2 / 4 = for every matrix (tests, A/B; the bits do not depend on it). */
+int vck_gemv_w4_plan(int M, int N, int K, int epi, int split_rows, int ksplit, int has_sk, int out[7]);
+void vck_set_gemv_w4_nt(int nt);
 void vck_rmsnorm_split(const float* x, const int* row_idx, const float* w, uint16_t* y, int rows, int D, float eps, int ldy,
                        uint64_t lo_off, void* stream);
 void vck_layernorm_split(const float* x, const float* w, const float* b, uint16_t* y, int rows, int D, float eps, int ldy,

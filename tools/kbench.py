@@ -508,6 +508,48 @@ def bench_gemv_fp8():
                   flush=True)
 
 
+def bench_gemv_formats(formats=("bf16", "w8", "w4")):
+    """The decoder linears of the 7b and 13b models at 1 / 8 / 16 / 32 rows in the three weight formats of the decode GEMV: bf16,
+    W8A16 (e4m3 bytes + row scales) and W4A16 (MXFP4 nibbles + block scale bytes): us per launch and the achieved fraction of the
+    8 TB/s HBM peak over the weight bytes of the format.  Random bytes (speed does not depend on the values); enough copies of a
+    matrix are rotated that a launch never finds its weights in the 256 MiB last-level cache.  KBENCH_W4_NT = 1 / 2 / 4 forces the
+    W4A16 tile geometry (A/B)."""
+    if os.environ.get("KBENCH_W4_NT"):
+        lib.vck_set_gemv_w4_nt(int(os.environ["KBENCH_W4_NT"]))
+    shapes = [("7b", 12288, 4096, 0, "qkv"), ("7b", 4096, 4096, 2, "o"), ("7b", 22016, 4096, 3, "gate-up"), ("7b", 4096, 11008, 2, "down"),
+              ("13b", 15360, 5120, 0, "qkv"), ("13b", 5120, 5120, 2, "o"), ("13b", 27648, 5120, 3, "gate-up"), ("13b", 5120, 13824, 2, "down")]
+    bpw = {"bf16": 2.0, "w8": 1.0, "w4": 0.5 + 1.0 / 32.0}
+    for (model, N, K, epi, name) in shapes:
+        npart = (K // 16 + 15) // 16 * 16
+        ssq = torch.rand(32, npart, device=dev)
+        norm = epi in (0, 3)
+        sc8 = torch.ones(N, device=dev)
+        sc4 = torch.full((N * K // 32,), 127, dtype=torch.uint8, device=dev)
+        for fmt in formats:
+            nbytes = int(N * K * bpw[fmt])
+            copies = max(4, min(64, (1 << 30) // nbytes))
+            Ws = [torch.randint(0, 120, (N * K * (2 if fmt == "bf16" else 1) // (2 if fmt == "w4" else 1),), dtype=torch.uint8, device=dev)
+                  for _ in range(copies)]
+            row = []
+            for M in (1, 8, 16, 32):
+                X = bf16(M, K)
+                out = torch.zeros((M, N), dtype=torch.float32 if epi in (1, 2) else torch.bfloat16, device=dev)
+                ldo = N // 2 if epi == 3 else N
+                it = [0]
+
+                def f():
+                    it[0] += 1
+                    W = Ws[it[0] % copies]
+                    common = (P(out), P(ssq) if norm else None, None, None, None, npart, C.c_float(1e-5), None, None, 0, M, N, K, ldo, epi, None)
+                    if fmt == "w4":
+                        lib.vck_gemv_w4(P(X), P(W), P(sc4), *common)
+                    else:
+                        lib.vck_gemv_ex(P(X), P(W), P(sc8) if fmt == "w8" else None, *common)
+                us = timeit(f, iters=3 * copies if copies < 14 else 40)
+                row.append(f"M{M:2d} {us:6.1f} us {nbytes / us / 1e6 / 8.0 * 100:5.1f}%")
+            print(f"gemv_formats {model:3s} {name:8s} N{N} K{K} {fmt:4s} ({nbytes / 2 ** 20:6.1f} MiB): " + " | ".join(row), flush=True)
+
+
 def bench_extend_linears():
     """vc_extend's routing question: one 7b decoder layer's linears (qkv, o, gate-up, down) over M token rows as
     ceil(M / 32) passes of the weight-streaming decode GEMV (folded-RMSNorm operands, as decode_linears runs them) against
@@ -766,6 +808,6 @@ if __name__ == "__main__":
              "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,
              "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn, "token_logprob": bench_token_logprob,
              "topk_logprob": bench_topk_logprob, "logits_process": bench_logits_process,
-             "score_head": bench_score_head}
+             "score_head": bench_score_head, "gemv_formats": bench_gemv_formats, "gemv_w4": lambda: bench_gemv_formats(("w4",))}
     for w in what:
         table[w]()

@@ -1,5 +1,6 @@
 // decode.hip — weight-streaming skinny GEMM for the decode steps (M <= 32 token rows per weight pass: a session's batch
-// or the rows of the shared decode pool), the fp8 quantisers of the W8A16 / W8A8 formats, weight packing.
+// or the rows of the shared decode pool), the fp8 quantisers of the W8A16 / W8A8 formats, the MXFP4 quantiser and GEMV of W4A16,
+// weight packing.
 //
 //   out[m][n] = epilogue( sum_k X[m][k] * W[n][k] )        (Llama linears have no bias)
 //
@@ -630,6 +631,185 @@ __global__ __launch_bounds__(WAVES * 64) void gemv_wg_kernel(GemvArgs p) {
     stamp_end(p.stamp, blockIdx.x);
 }
 
+// ---- W4A16: MXFP4 weights (e2m1 nibbles + one E8M0 scale per 32 consecutive k of a row) ----------------------------------------------
+// One lane's 16-byte load holds 32 nibbles = exactly one MX block of one output row, so a 1-KiB wave-instruction is a 16-row x 128-k
+// super-tile ([N/16][K/128][64 lanes][16 B]; lane = n%16 + 16*((k%128)/32); k even in the low nibble of a byte).  The lane widens its
+// block with sixteen v_cvt_scalef32_pk_*_fp4 — two nibbles each, times the block's power of two, exact — into the weight fragments of
+// four MFMAs whose activation fragments use the same k assignment: MFMA j takes k = 32g + 8j .. 32g + 8j + 7 from lane (m, g).  The
+// scale varies along K, so it is applied in the conversion, not in the epilogue.
+//
+// The schedule is gemv_dma_kernel's: four waves split K (wave w takes super-tiles w, w + 4, ... of the workgroup's K-slice), a private
+// ring of R slots per wave, every vector-memory operation of the loop a 16-byte LDS-DMA issued in program order, OPS per slot, a counted
+// vmcnt wait, no barrier in the loop.  One slot = 128 k:
+//   NT weight blocks (non-temporal) | 2 XP activation pieces (8 rows x one 128-byte line; a row's 128 k are two lines) | 1 scale block.
+// The scale bytes are laid out like the lanes that use them, [N/16][K/128][64 B], so a slot needs 64 contiguous bytes per tile: one DMA
+// instruction serves up to 16 tiles (lane l fetches 16-byte piece l & 3 of tile l >> 2; the lanes beyond NT tiles re-read the last
+// tile's), and lane l then reads byte t * 64 + l of the block for tile t.
+// The assignment of super-tiles to waves and K-slices does not depend on NT, XP or R: a row's sum is formed in the same order whichever
+// instance serves it.  K % 128 == 0, so there is no tail.
+template <int WAVES, int MG>
+VC_DEV void gemv_rstd_partials(const GemvArgs& p, const bool (&ovalid)[MG], float* ss_part /*[WAVES][16 * MG]*/) {
+    // gemv_dma_kernel's ssq_reduce (it says why the loads are unconditional and issued behind the primed ring)
+    if (p.ssq_in == nullptr) return;
+    constexpr int SQ = 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, g = lane >> 4;
+    const int nq = p.npart >> 2;
+    f32x4 sq[MG][SQ];
+#pragma unroll
+    for (int q = 0; q < MG; ++q) {
+        const float* sp = p.ssq_in + (size_t)(ovalid[q] ? m + 16 * q : 0) * p.npart;
+#pragma unroll
+        for (int j = 0; j < SQ; ++j) sq[q][j] = ld16f(sp + min(wave * 4 + g + j * WAVES * 4, nq - 1) * 4);
+    }
+#pragma unroll
+    for (int q = 0; q < MG; ++q) {
+#pragma unroll
+        for (int j = 0; j < SQ; ++j)
+            if (wave * 4 + g + j * WAVES * 4 >= nq) sq[q][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int j = 0; j < SQ; j += 2) {
+            s0 += (sq[q][j][0] + sq[q][j][1]) + (sq[q][j][2] + sq[q][j][3]);
+            s1 += (sq[q][j + 1][0] + sq[q][j + 1][1]) + (sq[q][j + 1][2] + sq[q][j + 1][3]);
+        }
+        float ss = s0 + s1;
+        const float* sp = p.ssq_in + (size_t)(ovalid[q] ? m + 16 * q : 0) * p.npart;
+        for (int qi = wave * 4 + g + SQ * WAVES * 4; qi < nq; qi += WAVES * 4) {
+            const f32x4 v = ld16f(sp + qi * 4);
+            ss += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+        ss += shfl_xor(ss, 16);
+        ss += shfl_xor(ss, 32);
+        if (g == 0) ss_part[wave * 16 * MG + 16 * q + m] = ss;
+    }
+}
+
+constexpr int W4_WAVES = 4;
+template <int NT, int R, int EPI, int XP>
+__global__ __launch_bounds__(W4_WAVES * 64) void gemv_w4_kernel(GemvArgs p) {
+    constexpr int WAVES = W4_WAVES;
+    constexpr int MG = (XP + 1) / 2;
+    constexpr int XO = 2 * XP;               // activation DMA instructions per slot
+    constexpr int OPS = NT + XO + 1;         // ... and all of them
+    constexpr int SLOT = OPS * 1024;
+    constexpr int SC = (NT + XO) * 1024;     // the slot's scale block
+    static_assert(NT <= 16, "one scale DMA serves at most 16 tiles");
+    static_assert(R * OPS >= NT * MG, "the ring is re-used for the cross-wave reduction");
+    stamp_begin(p.stamp, blockIdx.x);
+    VC_DYNAMIC_SMEM(char, ring);             // [WAVES][R][SLOT]
+    __shared__ float ss_part[WAVES][16 * MG];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ntiles = p.N >> 4;
+    const int KS = p.ksplit > 1 ? p.ksplit : 1;
+    const int ks = (int)blockIdx.x % KS;
+    const int nt0 = ((int)blockIdx.x / KS) * NT;
+    const int nst = p.K >> 7;                // super-tiles (= slots) along K
+    const int it0 = (int)((long)ks * nst / KS), it1 = (int)((long)(ks + 1) * nst / KS);
+    const int m = lane & 15, g = lane >> 4;
+    const int SR = p.split_rows;             // precision mode "split": hi rows [0, M), lo rows [G, G + M) (gemv_dma_kernel)
+    const int Mx = SR ? SR + p.M : p.M;
+    bool mvalid[MG], ovalid[MG];
+#pragma unroll
+    for (int q = 0; q < MG; ++q) {
+        mvalid[q] = m + 16 * q < Mx;
+        ovalid[q] = m + 16 * q < p.M;
+    }
+    char* my = ring + wave * (R * SLOT);
+    const char* wsrc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+        wsrc[t] = reinterpret_cast<const char*>(p.Wp) + ((size_t)min(nt0 + t, ntiles - 1) * nst * 64 + lane) * 16;
+    const char* ssrc = reinterpret_cast<const char*>(p.w4scale) + (size_t)min(nt0 + min(lane >> 2, NT - 1), ntiles - 1) * nst * 64 + (lane & 3) * 16;
+    // activation pieces: lane = (row xr of the piece, 16-byte slot xs of the line), swizzled on the source side as in gemv_dma_kernel
+    const int xr = lane >> 3, xs = lane & 7;
+    const char* xsrc[XP];
+#pragma unroll
+    for (int x = 0; x < XP; ++x) {
+        const int row = 8 * x + xr;
+        xsrc[x] = reinterpret_cast<const char*>(p.X + (size_t)(row < Mx ? row : 0) * p.K) + (xs ^ ((row >> 1) & 7)) * 16;
+    }
+    auto issue = [&](int i, int slot) {
+        char* dst = my + slot * SLOT;
+        const size_t st = (size_t)(it0 + wave + i * WAVES);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) glds16_nt(wsrc[t] + st * 1024, dst + t * 1024);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int x = 0; x < XP; ++x) glds16(xsrc[x] + (st * 2 + h) * 128, dst + (NT + h * XP + x) * 1024);
+        glds16(ssrc + st * 64, dst + SC);
+    };
+    f32x4 acc[NT][MG];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int q = 0; q < MG; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // LDS offset of 16-byte chunk c of line h of row 16q + m inside the slot
+    auto xoff = [&](int q, int h, int c) {
+        const int row = 16 * q + m;
+        return (NT + h * XP + (row >> 3)) * 1024 + ((row & 7) * 8 + (c ^ ((row >> 1) & 7))) * 16;
+    };
+    auto consume = [&](int slot) {
+        const char* s = my + slot * SLOT;
+        wave_lds_fence();   // pieces and scales are read across lanes (gemv_dma_kernel)
+        u32x4 w[NT];
+        float sc[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            w[t] = ld16(s + t * 1024 + lane * 16);
+            sc[t] = e8m0_to_f32(ld1(s + SC + t * 64 + lane));
+        }
+        u32x4 x[MG][4];
+#pragma unroll
+        for (int q = 0; q < MG; ++q) {
+            const bool have = 2 * q + (m >> 3) < XP;   // the piece holding this row was fetched
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x[q][j] = u32x4{0u, 0u, 0u, 0u};
+                if (have) x[q][j] = ld16(s + xoff(q, g >> 1, 4 * (g & 1) + j));
+                if (!mvalid[q]) x[q][j] = u32x4{0u, 0u, 0u, 0u};
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const u32x4 a = fp4x8_to_bf16x8(w[t][j], sc[t]);
+#pragma unroll
+                for (int q = 0; q < MG; ++q) acc[t][q] = mfma16(a, x[q][j], acc[t][q]);
+            }
+        wait_lgkmcnt<0>();  // the slot's reads have retired before it is re-armed
+        wave_lds_fence();
+    };
+    const int cnt = max(0, (it1 - it0 - wave + WAVES - 1) / WAVES);  // slots of this wave (wave-uniform)
+    const int primed = min(cnt, R);
+    if (cnt >= R) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) issue(r, r);
+        gemv_rstd_partials<WAVES, MG>(p, ovalid, &ss_part[0][0]);
+        int slot = 0;
+        for (int i = 0; i < cnt - R; ++i) {
+            wait_vmcnt<(R - 1) * OPS>();
+            consume(slot);
+            issue(i + R, slot);
+            slot = slot + 1 == R ? 0 : slot + 1;
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) {  // drain
+            wait_vmcnt_n((R - 1 - j) * OPS);
+            consume(slot);
+            slot = slot + 1 == R ? 0 : slot + 1;
+        }
+    } else {
+        for (int r = 0; r < primed; ++r) issue(r, r);
+        gemv_rstd_partials<WAVES, MG>(p, ovalid, &ss_part[0][0]);
+        wait_vmcnt<0>();
+        for (int r = 0; r < cnt; ++r) consume(r);
+    }
+    gemv_ring_finish<WAVES, NT, MG, EPI, false>(p, acc, ring, &ss_part[0][0], nt0, ks, KS, ovalid);
+    stamp_end(p.stamp, blockIdx.x);
+}
+
 // ---- host side: what to launch (gemv_plan) and the launch itself (launch_gemv) -----------------------------------------------------
 // Every geometry gives a row the same bits (the K partition of a matrix never depends on the row count or the form), so nothing
 // below shows in a numerical test: tests/golden/gemv_plan.npz pins the choice (test_gemv_plan_matches_recorded).
@@ -789,7 +969,59 @@ static const WideClass kWideClasses[] = {
     {7, GEMV_SWIGLU, {{2, 2, 2, 2}, {0, 4, 3, 3}}},
 };
 
+// ---- the W4A16 kernel's geometry (gemv_w4_kernel) -------------------------------------------------------------------------------
+// Always four waves (the K partition is part of the bits).  Tiles per workgroup by the tile count and the row count, ring depth by
+// (tiles per workgroup, activation pieces): a slot is NT + 2 XP + 1 KiB, from two pieces on the activation lines outweigh the nibbles.
+// Measured on MI355X (profiles/w4a16_wall_times.md; us at 1 / 8 / 16 / 32 rows, NT = 1 | 2 | 4 forced with set_gemv_w4_nt):
+//   7b o (256 tiles)       5.0  5.3  5.9  7.9 |  7.0  5.6  6.6  7.9 |  7.4  7.4  7.7  9.7    => <= 256 tiles: single tiles
+//   7b down (256)          8.8  8.9 10.4 15.4 | 10.0 10.1 13.3 17.1 | 13.7 14.0 16.0 21.1
+//   13b o (320)            7.5  8.1  9.9 16.3 |  6.7  6.3  7.9 10.1 |  8.2  8.7  9.5 12.6    => 257 .. 512: pairs
+//   13b down (320)        14.0 15.8 20.6 33.0 | 11.9 11.8 16.1 20.2 | 15.7 16.5 19.1 25.0
+//   7b qkv (768)          11.3 12.1 14.8 25.2 |  8.8  9.3 11.2 18.2 |  9.0  9.5  9.6 12.3    => wider: pairs up to 8 rows, four tiles
+//   13b qkv (960)         14.5 15.5 19.5 37.4 | 10.0 11.0 14.1 22.7 | 10.4 11.0 11.8 15.6       from 9 rows on (the activation lines a
+//   7b gate / up (1376)   18.5 20.1 23.3 46.8 | 13.1 13.5 16.1 27.1 | 16.2 17.2 17.2 22.7       workgroup re-reads from L2 are halved;
+//   13b gate / up (1728)  23.8 26.6 33.0 65.0 | 17.8 19.8 24.7 42.8 | 18.7 20.0 21.3 28.6       7b gate / up at 16 rows loses 1.1 us)
+// The ring depths were chosen, not measured: two workgroups per CU where the class launches more workgroups than CUs.
+// set_gemv_w4_nt forces the tiles per workgroup (tests: every instance on small matrices; A/B).
+static const int kW4Ring[5][4] = {{}, {4, 3, 2, 2}, {3, 2, 2, 2}, {}, {5, 3, 3, 2}};   // ring slots by [NT][activation pieces - 1]
+static int w4_tiles_per_wg(int tiles, int xp) {
+    if (tiles <= 256) return 1;
+    if (tiles <= 512 || xp == 1) return 2;
+    return 4;
+}
+static int g_gemv_w4_nt = 0;
+void set_gemv_w4_nt(int nt) { g_gemv_w4_nt = nt; }
+
+static GemvPlan plan_w4(const GemvArgs& a) {
+    if (a.wscale != nullptr || a.Wp_lo != nullptr)
+        throw std::runtime_error("W4A16 GEMV: the MXFP4 weights carry their own block scales and no lo plane");
+    if (a.K < 128 || a.K % 128 != 0 || a.N < 16 || a.N % 16 != 0 || a.M < 1)
+        throw std::runtime_error("W4A16 GEMV: K must be a multiple of 128 and N of 16");
+    if (a.split_rows && !((a.split_rows == 8 && a.M <= 8) || (a.split_rows == 16 && a.M <= 16)))
+        throw std::runtime_error("split GEMV: rows per pass must fit the group (G = 8: M <= 8, G = 16: M <= 16)");
+    const int tiles = a.N / 16, xr = x_rows(a);
+    if (xr > VC_GEMV_MAX_M) throw std::runtime_error("W4A16 GEMV: at most 32 rows per weight pass");
+    GemvPlan p{};
+    p.form = GEMV_FORM_W4;
+    p.waves = W4_WAVES;
+    p.xp = (xr + 7) / 8;
+    p.ksplit = 1;
+    if (a.ksplit > 1) {   // only on request; refused rather than dropped where it cannot be served
+        const size_t cap = a.sk_scratch_floats ? a.sk_scratch_floats : (size_t)4 * 512 * 2 * 256;
+        const int ncnt = a.sk_counters_n ? a.sk_counters_n : 512 * 2;
+        if (a.split_rows || !a.sk_scratch || !a.sk_counters || a.ksplit > a.K / 128 || (size_t)a.ksplit * tiles * 2 * 256 > cap || tiles * 2 > ncnt)
+            throw std::runtime_error("W4A16 GEMV: split-K needs the hand-off buffers (large enough), at most K / 128 slices, and no split rows");
+        p.ksplit = a.ksplit;
+    }
+    if (g_gemv_w4_nt != 0 && g_gemv_w4_nt != 1 && g_gemv_w4_nt != 2 && g_gemv_w4_nt != 4)
+        throw std::runtime_error("W4A16 GEMV: no geometry with that many tiles per workgroup");
+    p.nt = g_gemv_w4_nt ? g_gemv_w4_nt : w4_tiles_per_wg(tiles, p.xp);
+    p.r = kW4Ring[p.nt][p.xp - 1];
+    return p;
+}
+
 GemvPlan gemv_plan(const GemvArgs& a, int epilogue, int variant_knob, int wide_knob) {
+    if (a.w4scale != nullptr) return plan_w4(a);
     if (variant_knob != 0 && gemv_wg_applies(a)) return plan_wg(a, variant_knob);
     if (a.Wp_lo != nullptr)
         throw std::runtime_error("decode GEMV: the weight lo plane of an inexact checkpoint is served by the workgroup-shared split form only "
@@ -873,6 +1105,20 @@ static void launch_wg(const GemvArgs& a, hipStream_t s) {
     VC_LAUNCH((gemv_wg_kernel<NTW, XP, KH, CL, R, EPI, WL, WAVES>), grid, block, shmem, s, a);
 }
 
+template <int NT, int R, int EPI, int XP>
+static void launch_w4(const GemvArgs& a, hipStream_t s) {
+    const dim3 grid(((a.N / 16 + NT - 1) / NT) * (a.ksplit > 1 ? a.ksplit : 1)), block(W4_WAVES * 64);
+    constexpr size_t shmem = (size_t)W4_WAVES * R * (NT + 2 * XP + 1) * 1024;
+    static_assert(shmem + W4_WAVES * 16 * ((XP + 1) / 2) * 4 <= 160 * 1024, "ring exceeds the LDS of a CU");
+    static_assert(R * (NT + 2 * XP + 1) <= 63, "more DMAs in flight than vmcnt counts");
+    static bool once = false;
+    if (!once) {
+        allow_big_lds(gemv_w4_kernel<NT, R, EPI, XP>, shmem);
+        once = true;
+    }
+    VC_LAUNCH((gemv_w4_kernel<NT, R, EPI, XP>), grid, block, shmem, s, a);
+}
+
 // the epilogues a row is instantiated for: I(epilogue, row...) once per epilogue
 #define VC_EPI_ALL(I, ...) I(GEMV_BF16, __VA_ARGS__) I(GEMV_F32, __VA_ARGS__) I(GEMV_RESID_F32, __VA_ARGS__) I(GEMV_SWIGLU, __VA_ARGS__)
 #define VC_EPI_QKV(I, ...) I(GEMV_BF16, __VA_ARGS__)
@@ -908,6 +1154,11 @@ static void launch_wg(const GemvArgs& a, hipStream_t s) {
     X(1, 3, 6, false, 6, VC_EPI_ALL) X(2, 3, 6, false, 6, VC_EPI_ALL) X(3, 2, 6, false, 6, VC_EPI_ALL) X(4, 3, 6, false, 6, VC_EPI_ALL) \
     X(1, 3, 4, true, 6, VC_EPI_ALL) X(2, 3, 4, true, 6, VC_EPI_ALL) X(3, 2, 4, true, 6, VC_EPI_ALL) X(4, 3, 4, true, 6, VC_EPI_ALL)
 
+// every gemv_w4_kernel instance: X(NT, R, XP) — the cells of kW4Ring, all four epilogues each
+#define VC_GEMV_W4_INSTANCES(X)                                                     \
+    X(1, 4, 1) X(1, 3, 2) X(1, 2, 3) X(1, 2, 4) X(2, 3, 1) X(2, 2, 2) X(2, 2, 3) X(2, 2, 4) \
+    X(4, 5, 1) X(4, 3, 2) X(4, 3, 3) X(4, 2, 4)
+
 void launch_gemv(const GemvArgs& a0, int epilogue, hipStream_t s) {
     const GemvPlan p = gemv_plan(a0, epilogue);
     GemvArgs a = a0;
@@ -924,11 +1175,18 @@ void launch_gemv(const GemvArgs& a0, int epilogue, hipStream_t s) {
     if (epilogue == E && p.xp == XP && p.cl == CL && p.r == R && p.wlo == WL && p.waves == WAVES) return launch_wg<XP, CL, R, E, WL, WAVES>(a, s);
 #define VC_ROW_RING(FP8, WAVES, NT, R, XP, EPIS) EPIS(VC_TRY_RING, FP8, WAVES, NT, R, XP)
 #define VC_ROW_WG(XP, CL, R, WL, WAVES, EPIS) EPIS(VC_TRY_WG, XP, CL, R, WL, WAVES)
-    if (p.form == GEMV_FORM_WG) {
+#define VC_TRY_W4(E, NT, R, XP) \
+    if (epilogue == E && p.nt == NT && p.r == R && p.xp == XP) return launch_w4<NT, R, E, XP>(a, s);
+#define VC_ROW_W4(NT, R, XP) VC_EPI_ALL(VC_TRY_W4, NT, R, XP)
+    if (p.form == GEMV_FORM_W4) {
+        VC_GEMV_W4_INSTANCES(VC_ROW_W4)
+    } else if (p.form == GEMV_FORM_WG) {
         VC_GEMV_WG_INSTANCES(VC_ROW_WG)
     } else {
         VC_GEMV_RING_INSTANCES(VC_ROW_RING)
     }
+#undef VC_ROW_W4
+#undef VC_TRY_W4
 #undef VC_ROW_WG
 #undef VC_ROW_RING
 #undef VC_TRY_WG
@@ -987,6 +1245,56 @@ __global__ __launch_bounds__(256) void quantize_fp8_kernel(bf16_t* W, uint8_t* W
 }
 void launch_quantize_fp8(bf16_t* W, uint8_t* Wq, float* scale, int N, int K, hipStream_t s, uint8_t* Wrow) {
     VC_LAUNCH(quantize_fp8_kernel, dim3((unsigned)N), dim3(256), 0, s, W, Wq, scale, N, K, Wrow);
+}
+
+// ---- W4A16 quantiser (load time): MXFP4.  One workgroup per output row n of W [N, K]; a thread takes blocks of 32 consecutive k:
+//   e   = the smallest integer with absmax_block <= 6 * 2^e, clamped from below at -13 (the smallest non-zero effective weight,
+//         0.5 * 2^-13, is then a normal fp16: the bf16 and the fp16 library hold the same bytes); 0 for an all-zero block
+//   q   = e2m1(W / 2^e)  (f2fp4: nearest, ties to the even code)  -> Wq, the super-tile layout of gemv_w4_kernel
+//   scale byte e + 127   -> S [N/16][K/128][64 lanes]
+//   W  <- q * 2^e  IN PLACE (exact in bf16 and in fp16), so prefill, extend and the strict path compute with the weights decode sees.
+__global__ __launch_bounds__(256) void quantize_mxfp4_kernel(bf16_t* W, uint8_t* Wq, uint8_t* S, int N, int K) {
+    const int n = blockIdx.x;
+    bf16_t* row = W + (size_t)n * K;
+    const int nst = K >> 7;
+    for (int c = threadIdx.x; c < (K >> 5); c += 256) {
+        u32x4 v[4];
+        float amax = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] = ld16(row + c * 32 + i * 8);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) amax = fmaxf(amax, fmaxf(fabsf(bf2f_lo(v[i][e])), fabsf(bf2f_hi(v[i][e]))));
+        }
+        int e = 0;
+        if (amax > 0.f) {
+            const uint32_t u = __builtin_bit_cast(uint32_t, amax);
+            e = (int)(u >> 23) - 127 - ((u & 0x007FFFFFu) <= 0x00400000u ? 2 : 1);  // 6 = 1.5 * 2^2
+            e = max(e, -13);
+        }
+        const float s = __builtin_bit_cast(float, (uint32_t)(e + 127) << 23), inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);
+        u32x4 q;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uint32_t qw = 0;
+            u32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t a = f2fp4(bf2f_lo(v[i][j]) * inv), b = f2fp4(bf2f_hi(v[i][j]) * inv);
+                qw |= (a | (b << 4)) << (8 * j);
+                o[j] = pack_bf2(fp42f_sw(a) * s, fp42f_sw(b) * s);
+            }
+            q[i] = qw;
+            st16(row + c * 32 + i * 8, o);
+        }
+        const size_t at = ((size_t)(n >> 4) * nst + (c >> 2)) * 64 + (n & 15) + 16 * (c & 3);
+        st16(Wq + at * 16, q);
+        S[at] = (uint8_t)(e + 127);
+    }
+}
+void launch_quantize_mxfp4(bf16_t* W, uint8_t* Wq, uint8_t* scale, int N, int K, hipStream_t s) {
+    if (K % 128 != 0 || N % 16 != 0) throw std::runtime_error("MXFP4 quantiser: K must be a multiple of 128 and N of 16");
+    VC_LAUNCH(quantize_mxfp4_kernel, dim3((unsigned)N), dim3(256), 0, s, W, Wq, scale, N, K);
 }
 
 // Activation operand of the e4m3 x e4m3 prefill GEMM: every token row of A [M, lda] (bf16) gets its own power-of-two

@@ -246,6 +246,7 @@ struct vc_model {
     int kv_es = 2;      // bytes per element of this session's own KV cache (kc / vc): 2 bf16, 4 fp32 (precision 2)
     int weight_format = 0;  // 0: bf16; 1: W8A16 — decoder linears stored as e4m3 + per-row scales for the decode GEMV;
                             // 2: fp8 — 1 + the prefill GEMMs run e4m3 x e4m3 on the K=128 scaled MFMA (W8A8)
+                            // 3: W4A16 — decoder linears stored as MXFP4 nibbles + E8M0 block scales for the decode GEMV
     Buf s_cols, s_patches, s_vx, s_vxn, s_vqkv, s_vq, s_vk, s_vv, s_vattn, s_vh, s_sel, s_mid, s_feats;
     Buf s_xn, s_qkv, s_q, s_attn, s_h, s_kc, s_vc, s_xl;
     Buf pp_src, pp_sq, pp_tmp, pp_out, pp_tab, pp_f32;

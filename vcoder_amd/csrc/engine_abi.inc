@@ -296,9 +296,12 @@ VC_API int vc_model_set_precision(vc_model* m, int mode) {
  * bf16/fp32.  2: fp8 (BASELINE config C5, "CDNA4 fp8 MFMA") — the same weights; the cached decode steps stream the bytes
  * as in 1 (bf16 activations), and the prefill's decoder linears additionally quantise their activation rows to e4m3
  * (per-token power-of-two scale) and run e4m3 x e4m3 on v_mfma_scale_f32_16x16x128_f8f6f4 at twice the bf16 MFMA rate.
+ * 3: W4A16 — the same seven matrices as MXFP4 (OCP e2m1 elements, one power-of-two E8M0 scale per 32 consecutive k of a row); the
+ * cached decode steps stream the nibbles (bf16 activations), everything else computes with the effective weights q * 2^e, which the
+ * quantiser writes back over the row-major matrices.  Needs hidden and ffn sizes divisible by 128.
  * Must be called before vc_model_finalize. */
 VC_API int vc_model_set_weight_format(vc_model* m, int fmt) {
-    if (!m || fmt < 0 || fmt > 2) return VC_ERR_INVALID;
+    if (!m || fmt < 0 || fmt > 3) return VC_ERR_INVALID;
     if (m->finalized) return VC_ERR_STATE;
     m->weight_format = fmt;
     return VC_OK;
@@ -371,7 +374,12 @@ VC_API int vc_model_finalize(vc_model* m) {
     // decode copy of one decoder linear: MFMA-packed bf16, or (W8A16) e4m3 super-tiles + per-row scales — the quantiser
     // also rewrites the row-major bf16 matrix with the dequantised values so prefill and decode share one set of weights
     auto decode_copy = [&](bf16_t* W, int N, int K, bf16_t*& Wp, float*& Ws, uint8_t*& Wq) {
-        if (m->weight_format >= 1) {
+        if (m->weight_format == 3) {   // W4A16: nibbles + E8M0 block scale bytes (held in the layer's scale slot: engine_linears.inc gemv)
+            Wp = reinterpret_cast<bf16_t*>(walloc<uint8_t>(m, (size_t)N * K / 2));
+            Ws = reinterpret_cast<float*>(walloc<uint8_t>(m, (size_t)N * K / 32));
+            Wq = nullptr;
+            launch_quantize_mxfp4(W, reinterpret_cast<uint8_t*>(Wp), reinterpret_cast<uint8_t*>(Ws), N, K, m->st);
+        } else if (m->weight_format >= 1) {
             Wp = reinterpret_cast<bf16_t*>(walloc<uint8_t>(m, (size_t)N * K));
             Ws = walloc<float>(m, N);
             Wq = m->weight_format == 2 ? walloc<uint8_t>(m, (size_t)N * K) : nullptr;
@@ -381,7 +389,9 @@ VC_API int vc_model_finalize(vc_model* m) {
             launch_pack_weight(W, Wp, N, K, m->st);
         }
     };
-    if (m->weight_format >= 1)
+    if (m->weight_format == 3)
+        REQUIRE(D % 128 == 0 && F % 128 == 0, VC_ERR_INVALID, "W4A16 (MXFP4) needs hidden and ffn sizes divisible by 128 (got %d, %d)", D, F);
+    else if (m->weight_format >= 1)
         REQUIRE(D % 64 == 0 && F % 64 == 0, VC_ERR_INVALID, "W8A16 needs hidden and ffn sizes divisible by 64");
     if (m->weight_format == 2)
         REQUIRE(D % 128 == 0 && F % 128 == 0, VC_ERR_INVALID, "the fp8 prefill GEMM needs hidden and ffn sizes divisible by 128");

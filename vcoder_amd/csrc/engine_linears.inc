@@ -122,7 +122,9 @@ void gemv(vc_model* m, const LoopView& v, const bf16_t* X, const bf16_t* Wp, con
         GemvArgs a{};
         a.X = X + xrow0 * K;
         a.Wp = Wp;
-        a.wscale = wscale;
+        // W4A16 keeps its E8M0 block-scale bytes where the e4m3 formats keep their per-row scales (lm_head: bf16, no scales)
+        if (root_of(m)->weight_format == 3 && wscale != nullptr) a.w4scale = reinterpret_cast<const uint8_t*>(wscale);
+        else a.wscale = wscale;
         a.out = reinterpret_cast<char*>(out) + (f32out ? (size_t)m0 : xrow0) * ldo * esz;
         a.M = std::min(pass, M - m0);
         a.N = N;

@@ -306,7 +306,7 @@ std::mutex g_pool_create;
 // can serve EVERY matrix of the model, else the per-wave-ring form's two passes of 16
 int pool_split_G(const vc_model* root) {
     const vc_model_cfg& c = root->c;
-    const bool fp8w = root->weight_format != 0;
+    const bool fp8w = root->weight_format != 0;   // (W4A16 included: like the e4m3 formats it is served by per-wave rings only)
     return (gemv_wg_enabled() && gemv_wg_applies(c.hidden, fp8w) && gemv_wg_applies(c.ffn, fp8w)) ? 32 : 16;
 }
 

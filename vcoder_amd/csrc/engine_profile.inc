@@ -299,7 +299,8 @@ VC_API int vc_profile_decode_gemv(vc_model* m, int B, int reps, int* launches, d
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, m->ev[0], m->ev[1]));
     const int n = 4 * c.layers + 1;
-    const double wb = m->weight_format >= 1 ? 1.0 : 2.0;  // bytes per decoder-linear weight (lm_head stays bf16)
+    // bytes per decoder-linear weight (lm_head stays bf16); W4A16: a nibble + 1/32 of a scale byte
+    const double wb = root_of(m)->weight_format == 3 ? 0.5 + 1.0 / 32.0 : m->weight_format >= 1 ? 1.0 : 2.0;
     const double bytes = wb * (double)c.layers * (4.0 * D * D + 3.0 * D * F) + 2.0 * (double)D * c.vocab;
     if (launches) *launches = n;
     if (avg_us) *avg_us = (double)ms * 1e3 / ((double)reps * n);

@@ -337,6 +337,48 @@ VCK_EXPORT int vck_gemv_plan(int M, int N, int K, int epi, int fp8, int split_ro
         return -1;
     }
 }
+/* W4A16 (MXFP4): the load-time quantiser and the nibble-streaming decode GEMV (kernels.h GemvArgs::w4scale) */
+VCK_EXPORT void vck_quantize_mxfp4(uint16_t* W, uint8_t* Wq, uint8_t* scale, int N, int K, void* stream) {
+    launch_quantize_mxfp4(W, Wq, scale, N, K, S(stream));
+}
+static GemvArgs w4_args(const uint16_t* X, const void* Wq, const uint8_t* w4scale, void* out, const float* ssq_in, float* ssq_out,
+                        const float* xg_w, uint16_t* xg_out, int npart, float eps, float* sk_scratch, unsigned* sk_counters, int ksplit,
+                        int M, int N, int K, int ldo, int G) {
+    GemvArgs a{};
+    a.X = X; a.Wp = reinterpret_cast<const uint16_t*>(Wq); a.w4scale = w4scale; a.out = out; a.M = M; a.N = N; a.K = K; a.ldo = ldo;
+    a.ssq_in = ssq_in; a.ssq_out = ssq_out; a.xg_w = xg_w; a.xg_out = xg_out; a.npart = npart; a.eps = eps;
+    a.sk_scratch = sk_scratch; a.sk_counters = sk_counters; a.ksplit = ksplit;
+    a.split_rows = G;
+    return a;
+}
+VCK_EXPORT void vck_gemv_w4(const uint16_t* X, const void* Wq, const uint8_t* w4scale, void* out, const float* ssq_in, float* ssq_out,
+                            const float* xg_w, uint16_t* xg_out, int npart, float eps, float* sk_scratch, unsigned* sk_counters,
+                            int ksplit, int M, int N, int K, int ldo, int epi, void* stream) {
+    launch_gemv(w4_args(X, Wq, w4scale, out, ssq_in, ssq_out, xg_w, xg_out, npart, eps, sk_scratch, sk_counters, ksplit, M, N, K, ldo, 0), epi,
+                S(stream));
+}
+VCK_EXPORT void vck_gemv_w4_split(const uint16_t* X, const void* Wq, const uint8_t* w4scale, void* out, const float* ssq_in,
+                                  float* ssq_out, const float* xg_w, uint16_t* xg_out, int npart, float eps, int M, int N, int K, int ldo,
+                                  int epi, int G, void* stream) {
+    launch_gemv(w4_args(X, Wq, w4scale, out, ssq_in, ssq_out, xg_w, xg_out, npart, eps, nullptr, nullptr, 0, M, N, K, ldo, G), epi, S(stream));
+}
+/* what vck_gemv_w4 / vck_gemv_w4_split would launch: 0 and out = {form, waves, nt, r, xp, ksplit, workgroups}, or -1 where refused */
+VCK_EXPORT int vck_gemv_w4_plan(int M, int N, int K, int epi, int split_rows, int ksplit, int has_sk, int out[7]) {
+    static float present_f;
+    static unsigned present_u;
+    static const uint8_t present_b = 0;
+    const GemvArgs a = w4_args(nullptr, nullptr, &present_b, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f, has_sk ? &present_f : nullptr,
+                               has_sk ? &present_u : nullptr, ksplit, M, N, K, N, split_rows);
+    try {
+        const GemvPlan p = gemv_plan(a, epi);
+        const int v[7] = {p.form, p.waves, p.nt, p.r, p.xp, p.ksplit, (N / 16 + p.nt - 1) / p.nt * p.ksplit};
+        for (int i = 0; i < 7; ++i) out[i] = v[i];
+        return 0;
+    } catch (const std::runtime_error&) {
+        return -1;
+    }
+}
+VCK_EXPORT void vck_set_gemv_w4_nt(int nt) { set_gemv_w4_nt(nt); }
 /* split-mode GEMV: 0 = per-wave rings, 1 / -1 = workgroup-shared activation chunks (default) */
 VCK_EXPORT void vck_set_gemv_variant(int v) { set_gemv_variant(v); }
 VCK_EXPORT void vck_set_gemm_force_8phase(int on) { set_gemm_force_8phase(on != 0); }

@@ -146,6 +146,9 @@ struct GemvArgs {
     // the packed lo plane of an inexact checkpoint's weight (w = bf16 hi + bf16 lo; same layout as Wp), or nullptr.  Precision mode
     // "split" on the workgroup-shared kernel only: out[m] = x_hi.w_hi + x_lo.w_hi + x_hi.w_lo
     const bf16_t* Wp_lo;
+    // W4A16 (MXFP4): Wp holds e2m1 nibbles in the 128-wide super-tile layout and w4scale one E8M0 byte per block of 32 k
+    // ([N/16][K/128][64 lanes]: launch_quantize_mxfp4); nullptr = another format.  K % 128 == 0; wscale and Wp_lo stay null.
+    const uint8_t* w4scale;
 };
 void launch_gemv(const GemvArgs& a, int epilogue, hipStream_t s);
 // What launch_gemv launches for a call: the kernel instance and the K-slices, a pure function of the arguments and the two knobs
@@ -154,6 +157,7 @@ enum GemvForm : int {
     GEMV_FORM_RING = 0,  // gemv_dma_kernel, pair / single-tile geometry by tile-count class
     GEMV_FORM_WIDE = 1,  // gemv_dma_kernel, one deep-ringed workgroup per CU
     GEMV_FORM_WG = 2,    // gemv_wg_kernel (precision mode "split")
+    GEMV_FORM_W4 = 3,    // gemv_w4_kernel (W4A16: GemvArgs::w4scale)
 };
 struct GemvPlan {
     int form;
@@ -176,6 +180,12 @@ unsigned long gemv_wg_launches();   // launches served by the workgroup-shared f
 void launch_pack_weight(const bf16_t* W, bf16_t* Wp, int N, int K, hipStream_t s);
 // W [N,K] bf16 -> e4m3 packed + per-row scales; W is overwritten with the dequantised values (see decode.hip)
 void launch_quantize_fp8(bf16_t* W, uint8_t* Wq, float* scale, int N, int K, hipStream_t s, uint8_t* Wrow = nullptr);
+// W [N,K] -> MXFP4: e2m1 nibbles Wq [N * K / 2] in the W4A16 GEMV's super-tile order + E8M0 block scales [N * K / 32]; W is overwritten
+// with the effective weights q * 2^e (decode.hip).  K % 128 == 0, N % 16 == 0
+void launch_quantize_mxfp4(bf16_t* W, uint8_t* Wq, uint8_t* scale, int N, int K, hipStream_t s);
+// tiles per workgroup of the W4A16 GEMV: 0 = by the tile count (default), 1 / 2 / 4 = that geometry for every matrix (tests, A/B; the
+// K partition, hence every bit of the result, is the same)
+void set_gemv_w4_nt(int nt);
 // token rows of A [M, lda] bf16 -> e4m3 bytes Q [M, K] + per-row power-of-two scales (K % 16 == 0)
 void launch_quant_act_rows(const bf16_t* A, int lda, uint8_t* Q, float* scale, int M, int K, hipStream_t s);
 // interleave gate/up rows: out[2f] = gate[f], out[2f+1] = up[f]

@@ -217,6 +217,45 @@ VC_DEV uint32_t f32x4_to_fp8x4(float a, float b, float c, float d) {
     return (uint32_t)f2fp8(a) | ((uint32_t)f2fp8(b) << 8) | ((uint32_t)f2fp8(c) << 16) | ((uint32_t)f2fp8(d) << 24);
 }
 
+// ---- fp4 (OCP e2m1: sign, 2 exponent bits, 1 mantissa bit; magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6) + one E8M0 scale per block of 32
+// consecutive k: MXFP4, the W4A16 weight format (decode.hip quantize_mxfp4_kernel).  Encode is software on both builds (load-time
+// only; round to nearest, ties to the even code; the sign bit is copied from the input), so the device, the emulator and
+// vcoder_amd/quant.py produce identical nibbles.  |x| <= 6 by construction of the block scale: no saturation.
+VC_DEV uint32_t f2fp4(float x) {
+    const float a = __builtin_fabsf(x);
+    const uint32_t code = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) +
+                          (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.f);
+    return ((__builtin_bit_cast(uint32_t, x) >> 28) & 8u) | code;
+}
+VC_DEV float fp42f_sw(uint32_t c) {
+    const uint32_t e = (c >> 1) & 3u, m = c & 1u;
+    const float mag = e == 0 ? 0.5f * (float)m : __builtin_bit_cast(float, ((e + 126u) << 23) | (m << 22));
+    return (c & 8u) ? -mag : mag;
+}
+// the power of two an E8M0 byte stands for (the quantiser keeps the byte within [114, 253]: a normal fp32)
+VC_DEV float e8m0_to_f32(uint32_t b) { return __builtin_bit_cast(float, b << 23); }
+// 8 packed e2m1 (k even in the low nibble of a byte, k + 1 in the high one) times a power-of-two scale -> 8 values of the 16-bit
+// operand format (four packed words), exact: every q * 2^e the quantiser produces is representable.  On the device one
+// v_cvt_scalef32_pk_{bf16,f16}_fp4 per byte.
+#ifdef VC_EMU
+VC_DEV u32x4 fp4x8_to_bf16x8(uint32_t v, float scale) {
+    u32x4 r;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) r[b] = pack_bf2(fp42f_sw((v >> (8 * b)) & 15u) * scale, fp42f_sw((v >> (8 * b + 4)) & 15u) * scale);
+    return r;
+}
+#else
+VC_DEV u32x4 fp4x8_to_bf16x8(uint32_t v, float scale) {
+#ifdef VC_F16
+#define VC_CVT_FP4(sel) __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, scale, sel))
+#else
+#define VC_CVT_FP4(sel) __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, sel))
+#endif
+    return u32x4{VC_CVT_FP4(0), VC_CVT_FP4(1), VC_CVT_FP4(2), VC_CVT_FP4(3)};
+#undef VC_CVT_FP4
+}
+#endif
+
 // ---- MFMA ----------------------------------------------------------------------------------
 #ifndef VC_EMU
 #ifdef VC_F16
@@ -392,6 +431,7 @@ VC_DEV u32x4 ld16(const void* p) { VC_LDS_R(p); return *reinterpret_cast<const u
 VC_DEV void st16(void* p, u32x4 v) { VC_LDS_W(p); *reinterpret_cast<u32x4*>(p) = v; }
 VC_DEV u32x2 ld8(const void* p) { VC_LDS_R(p); return *reinterpret_cast<const u32x2*>(p); }
 VC_DEV void st8(void* p, u32x2 v) { VC_LDS_W(p); *reinterpret_cast<u32x2*>(p) = v; }
+VC_DEV uint32_t ld1(const void* p) { VC_LDS_R(p); return *reinterpret_cast<const uint8_t*>(p); }
 VC_DEV f32x4 ld16f(const void* p) { VC_LDS_R(p); return *reinterpret_cast<const f32x4*>(p); }
 VC_DEV void st16f(void* p, f32x4 v) { VC_LDS_W(p); *reinterpret_cast<f32x4*>(p) = v; }
 

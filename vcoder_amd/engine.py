@@ -160,8 +160,10 @@ class HipEngine:
         """'bf16' (default); 'w8a16': decoder linears as e4m3 + per-row power-of-two scales, quantised at finalize and
         streamed as bytes by the decode steps, bf16 activations everywhere; 'fp8' (BASELINE configs[4]): the same weights,
         and the prefill's decoder linears also quantise their activation rows to e4m3 and run on the K=128 scaled fp8 MFMA
-        (W8A8).  vcoder_amd/quant.py is the host restatement of both quantisers.  Before finalize()."""
-        code = {"bf16": 0, "w8a16": 1, "fp8": 2}[fmt]
+        (W8A8); 'w4a16': decoder linears as MXFP4 (e2m1 elements, one power-of-two scale per 32 consecutive k), streamed as
+        nibbles by the decode steps, bf16 activations everywhere; needs hidden and ffn sizes divisible by 128.
+        vcoder_amd/quant.py is the host restatement of the quantisers.  Before finalize()."""
+        code = {"bf16": 0, "w8a16": 1, "fp8": 2, "w4a16": 3}[fmt]
         self._check(self.lib.vc_model_set_weight_format(self._model, code))
         self.weight_format = fmt
 

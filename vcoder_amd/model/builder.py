@@ -5,7 +5,8 @@ builder.py:93-108), same processor aliasing (:145-151) and context_len rule (:13
 reference: bitsandbytes LLM.int8, builder.py:31-33) selects this build's 8-bit weight format instead: W8A16, decoder
 linears as fp8-e4m3 with per-row power-of-two scales (vcoder_amd/quant.py).  `model_base` selects the reference's two
 overlay paths (builder.py:42-92): LoRA adapters are merged on the host (W + alpha / r * B A, what peft's merge_and_unload
-computes), projector-only checkpoints overlay `mm_projector.bin`.  4-bit (NF4) raises."""
+computes), projector-only checkpoints overlay `mm_projector.bin`.  `load_4bit=True` raises: it promises bitsandbytes NF4, which this
+build does not have; its 4-bit format is MXFP4, selected with `weight_format="w4a16"`."""
 from __future__ import annotations
 
 from .language_model import LlavaLlamaForCausalLM, VCoderDSLlavaLlamaForCausalLM, VCoderLlavaLlamaForCausalLM
@@ -16,12 +17,14 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
     """Signature and return value of the reference's loader (builder.py:25,154).  load_8bit=True selects the 8-bit
     weight format of this build, 'w8a16' (e4m3 decoder weights, bf16 activations); `weight_format` (an addition, keyword
     only in practice) names a format directly: 'bf16' | 'w8a16' | 'fp8' (the latter also runs the prefill linears on
-    e4m3 activations — BASELINE configs[4]; faster, and noisier: DESIGN.md section 4.2b).  `operands` (an addition): 'bf16' — the
+    e4m3 activations — BASELINE configs[4]; faster, and noisier: DESIGN.md section 4.2b) | 'w4a16' (MXFP4 decoder weights, bf16
+    activations; not the NF4 that `load_4bit` asks the reference for, so that flag keeps raising).  `operands` (an addition): 'bf16' — the
     benchmarked library; 'fp16' — libvcoder_hip_f16.so, IEEE fp16 MFMA operands, what the reference's torch_dtype=torch.float16
     (builder.py:39) and its fp16 tower (:142) compute with: an fp16 checkpoint is held exactly."""
     if load_4bit:
         raise NotImplementedError("bitsandbytes NF4 loading is a CUDA-only path of the reference; the MI355X build runs "
-                                  "bf16 weights or, with load_8bit=True, fp8-e4m3 decoder weights (W8A16)")
+                                  "bf16 weights or, with load_8bit=True, fp8-e4m3 decoder weights (W8A16); its 4-bit format is "
+                                  "MXFP4, selected with weight_format=\"w4a16\"")
     name = model_name.lower()
     if "llava" not in name:
         raise ValueError(f"'{model_name}': only LLaVA-family checkpoints (llava / vcoder_llava / vcoder_ds_llava) are "
