@@ -340,6 +340,24 @@ int vc_request_generate_logprobs(vc_model* m, int top_k, float* token_logprobs /
                                  float* top_logprobs /* [B, max_new, top_k] host, NULL iff top_k == 0 */,
                                  int32_t* top_ids /* same shape */, size_t cap_rows /* >= B * max_new of the call it applies to */);
 
+/* Prompt-lookup speculative decoding for the NEXT vc_generate / vc_generate_greedy* call (one-shot; HF's prompt_lookup_num_tokens).
+ * Each step of the call's loop drafts up to k ids per sequence — the ids behind the latest earlier occurrence of the sequence's last
+ * max_ngram .. 1 ids in (lookup ids | prompt ids | ids generated so far) — runs the last emitted id and the drafts through the
+ * decoder as k + 1 rows of ONE weight pass (a verify attention that reproduces the plain step's bits per row), and emits the model's
+ * own greedy tokens for as long as the drafts agree with them.  The ids, n_generated and log-probs are those of the same call without
+ * the request, in fewer steps.  lookup_ids: what the caller expects the answer to resemble (a previous turn, a class list), the B
+ * sequences' ids back to back, lookup_lens[b] each; NULL / NULL: none.
+ * Served on the session's own loop (whatever VC_POOL says) when the call is greedy, has no logits processors, runs in the bf16
+ * precision mode, B * (k + 1) <= 32, and the score rows of k + 1 queries over the call's cache fit a CU's LDS; otherwise the call runs
+ * as without the request.  vc_generate_beam ignores it.  Behind a served call the rows stand at different positions: vc_decode_step
+ * and vc_extend refuse (VC_ERR_STATE) until the next prefill.  k outside 1 .. 7, max_ngram outside 1 .. 4, lengths outside
+ * 0 .. max_position_embeddings or more than 16 sequences: VC_ERR_INVALID here, nothing changed; a B other than the call's makes that
+ * call fail with VC_ERR_INVALID.  Cleared when that call returns, also when it fails; k == 0 cancels. */
+int vc_request_speculation(vc_model* m, int k, int max_ngram, const int32_t* lookup_ids, const int32_t* lookup_lens, int B);
+/* Per-sequence counters of the last vc_generate* call of this session: out[b] = {verify steps, tokens they emitted, drafts proposed,
+ * drafts accepted}.  VC_ERR_STATE when that call did not speculate. */
+int vc_last_speculation(vc_model* m, int32_t* out /* [B][4] */, int B);
+
 /* Logits processors of the NEXT vc_generate / vc_generate_greedy* call (one-shot), applied on the device in front of every selection
  * of the loop, in HF 4.31's order (generation/logits_process.py):
  *   repetition_penalty p   RepetitionPenaltyLogitsProcessor: every id t of the row's history gets raw[t] < 0 ? raw[t] * p : raw[t] / p

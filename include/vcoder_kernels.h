@@ -91,6 +91,15 @@ void vck_attention_decode_fused(const uint16_t* qkv, uint16_t* k, uint16_t* v, u
 void vck_attention_decode_rows(const uint16_t* qkv, uint16_t* k, uint16_t* v, uint16_t* out, int B, int H, int hd,
                                int kv_stride, const int* pos_rows, int pos_stride, const int* active_rows,
                                const float* rope_cos, const float* rope_sin, float scale, void* stream);
+/* verify attention (prompt-lookup speculation): nq[b] <= Q <= 8 consecutive query rows of sequence b — rows b * Q + j of qkv
+ * [B * Q, 3 H hd] and out [B * Q, H hd] at positions pos_rows[b * pos_stride] + j — roped, appended to the cache (bf16, or e4m3
+ * bytes when kv8) and attended in one launch over one read of the K and V streams.  Row j's output and the appended cache rows
+ * are bit-identical to what vck_attention_decode_rows gives the row in a step of its own (an exactly-zero output may differ in
+ * sign).  nq[b] <= 0 leaves sequence b untouched.  key_mask as above or NULL.  hd 128 or 64.  Returns 0, or -1 when the score
+ * rows of Q queries over kv_stride keys do not fit the LDS of a CU (nothing is launched). */
+int vck_attention_verify(const uint16_t* qkv, void* k, void* v, uint16_t* out, int B, int H, int hd, int kv_stride, int Q,
+                         const int* pos_rows, int pos_stride, const int* nq, const float* rope_cos, const float* rope_sin,
+                         float scale, int kv8, const uint8_t* key_mask, int mask_stride, void* stream);
 /* extend attention (a multi-token continuation of a cached sequence): n roped queries per (b, h) (q [B,H,q_stride,hd]) at
  * positions P .. P+n-1 over keys [0, P+n) of the key-major decode cache (k, v [B,H,kv_stride,hd]: bf16, or e4m3 bytes when
  * kv8), causal inside the chunk; key_mask [B][mask_stride] bytes (0 = hidden; key 0 must be visible) or NULL.  hd 128.
@@ -114,6 +123,25 @@ void vck_select_embed(const float* logits, int ldl, int* rows, int* next_tok, in
                       float* ssq, const float* xg_w, uint16_t* xg, int D, int npart, int V, int nrows, int advance,
                       void* stream);
 int vck_row_state_stride(void);
+/* Prompt-lookup speculation, one workgroup per sequence (csrc/select.hip; records as above, sequence b = rows[b]).
+ * vck_spec_draft: the corpus of a sequence is its lookup ids (lookup [B][lookup_stride], lookup_len [B]; NULL: none) | a separator
+ * no window may touch | its prompt ids (prompt [B][prompt_stride], prompt_len [B] of them or, NULL, all; placeholders and all) | the
+ * ids generated so far.  For ng = max_ngram .. 1
+ * (an ng longer than prompt + generated is not tried) the last ng ids are sought at every earlier start; the latest match of the
+ * first ng with a match decides; the ids behind it are the drafts — at most min(k, Q - 1, slots left - 1), cut at the corpus end and
+ * at the first id outside [0, V).  tok [B * Q] = last emitted id, drafts, pad; nq [B] = 1 + drafts, 0 for an inactive, finished or
+ * full row (whose token rows are pad).
+ * vck_spec_accept: logits [B * Q, ldl]; a_j = argmax of row j (ties to the lower id); the leading drafts tok[j] == a_(j-1) are
+ * accepted and a_0 .. a_n go one by one through the bookkeeping vck_select_embed applies to its token (EOS, stop sequences, the
+ * row's last slot: a finishing token cuts the rest); words 2 / 3 of the record advance by the number emitted; next_tok[b] = the last
+ * emitted id; counters [B][4] += {1, emitted, nq - 1, emitted - 1} (NULL: none).  lp_tok != NULL: the emitted rows' entries of
+ * scratch_lp / scratch_ids ([B * Q, scratch_k], a vck_topk_logprob over the rows) go to the slabs at the ids' slots: lp_tok = entry 0,
+ * lp_top / lp_ids = the first lp_k entries. */
+void vck_spec_draft(const int* rows, const int* out_ids, const int* lookup, const int* lookup_len, int lookup_stride, const int* prompt,
+                    const int* prompt_len, int prompt_stride, int* tok, int* nq, int B, int Q, int k, int max_ngram, int V, void* stream);
+void vck_spec_accept(const float* logits, int ldl, int V, int* rows, int* next_tok, int* out_ids, const int* tok, const int* nq, int B,
+                     int Q, int* counters, const float* scratch_lp, const int* scratch_ids, int scratch_k, float* lp_tok, float* lp_top,
+                     int* lp_ids, int lp_k, void* stream);
 /* test hook of the sampler: u[i] = the uniform in (0,1) the Gumbel-max draw derives from 32-bit hash h[i] (strictly
  * inside the interval for EVERY h, so the Gumbel term -log(-log(u)) written to gumbel[i] is finite) */
 void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, void* stream);

@@ -800,6 +800,38 @@ def bench_dattn():
     print(f"decode attention ctx={pos + 1}: {us:7.1f} us  {4.0 * B * (pos + 1) * D / us / 1e3:7.1f} GB/s", flush=True)
 
 
+def bench_attention_verify():
+    """attention_verify_kernel (Q query rows per sequence, one read of the K / V streams) beside the fused decode attention it
+    replaces Q launches of: 7b heads, a context of 1216 keys, bf16 and e4m3 caches; B = 1 at Q = 2 / 4 / 8 and B = 4 at Q = 8"""
+    H, hd, pos, S = 32, 128, 1216, 1408
+    D = H * hd
+    cos, sin = torch.rand(S, hd // 2, device=dev), torch.rand(S, hd // 2, device=dev)
+    scale = C.c_float(1 / math.sqrt(hd))
+    for kv8 in (0, 1):
+        for B, Q in ((1, 2), (1, 4), (1, 8), (4, 8)):
+            es = 1 if kv8 else 2
+            ks = [torch.randint(0, 120, (B, H, S, hd * es), dtype=torch.uint8, device=dev) for _ in range(4)]
+            vs = [torch.randint(0, 120, (B, H, S, hd * es), dtype=torch.uint8, device=dev) for _ in range(4)]
+            qkv, qkv1 = bf16(B * Q, 3 * D), bf16(B, 3 * D)
+            out, out1 = torch.zeros((B * Q, D), dtype=torch.bfloat16, device=dev), torch.zeros((B, D), dtype=torch.bfloat16, device=dev)
+            rec = torch.tensor([[1, pos]] * B, dtype=torch.int32, device=dev)
+            nq = torch.full((B,), Q, dtype=torch.int32, device=dev)
+            it = [0]
+
+            def verify():
+                it[0] += 1
+                lib.vck_attention_verify(P(qkv), P(ks[it[0] % 4]), P(vs[it[0] % 4]), P(out), B, H, hd, S, Q, C.c_void_p(rec.data_ptr() + 4), 2,
+                                         P(nq), P(cos), P(sin), scale, 3 if kv8 else 0, None, 0, None)
+
+            def plain():
+                it[0] += 1
+                lib.vck_attention_decode_masked(P(qkv1), P(ks[it[0] % 4]), P(vs[it[0] % 4]), P(out1), B, H, hd, S, C.c_void_p(rec.data_ptr() + 4),
+                                                2, C.c_void_p(rec.data_ptr()), P(cos), P(sin), scale, 3 if kv8 else 0, 0, None, 0, None)
+            uv, up = timeit(verify, iters=40), timeit(plain, iters=40)
+            print(f"attention_verify {'e4m3' if kv8 else 'bf16'} B {B} Q {Q} ctx {pos + Q}: {uv:7.1f} us | decode attention B {B} ctx {pos + 1}: "
+                  f"{up:7.1f} us  (x{uv / up:4.2f}; {Q} plain launches {Q * up:7.1f} us)", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["gemm", "gemv", "attn", "dattn"]
     table = {"gemm_qkv": bench_gemm_qkv, "gemm": bench_gemm, "gemv": bench_gemv, "attn": bench_attn, "dattn": bench_dattn, "gemv_fp8": bench_gemv_fp8,
@@ -808,6 +840,6 @@ if __name__ == "__main__":
              "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,
              "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn, "token_logprob": bench_token_logprob,
              "topk_logprob": bench_topk_logprob, "logits_process": bench_logits_process,
-             "score_head": bench_score_head, "gemv_formats": bench_gemv_formats, "gemv_w4": lambda: bench_gemv_formats(("w4",))}
+             "score_head": bench_score_head, "attention_verify": bench_attention_verify, "gemv_formats": bench_gemv_formats, "gemv_w4": lambda: bench_gemv_formats(("w4",))}
     for w in what:
         table[w]()

@@ -120,6 +120,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_request_top_logprobs.restype = C.c_int
     lib.vc_request_generate_logprobs.argtypes = [vp, i32, vp, vp, vp, C.c_size_t]
     lib.vc_request_generate_logprobs.restype = C.c_int
+    lib.vc_request_speculation.argtypes = [vp, i32, i32, vp, vp, i32]
+    lib.vc_request_speculation.restype = C.c_int
+    lib.vc_last_speculation.argtypes = [vp, vp, i32]
+    lib.vc_last_speculation.restype = C.c_int
     lib.vck_topk_logprob.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.vck_topk_logprob.restype = None
     lib.vc_request_logits_processors.argtypes = [vp, C.POINTER(LogitsProcessors)]

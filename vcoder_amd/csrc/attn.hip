@@ -1093,4 +1093,317 @@ void launch_attention_decode_fused(const AttnDecodeFusedArgs& a, hipStream_t s) 
     }
 }
 
+// =============================================================================================
+// Verify attention (speculative decoding): nq <= Q <= 8 consecutive query rows of ONE sequence — activation rows b * Q + j at
+// positions pos + j — in one launch over one read of the K and the V stream.  Query j's output row and the cache rows appended for
+// it are the bits attention_decode_fused_kernel gives that row in a step of its own, because per query nothing about the arithmetic
+// changes: the key -> (wave, window slot, key row) map (UK, KPW and BATCH are the decode kernel's), lanes_sum over a key row's lanes,
+// the per-thread stride-512 max / sum of the softmax followed by the wave and the 8-wave reductions, the lane and wave order of the V
+// pass, __expf, the bf16 rounding of q.  What differs is invisible to a query: its score row runs to the CHUNK's padded end, and the
+// keys between its own context and that end carry -inf -> p = 0 (they add +-0 to sums; an exactly-zero output may differ in sign),
+// while the decode kernel re-reads its last valid row there, also under p = 0.
+//   phase 0  64 threads per query: rotate q / k, append the K and V rows, q (bf16-rounded) to LDS
+//   phase 1  every loaded key row dotted against the nq queries -> sc[j][key]; query j sees keys <= pos + j
+//   phase 2  softmax per query
+//   phase 3  V rows into nq accumulator sets; `part` serves the queries one after another
+// Scores: Q rows of kv_stride + BATCH floats of dynamic LDS.
+// =============================================================================================
+// One accumulation acc + pk * v of the V pass, rounded as the COMPILED decode kernel rounds it.  The source of both kernels says
+// `acc[e] += pk * v`; under the default contraction the back end makes that an fma for every element of a lane except its last
+// two, whose accumulators the vectorizer turns into a two-wide add chain behind two-wide products (v_pk_mul_f32 + v_pk_add_f32 in
+// every instantiation and both operand formats of attention_decode_fused_kernel): there the product is rounded before the add.
+// In this kernel's larger loop body the same source line contracts everywhere, so the choice is spelled out here.  (The emulator
+// build compiles both kernels for the host, where the plain expression means the same thing in both.)
+template <bool LAST_PAIR> VC_DEV float vacc(float acc, float pk, float v) {
+#ifdef VC_EMU
+    return acc + pk * v;
+#else
+    if constexpr (LAST_PAIR) {
+#pragma clang fp contract(off)
+        const float t = pk * v;
+        return acc + t;
+    } else {
+        return __builtin_fmaf(pk, v, acc);
+    }
+#endif
+}
+
+template <int HD, int UK, bool F8, int QM>
+__global__ __launch_bounds__(512) void attention_verify_kernel(AttnVerifyArgs p) {
+    constexpr int EPL = F8 ? 16 : 8;
+    constexpr int ESZ = F8 ? 1 : 2;
+    constexpr int ROWB = HD * ESZ;
+    constexpr int LPK = HD / EPL;
+    constexpr int KPW = 64 / LPK;
+    constexpr int BATCH = 8 * KPW * UK;
+    VC_DYNAMIC_SMEM(float, sc);   // [Q][kv_stride + BATCH]
+    __shared__ __attribute__((aligned(16))) float q_s[QM][HD];
+    __shared__ __attribute__((aligned(16))) float part[8][HD];
+    __shared__ float red[QM][8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x, b = blockIdx.y;
+    const size_t bh = (size_t)b * p.H + h;
+    const int pos = p.pos_dev[(size_t)b * p.pos_stride];
+    // queries of this sequence: none skips it; never more than the launch's Q or than the cache holds behind pos
+    const int nq = min(min(p.nq_dev[b], min(p.Q, QM)), p.kv_stride - pos);
+    if (nq <= 0 || pos < 0) return;
+    const int srow = p.kv_stride + BATCH;
+    const int ctx = pos + nq;   // keys of the last query
+    const int D = p.H * HD;
+    char* kbase = reinterpret_cast<char*>(p.k) + bh * p.kv_stride * ROWB;
+    char* vbase = reinterpret_cast<char*>(p.v) + bh * p.kv_stride * ROWB;
+    const int krow = lane / LPK, kcol = (lane % LPK) * EPL;
+    auto row_off = [&](int key) { return (uint32_t)(min(key, ctx - 1) * ROWB) + (uint32_t)(kcol * ESZ); };
+    // ---- phase 0: query j = tid / 64 at position pos + j
+    {
+        const int j = tid >> 6, d = tid & 63;
+        if (j < nq && d < HD / 2) {
+            const int pj = pos + j;
+            const float c = p.rope_cos[(size_t)pj * (HD / 2) + d], s = p.rope_sin[(size_t)pj * (HD / 2) + d];
+            const bf16_t* row = p.qkv + ((size_t)b * p.Q + j) * (3 * D) + h * HD;
+            const bf16_t rq0 = row[d], rq1 = row[d + HD / 2], rk0 = row[D + d], rk1 = row[D + d + HD / 2];
+            const bf16_t v0 = row[2 * D + d], v1 = row[2 * D + d + HD / 2];
+            const float q0 = bf2f(rq0), q1 = bf2f(rq1);
+            const float k0 = bf2f(rk0), k1 = bf2f(rk1);
+            q_s[j][d] = bf2f(f2bf(q0 * c - q1 * s));
+            q_s[j][d + HD / 2] = bf2f(f2bf(q1 * c + q0 * s));
+            if constexpr (F8) {
+                uint8_t* ko = reinterpret_cast<uint8_t*>(kbase) + (size_t)pj * HD;
+                ko[d] = f2fp8(bf2f(f2bf(k0 * c - k1 * s)));
+                ko[d + HD / 2] = f2fp8(bf2f(f2bf(k1 * c + k0 * s)));
+                uint8_t* vo = reinterpret_cast<uint8_t*>(vbase) + (size_t)pj * HD;
+                vo[d] = f2fp8(bf2f(v0));
+                vo[d + HD / 2] = f2fp8(bf2f(v1));
+            } else {
+                bf16_t* ko = reinterpret_cast<bf16_t*>(kbase) + (size_t)pj * HD;
+                ko[d] = f2bf(k0 * c - k1 * s);
+                ko[d + HD / 2] = f2bf(k1 * c + k0 * s);
+                bf16_t* vo = reinterpret_cast<bf16_t*>(vbase) + (size_t)pj * HD;
+                vo[d] = v0;
+                vo[d + HD / 2] = v1;
+            }
+        }
+    }
+    __syncthreads();  // workgroup-scope release/acquire: the appended K / V rows are visible to this block
+    // ---- phase 1: scores of every query over one pass of the K stream
+    const int ctx_pad = (ctx + BATCH - 1) / BATCH * BATCH;
+    const uint8_t* kmask = p.key_mask != nullptr ? p.key_mask + (size_t)b * p.mask_stride : nullptr;
+    u32x4 kv[UK];
+    {
+        // 8 queries of 16 elements would take 128 registers beside the rolling window: they are held as operand-format pairs (q is
+        // rounded to that format, so the pair is exact) and widened at use
+        constexpr bool PACKQ = F8 && QM == 8;
+        float qv[PACKQ ? 1 : QM][EPL];
+        uint32_t qp[PACKQ ? QM : 1][EPL / 2];
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            const float* qj = q_s[j < nq ? j : 0] + (lane % LPK) * EPL;
+            if constexpr (PACKQ) {
+#pragma unroll
+                for (int e = 0; e < EPL / 2; ++e) qp[j][e] = pack_bf2(qj[2 * e], qj[2 * e + 1]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) qv[j][e] = qj[e];
+            }
+        }
+        auto qe = [&](int j, int e) {
+            if constexpr (PACKQ) return (e & 1) ? bf2f_hi(qp[j][e >> 1]) : bf2f_lo(qp[j][e >> 1]);
+            else return qv[j][e];
+        };
+        auto dot = [&](const u32x4& r, int j) {
+            float s = 0.f;
+            if constexpr (F8) {
+#pragma unroll
+                for (int w4 = 0; w4 < 4; ++w4) {
+                    const f32x4 f = fp8x4_to_f32x4(r[w4]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) s += qe(j, 4 * w4 + e) * f[e];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s += qe(j, 2 * e) * bf2f_lo(r[e]) + qe(j, 2 * e + 1) * bf2f_hi(r[e]);
+            }
+            return s;
+        };
+#pragma unroll
+        for (int u = 0; u < UK; ++u) kv[u] = ld16_stream(kbase + row_off(wave * KPW * UK + u * KPW + krow));
+        for (int kb = wave * KPW * UK; kb < ctx_pad; kb += BATCH) {
+#pragma unroll
+            for (int u = 0; u < UK; ++u) {
+                const int key = kb + u * KPW + krow;
+                const u32x4 r = kv[u];
+                kv[u] = ld16_stream(kbase + row_off(key + BATCH));
+                const bool open = kmask == nullptr || kmask[min(key, ctx - 1)] != 0;
+#pragma unroll
+                for (int j = 0; j < QM; ++j) {
+                    if (j < nq) {
+                        float s = dot(r, j);
+                        s = lanes_sum<LPK>(s);
+                        if ((lane % LPK) == 0) sc[j * srow + key] = (key <= pos + j && open) ? s * p.scale : -INFINITY;
+                    }
+                }
+            }
+        }
+    }
+    u32x4 vv[UK];
+#pragma unroll
+    for (int u = 0; u < UK; ++u) vv[u] = ld16_stream(vbase + row_off(wave * KPW * UK + u * KPW + krow));
+    __syncthreads();
+    // ---- phase 2: softmax of every query over sc[j][0 .. ctx_pad)
+    float inv[QM];
+    {
+        float mx[QM];
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            mx[j] = -INFINITY;
+            if (j < nq) {
+                for (int i = tid; i < ctx_pad; i += 512) mx[j] = fmaxf(mx[j], sc[j * srow + i]);
+                mx[j] = wave_max(mx[j]);
+                if (lane == 0) red[j][wave] = mx[j];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            if (j < nq) {
+                mx[j] = red[j][0];
+#pragma unroll
+                for (int w = 1; w < 8; ++w) mx[j] = fmaxf(mx[j], red[j][w]);
+            }
+        }
+        __syncthreads();
+        float sum[QM];
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            sum[j] = 0.f;
+            if (j < nq) {
+                for (int i = tid; i < ctx_pad; i += 512) {
+                    const float e = __expf(sc[j * srow + i] - mx[j]);
+                    sc[j * srow + i] = e;
+                    sum[j] += e;
+                }
+                sum[j] = wave_sum(sum[j]);
+                if (lane == 0) red[j][wave] = sum[j];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            inv[j] = 0.f;
+            if (j < nq) {
+                float t = 0.f;
+#pragma unroll
+                for (int w = 0; w < 8; ++w) t += red[j][w];
+                inv[j] = 1.0f / t;
+            }
+        }
+    }
+    // ---- phase 3: one pass of the V stream into nq accumulator sets
+    float acc[QM][EPL];
+#pragma unroll
+    for (int j = 0; j < QM; ++j)
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) acc[j][e] = 0.f;
+    for (int kb = wave * KPW * UK; kb < ctx_pad; kb += BATCH) {
+#pragma unroll
+        for (int u = 0; u < UK; ++u) {
+            const int key = kb + u * KPW + krow;
+            const u32x4 v = vv[u];
+            vv[u] = ld16_stream(vbase + row_off(key + BATCH));
+#pragma unroll
+            for (int j = 0; j < QM; ++j) {
+                if (j < nq) {
+                    const float pk = sc[j * srow + key];
+                    if constexpr (F8) {
+#pragma unroll
+                        for (int w4 = 0; w4 < 4; ++w4) {
+                            const f32x4 f = fp8x4_to_f32x4(v[w4]);
+                            acc[j][4 * w4] = vacc<false>(acc[j][4 * w4], pk, f[0]);
+                            acc[j][4 * w4 + 1] = vacc<false>(acc[j][4 * w4 + 1], pk, f[1]);
+                            if (w4 == 3) {
+                                acc[j][14] = vacc<true>(acc[j][14], pk, f[2]);
+                                acc[j][15] = vacc<true>(acc[j][15], pk, f[3]);
+                            } else {
+                                acc[j][4 * w4 + 2] = vacc<false>(acc[j][4 * w4 + 2], pk, f[2]);
+                                acc[j][4 * w4 + 3] = vacc<false>(acc[j][4 * w4 + 3], pk, f[3]);
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 3; ++e) {
+                            acc[j][2 * e] = vacc<false>(acc[j][2 * e], pk, bf2f_lo(v[e]));
+                            acc[j][2 * e + 1] = vacc<false>(acc[j][2 * e + 1], pk, bf2f_hi(v[e]));
+                        }
+                        acc[j][6] = vacc<true>(acc[j][6], pk, bf2f_lo(v[3]));
+                        acc[j][7] = vacc<true>(acc[j][7], pk, bf2f_hi(v[3]));
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < QM; ++j) {
+        if (j < nq) {   // block-uniform: the barriers below are reached by every thread
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) {
+                float a = acc[j][e];
+#pragma unroll
+                for (int mk = LPK; mk < 64; mk <<= 1) a += shfl_xor(a, mk);
+                acc[j][e] = a;
+            }
+            if (lane < LPK) {
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) part[wave][lane * EPL + e] = acc[j][e];
+            }
+            __syncthreads();
+            if (tid < HD) {
+                float a = 0.f;
+#pragma unroll
+                for (int w = 0; w < 8; ++w) a += part[w][tid];
+                a *= inv[j];
+                p.out[((size_t)b * p.Q + j) * D + h * HD + tid] = f2bf(a);
+            }
+            __syncthreads();   // `part` is free for the next query
+        }
+    }
+}
+
+template <int HD, int UK, bool F8, int QM>
+static void launch_attention_verify_v(const AttnVerifyArgs& a, size_t lds, hipStream_t s) {
+#ifndef VC_EMU
+    static size_t allowed = 0;
+    if (lds > 48 * 1024 && lds > allowed) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_verify_kernel<HD, UK, F8, QM>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        allowed = lds;
+    }
+#endif
+    VC_LAUNCH((attention_verify_kernel<HD, UK, F8, QM>), dim3(a.H, a.B), dim3(512), lds, s, a);
+}
+
+// dynamic + static LDS of one workgroup of the verify attention; a launch needs it <= ATTN_VERIFY_LDS_MAX
+size_t attention_verify_lds_bytes(int Q, int hd, int kv8, int kv_stride) {
+    const int uk = kv8 ? (hd == 128 ? 6 : 4) : 8, epl = kv8 ? 16 : 8;
+    const int batch = 8 * (64 / (hd / epl)) * uk;
+    const int qm = Q <= 4 ? 4 : 8;
+    return (size_t)Q * (kv_stride + batch) * 4 + (size_t)(qm + 8) * hd * 4 + (size_t)qm * 8 * 4;
+}
+
+void launch_attention_verify(const AttnVerifyArgs& a, hipStream_t s) {
+    if (a.Q < 1 || a.Q > 8 || (a.hd != 128 && a.hd != 64)) throw std::runtime_error("attention_verify: Q in 1 .. 8, head dim 128 or 64");
+    if (attention_verify_lds_bytes(a.Q, a.hd, a.kv8, a.kv_stride) > ATTN_VERIFY_LDS_MAX)
+        throw std::runtime_error("attention_verify: the score rows of Q queries over this cache capacity exceed the LDS of a CU");
+    const int uk = a.kv8 ? (a.hd == 128 ? 6 : 4) : 8, epl = a.kv8 ? 16 : 8;
+    const size_t lds = (size_t)a.Q * (a.kv_stride + 8 * (64 / (a.hd / epl)) * uk) * 4;
+    // the rows in flight per lane are the decode kernel's: they are part of the key -> lane map
+    const bool q4 = a.Q <= 4;
+    if (a.kv8) {
+        if (a.hd == 128) q4 ? launch_attention_verify_v<128, 6, true, 4>(a, lds, s) : launch_attention_verify_v<128, 6, true, 8>(a, lds, s);
+        else q4 ? launch_attention_verify_v<64, 4, true, 4>(a, lds, s) : launch_attention_verify_v<64, 4, true, 8>(a, lds, s);
+    } else {
+        if (a.hd == 128) q4 ? launch_attention_verify_v<128, 8, false, 4>(a, lds, s) : launch_attention_verify_v<128, 8, false, 8>(a, lds, s);
+        else q4 ? launch_attention_verify_v<64, 8, false, 4>(a, lds, s) : launch_attention_verify_v<64, 8, false, 8>(a, lds, s);
+    }
+}
+
 }  // namespace vc

@@ -216,18 +216,42 @@ inline bool operator==(const BeamLoop& a, const BeamLoop& b) {
 // vck_set_gemv_variant and vck_set_gemv_wide (the third, vck_set_gemm_force_8phase, concerns the prefill GEMMs only) — and the
 // VC_SPLIT_KV environment switch (read once per process; it shows in es anyway).  A step captured before one of the knobs is turned stays
 // on the kernels it was captured with.
+// A verify step of prompt-lookup speculation (STEP_SPEC) bakes in, beside its view (whose per-step buffers hold B * Q rows) and
+// nrows = B * Q: the draft's token rows, query counts, counters, the lookup / prompt id stores with their strides (the lengths are
+// read on the device), the log-prob scratch with its width, and B, Q, the n-gram size.
+struct SpecLoop {
+    int *tok, *nq, *counters;
+    const int *lookup, *lookup_len, *prompt, *prompt_len;
+    float* s_lp;
+    int* s_ids;
+    int lookup_stride, prompt_stride, s_k, B, Q, ngram;
+};
+inline bool operator==(const SpecLoop& a, const SpecLoop& b) {
+    static_assert(sizeof(SpecLoop) == 96, "SpecLoop changed: compare the new member here");
+    return a.tok == b.tok && a.nq == b.nq && a.counters == b.counters && a.lookup == b.lookup && a.lookup_len == b.lookup_len &&
+           a.prompt == b.prompt && a.prompt_len == b.prompt_len && a.s_lp == b.s_lp && a.s_ids == b.s_ids &&
+           a.lookup_stride == b.lookup_stride && a.prompt_stride == b.prompt_stride && a.s_k == b.s_k && a.B == b.B && a.Q == b.Q &&
+           a.ngram == b.ngram;
+}
 struct StepKey {
     LoopView view;
     int nrows;
     bool has_beam;
     BeamLoop beam;   // zeroes without one
+    SpecLoop spec;   // zeroes without one (Q == 0)
 };
 inline bool operator==(const StepKey& a, const StepKey& b) {
-    static_assert(sizeof(StepKey) == sizeof(LoopView) + 8 + sizeof(BeamLoop), "StepKey changed: compare the new member here");
-    return a.view == b.view && a.nrows == b.nrows && a.has_beam == b.has_beam && a.beam == b.beam;
+    static_assert(sizeof(StepKey) == sizeof(LoopView) + 8 + sizeof(BeamLoop) + sizeof(SpecLoop), "StepKey changed: compare the new member here");
+    return a.view == b.view && a.nrows == b.nrows && a.has_beam == b.has_beam && a.beam == b.beam && a.spec == b.spec;
 }
-// one captured step per kind, so that a plain vc_decode_step behind a log-prob or a beam call replays without a re-capture
-enum StepKind { STEP_PLAIN = 0, STEP_CALL = 1 /* a generate() call's own: log-probs and / or processors */, STEP_BEAM = 2, STEP_KINDS = 3 };
+// one captured step per kind, so that a plain vc_decode_step behind a log-prob, a beam or a speculated call replays without a re-capture
+enum StepKind {
+    STEP_PLAIN = 0,
+    STEP_CALL = 1,   // a generate() call's own: log-probs and / or processors
+    STEP_BEAM = 2,
+    STEP_SPEC = 3,   // the verify step of prompt-lookup speculation
+    STEP_KINDS = 4
+};
 struct StepGraph {
     StepKey key{};
     hipGraphExec_t exec = nullptr;
@@ -332,6 +356,15 @@ struct vc_model {
     int gproc_eos[VC_MAX_EOS_EXTRA] = {};
     std::vector<int> gproc_bad;
     Buf proc_prompt, proc_bad, proc_logits;
+    // prompt-lookup speculation of the NEXT vc_generate* (vc_request_speculation; one-shot): k drafts per step, the largest n-gram,
+    // the caller's lookup ids [B][spec_lookup_stride] with their lengths.  A call that serves it runs verify steps (STEP_SPEC) over
+    // B * (k + 1) rows on the sp_* buffers; spec_counters [B][4] (steps, tokens, drafted, accepted) of the last call when spec_last
+    int spec_k = 0, spec_ngram = 0, spec_B = 0, spec_lookup_stride = 0;
+    std::vector<int> spec_lookup, spec_lookup_len;
+    bool spec_last = false;
+    bool spec_closed = false;     // a speculated call left the rows at different positions: the session's loop is closed
+    std::vector<int> spec_counters;
+    Buf sp_x, sp_xg, sp_qkv, sp_attn, sp_h, sp_logits, sp_ssq, sp_tok, sp_state, sp_lookup, sp_prompt, sp_lp, sp_ids;
     bool tok_stale = false;       // vc_rewind ran: the token the last step selected on the device no longer continues the sequence
     bool plan_only = false;       // do_prefill stops behind the splice plan (vc_plan_spliced_len): no tower pass, no state change
     int reserve_new = 64;         // KV slots a vc_prefill keeps free behind the prompt (vc_model_reserve_decode)
@@ -402,6 +435,11 @@ static void clear_logits_processors_request(vc_model* m) {
     m->gproc = false;
     m->gproc_bad.clear();
 }
+static void clear_speculation_request(vc_model* m) {
+    m->spec_k = m->spec_ngram = m->spec_B = m->spec_lookup_stride = 0;
+    m->spec_lookup.clear();
+    m->spec_lookup_len.clear();
+}
 static void clear_generate_logprobs_request(vc_model* m) {
     m->glp_k = 0;
     m->glp_tok = m->glp_top = nullptr;
@@ -424,6 +462,7 @@ struct OneShotReset {
         clear_score_request(m);
         clear_generate_logprobs_request(m);
         clear_logits_processors_request(m);
+        clear_speculation_request(m);
     }
 };
 

@@ -652,6 +652,54 @@ VC_API int vc_request_generate_logprobs(vc_model* m, int top_k, float* token_log
     return VC_OK;
 }
 
+/* Prompt-lookup speculation of the NEXT vc_generate* call (one-shot): k drafts per verify step from n-gram matches of at most
+ * max_ngram ids in (lookup ids | prompt | generated).  k == 0 cancels.  See include/vcoder_hip.h. */
+VC_API int vc_request_speculation(vc_model* m, int k, int max_ngram, const int32_t* lookup_ids, const int32_t* lookup_lens, int B) {
+    if (!m) return VC_ERR_INVALID;
+    if (k == 0) {
+        clear_speculation_request(m);
+        return VC_OK;
+    }
+    bool ok = k >= 1 && k <= 7 && max_ngram >= 1 && max_ngram <= 4 && (lookup_ids == nullptr) == (lookup_lens == nullptr) &&
+              (lookup_ids == nullptr || (B >= 1 && B <= VC_MAX_ROWS));
+    int stride = 0;
+    for (int b = 0; ok && lookup_ids && b < B; ++b) {
+        ok = lookup_lens[b] >= 0 && lookup_lens[b] <= m->c.max_positions;
+        stride = std::max(stride, (int)lookup_lens[b]);
+    }
+    if (!ok) {
+        m->ctx->err = "vc_request_speculation needs k in 1 .. 7, max_ngram in 1 .. 4 and, with lookup ids, their lengths (0 .. "
+                      "max_position_embeddings each) for 1 .. 16 sequences";
+        return VC_ERR_INVALID;   // (a pending request stays as it was: nothing touched)
+    }
+    clear_speculation_request(m);
+    m->spec_k = k;
+    m->spec_ngram = max_ngram;
+    if (lookup_ids) {   // ragged in, [B][longest] here
+        m->spec_B = B;
+        m->spec_lookup_stride = stride;
+        m->spec_lookup.assign((size_t)B * std::max(stride, 1), 0);
+        m->spec_lookup_len.assign(lookup_lens, lookup_lens + B);
+        size_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            std::copy(lookup_ids + off, lookup_ids + off + lookup_lens[b], m->spec_lookup.begin() + (size_t)b * std::max(stride, 1));
+            off += lookup_lens[b];
+        }
+    }
+    return VC_OK;
+}
+/* the counters of the last vc_generate* call if it speculated: out [B][4] = steps, tokens emitted, drafts proposed, drafts accepted per
+ * sequence; VC_OK, or VC_ERR_STATE ("not speculated") */
+VC_API int vc_last_speculation(vc_model* m, int32_t* out, int B) {
+    if (!m || !out) return VC_ERR_INVALID;
+    if (!m->spec_last || (size_t)B * 4 != m->spec_counters.size()) {
+        m->ctx->err = "the last generate call of this session was not speculated";
+        return VC_ERR_STATE;
+    }
+    std::copy(m->spec_counters.begin(), m->spec_counters.end(), out);
+    return VC_OK;
+}
+
 /* Logits processors of the NEXT vc_generate* call (one-shot): repetition penalty, no-repeat n-gram, bad words, minimum new tokens,
  * applied on the device in front of every selection.  p == NULL cancels.  See include/vcoder_hip.h. */
 VC_API int vc_request_logits_processors(vc_model* m, const vc_logits_processors* p) {
@@ -870,6 +918,8 @@ VC_API int vc_rewind(vc_model* m, int P) {
 
 // one cached step of the session's loop (vc_decode_step; vc_extend in precision modes "strict" / "split")
 void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* next_tok) {
+    REQUIRE(!(m->cur_pos < 0 && m->spec_closed), VC_ERR_STATE,
+            "vc_decode_step behind a speculated generate: its rows stand at different positions (prefill again)");
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_decode_step before vc_prefill");
     REQUIRE(tok || !m->tok_stale, VC_ERR_STATE,
             "vc_decode_step(tok = NULL) after vc_rewind: the token selected on the device belongs to the rows that were dropped");
@@ -938,6 +988,8 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
     USE_DEVICE(m->ctx);
     const vc_model_cfg& c = m->c;
     // every check before anything is enqueued: a refused call leaves the cache and the loop's state as they were
+    REQUIRE(!(m->cur_pos < 0 && m->spec_closed), VC_ERR_STATE,
+            "vc_extend behind a speculated generate: its rows stand at different positions (prefill again)");
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_extend before vc_prefill");
     REQUIRE(tok && n >= 1, VC_ERR_INVALID, "vc_extend needs n >= 1 tokens per row");
     REQUIRE(B == m->curB, VC_ERR_INVALID, "vc_extend: %d rows given, the session's loop has %d", B, m->curB);

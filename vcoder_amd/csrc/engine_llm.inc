@@ -772,6 +772,113 @@ hipGraphExec_t step_graph(vc_model* m, StepKind kind, const LoopView& view, int 
     return s.exec;
 }
 
+// ---- prompt-lookup speculation: the verify step (STEP_SPEC) ---------------------------------------------------------------------
+// device words of sp_state: query counts | counters | prompt lengths | lookup lengths, VC_MAX_ROWS sequences each
+constexpr int SPEC_STATE_INTS = VC_MAX_ROWS * (1 + 4 + 1 + 1);
+constexpr int SPEC_MAX_ROWS = VC_GEMV_MAX_M;   // B * (k + 1) rows ride one weight pass
+// the buffers of a speculated call of B sequences, Q rows each: the per-step buffers of R = B * Q rows, the id stores (strides
+// max_positions: no call's lengths are baked into the step), the log-prob scratch of the widest K
+void ensure_spec(vc_model* m, int R) {
+    const vc_model_cfg& c = m->c;
+    const size_t Rp = rup(R, 16), D = c.hidden;
+    m->sp_x.ensure(Rp * D * 4, true);
+    m->sp_xg.ensure(Rp * D * 2, true);
+    m->sp_qkv.ensure(Rp * 3 * D * 2, true);
+    m->sp_attn.ensure(Rp * D * 2, true);
+    m->sp_h.ensure(Rp * c.ffn * 2, true);
+    m->sp_logits.ensure(Rp * c.vocab * 4, true);
+    m->sp_ssq.ensure(Rp * m->npart * 4, true);
+    m->sp_tok.ensure((size_t)SPEC_MAX_ROWS * 4, true);
+    m->sp_state.ensure((size_t)SPEC_STATE_INTS * 4, true);
+    m->sp_lookup.ensure((size_t)VC_MAX_ROWS * c.max_positions * 4);
+    m->sp_prompt.ensure((size_t)VC_MAX_ROWS * c.max_positions * 4);
+    m->sp_lp.ensure((size_t)SPEC_MAX_ROWS * VC_MAX_TOP_LOGPROBS * 4);
+    m->sp_ids.ensure((size_t)SPEC_MAX_ROWS * VC_MAX_TOP_LOGPROBS * 4);
+}
+SpecLoop spec_view(vc_model* m, int B, int Q, int ngram, bool lookup, int lp_k) {
+    SpecLoop sl{};
+    int* st = m->sp_state.as<int>();
+    sl.tok = m->sp_tok.as<int>();
+    sl.nq = st;
+    sl.counters = st + VC_MAX_ROWS;
+    sl.prompt_len = st + 5 * VC_MAX_ROWS;
+    sl.prompt = m->sp_prompt.as<int>();
+    sl.prompt_stride = m->c.max_positions;
+    if (lookup) {
+        sl.lookup = m->sp_lookup.as<int>();
+        sl.lookup_len = st + 6 * VC_MAX_ROWS;
+        sl.lookup_stride = m->c.max_positions;
+    }
+    if (lp_k >= 0) {   // a call with log-probs: entry 0 of a scratch row is the row's argmax
+        sl.s_lp = m->sp_lp.as<float>();
+        sl.s_ids = m->sp_ids.as<int>();
+        sl.s_k = std::max(lp_k, 1);
+    }
+    sl.B = B;
+    sl.Q = Q;
+    sl.ngram = ngram;
+    return sl;
+}
+// the per-step buffers of a view replaced by the B * Q row ones (the caches, records, next_tok, out_ids and slabs stay)
+LoopView spec_loop_view(vc_model* m, const LoopView& call) {
+    LoopView v = call;
+    v.x_dec = m->sp_x.as<float>();
+    v.xg_dec = m->sp_xg.as<bf16_t>();
+    v.qkv_dec = m->sp_qkv.as<bf16_t>();
+    v.attn_dec = m->sp_attn.as<bf16_t>();
+    v.h_dec = m->sp_h.as<bf16_t>();
+    v.logits = m->sp_logits.as<float>();
+    v.ssq = m->sp_ssq.as<float>();
+    return v;
+}
+// draft + embedding of the B * Q token rows -> the linears with the verify attention between -> (log-probs of every row) -> accept
+void enqueue_spec_step(vc_model* m, const LoopView& v, const SpecLoop& sl) {
+    const vc_model_cfg& c = m->c;
+    const int R = sl.B * sl.Q;
+    SpecDraftArgs da{v.rows, v.out_ids, sl.lookup, sl.lookup_len, sl.lookup_stride, sl.prompt, sl.prompt_len, sl.prompt_stride,
+                     sl.tok, sl.nq, sl.B, sl.Q, sl.Q - 1, sl.ngram, c.vocab};
+    launch_spec_draft(da, v.st);
+    launch_embed_tokens_ssq(sl.tok, m->embed, v.x_dec, v.ssq, m->llm[0].in_norm, v.xg_dec, R, c.hidden, m->npart, v.st);
+    const KvTarget kv = loop_kv(v);
+    decode_linears(m, v, R, [&](int l) {
+        AttnVerifyArgs va{v.qkv_dec, kcache(m, kv, l), vcache(m, kv, l), v.attn_dec, sl.B, c.heads, m->hd, v.capS, sl.Q,
+                          v.rows + RS_POS, RS_STRIDE, sl.nq, m->rope_cos, m->rope_sin, 1.0f / sqrtf((float)m->hd), v.es == 1 ? 3 : 0,
+                          v.kmask, v.kmask_stride};
+        launch_attention_verify(va, v.st);
+    });
+    if (v.lp_tok) {
+        TopkLogprobArgs ta{v.logits, c.vocab, nullptr, nullptr, sl.s_lp, sl.s_ids, c.vocab, sl.s_k, nullptr, nullptr, 0};
+        launch_topk_logprob(ta, R, -1, v.st);
+    }
+    SpecAcceptArgs aa{v.logits, c.vocab, c.vocab, v.rows, v.next_tok, v.out_ids, sl.tok, sl.nq, sl.B, sl.Q, sl.counters,
+                      v.lp_tok ? sl.s_lp : nullptr, v.lp_tok ? sl.s_ids : nullptr, sl.s_k, v.lp_tok, v.lp_top, v.lp_ids, v.lp_k};
+    launch_spec_accept(aa, v.st);
+}
+// the session's captured verify step for this view and loop: replayed while both equal what it was captured from
+hipGraphExec_t spec_step_graph(vc_model* m, const LoopView& view, const SpecLoop& sl) {
+    StepGraph& s = m->step[STEP_SPEC];
+    StepKey key{view, sl.B * sl.Q, false, BeamLoop{}, sl};
+    if (s.exec && s.key == key) return s.exec;
+    if (s.exec) {
+        (void)hipGraphExecDestroy(s.exec);
+        s.exec = nullptr;
+    }
+    hipGraph_t g = nullptr;
+    HIPCHK(hipStreamBeginCapture(view.st, hipStreamCaptureModeThreadLocal));
+    try {
+        enqueue_spec_step(m, view, sl);
+    } catch (...) {
+        (void)hipStreamEndCapture(view.st, &g);
+        throw;
+    }
+    HIPCHK(hipStreamEndCapture(view.st, &g));
+    HIPCHK(hipGraphInstantiate(&s.exec, g, nullptr, nullptr, 0));
+    HIPCHK(hipGraphDestroy(g));
+    s.key = key;
+    m->step_captures += 1;
+    return s.exec;
+}
+
 void ensure_out_ids(vc_model* m, int B, int max_new) {
     const int stride = std::max(max_new, 1);
     if (stride > m->out_stride || m->out_ids.cap < (size_t)rup(B, 16) * stride * 4) {
@@ -1236,6 +1343,7 @@ void arm_session_rows(vc_model* m, const GenParams& g, const int* tail) {
     HIPCHK(hipMemcpyAsync(m->rows.p, rec.data(), rec.size() * 4, hipMemcpyHostToDevice, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
     m->cur_pos = S;
+    m->spec_closed = false;
     m->tok_stale = false;
 }
 

@@ -598,13 +598,26 @@ std::unique_lock<std::mutex> prefill_on_session(vc_model* m, const int64_t* ids,
     return gate;
 }
 
-// generate() on the session's own loop: prefill, then max_new - 1 graph-replayed (strict: eagerly enqueued) decode steps
+// whether the pending vc_request_speculation is served by a call of this form (the LDS bound of the verify attention is known
+// behind the prefill only): greedy, no processors, the bf16 step, B * (k + 1) rows in one weight pass
+bool spec_request_served(const vc_model* m, const GenParams& g, int B) {
+    return m->spec_k > 0 && !g.do_sample && !g.proc && m->precision == 0 && B * (m->spec_k + 1) <= SPEC_MAX_ROWS;
+}
+
+// generate() on the session's own loop: prefill, then max_new - 1 graph-replayed (strict: eagerly enqueued) decode steps — or, with a
+// served speculation request, verify steps until every row is finished or full
 void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
                          int on_dev, const GenParams& g, const std::vector<int>& tail, vc_token_cb cb, void* cb_user,
                          int cb_every, int32_t* out_ids, int* n_generated) {
     const int max_new = g.max_new;
+    m->spec_closed = false;
     std::unique_lock<std::mutex> gate = prefill_on_session(m, ids, B, T, img, seg, depth, on_dev, max_new);
     ensure_out_ids(m, B, max_new);
+    // vc_request_speculation: served when the call's form allows (spec_request_served) and the score rows of Q queries over this
+    // cache fit a CU's LDS.  (A row drafts no further than its last slot, so the prefill's reserve of max_new positions holds.)
+    const int Q = spec_request_served(m, g, B) ? m->spec_k + 1 : 0;
+    const bool spec = Q > 0 && (m->hd == 128 || m->hd == 64) && (m->kv_es == 2 || m->kv_es == 1) &&
+                      attention_verify_lds_bytes(Q, m->hd, m->kv_es == 1, m->capS) <= ATTN_VERIFY_LDS_MAX;
     // the steps of this call: the session's plain view, plus what the call asked for — the view goes to the step-0 selection, to the
     // captured step (STEP_CALL with either request, else the plain one) and, in strict mode, to the eager step
     LoopView v = session_view(m);
@@ -665,7 +678,62 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     };
     const int every = cb ? std::max(cb_every, 1) : 8;
     if (cb && every == 1) report(1);
-    if (max_new > 1 && !all_finished()) {
+    if (spec) {
+        // the verify loop: every replay emits 1 .. Q tokens per row, so a row's progress is its record's, not the host's step count
+        ensure_spec(m, B * Q);
+        const int ld = m->c.max_positions;
+        const bool lookup = !m->spec_lookup.empty();
+        std::vector<int> ids32((size_t)B * T), st(SPEC_STATE_INTS, 0);
+        for (size_t i = 0; i < ids32.size(); ++i) ids32[i] = (int)std::max<int64_t>(std::min<int64_t>(ids[i], INT32_MAX), INT32_MIN);
+        for (int b = 0; b < B; ++b) {
+            st[5 * VC_MAX_ROWS + b] = T;
+            st[6 * VC_MAX_ROWS + b] = lookup ? m->spec_lookup_len[b] : 0;
+        }
+        REQUIRE(T <= ld, VC_ERR_INVALID, "prompt of %d ids exceeds max_position_embeddings=%d", T, ld);
+        HIPCHK(hipMemcpy2DAsync(m->sp_prompt.p, (size_t)ld * 4, ids32.data(), (size_t)T * 4, (size_t)T * 4, B, hipMemcpyHostToDevice, m->st));
+        if (lookup && m->spec_lookup_stride > 0)
+            HIPCHK(hipMemcpy2DAsync(m->sp_lookup.p, (size_t)ld * 4, m->spec_lookup.data(), (size_t)m->spec_lookup_stride * 4,
+                                    (size_t)m->spec_lookup_stride * 4, B, hipMemcpyHostToDevice, m->st));
+        HIPCHK(hipMemcpyAsync(m->sp_state.p, st.data(), st.size() * 4, hipMemcpyHostToDevice, m->st));
+        HIPCHK(hipStreamSynchronize(m->st));   // the host vectors
+        const SpecLoop sl = spec_view(m, B, Q, m->spec_ngram, lookup, want_lp ? K : -1);
+        const LoopView sv = spec_loop_view(m, v);
+        // -> every row finished or full; least tokens an unfinished row still has to emit; least step over the unfinished rows
+        int left = 0, low = 0;
+        auto poll = [&]() {
+            HIPCHK(hipMemcpyAsync(rec.data(), m->rows.p, rec.size() * 4, hipMemcpyDeviceToHost, m->st));
+            HIPCHK(hipStreamSynchronize(m->st));
+            left = 0;
+            low = max_new;
+            produced = 0;
+            for (int b = 0; b < B; ++b) {
+                const int* r = rec.data() + (size_t)b * RS_STRIDE;
+                produced = std::max(produced, std::min(r[RS_STEP], max_new));
+                if (r[RS_FINISHED] || r[RS_STEP] >= max_new) continue;
+                left = std::max(left, max_new - r[RS_STEP]);
+                low = std::min(low, r[RS_STEP]);
+            }
+            return left == 0;
+        };
+        if (max_new > 1 && !poll()) {
+            const hipGraphExec_t exec = spec_step_graph(m, sv, sl);
+            do {
+                // that many steps are needed whatever is accepted; a row that may finish early, or a streamer, is looked at sooner
+                int n = std::max(1, (left + Q - 1) / Q);
+                if (can_finish || cb) n = std::min(n, every);
+                for (int i = 0; i < n; ++i) HIPCHK(hipGraphLaunch(exec, m->st));
+                const bool done = poll();
+                if (cb) report(done ? produced : low);
+                if (done) break;
+            } while (true);
+        }
+        m->spec_counters.assign((size_t)B * 4, 0);
+        HIPCHK(hipMemcpyAsync(m->spec_counters.data(), sl.counters, (size_t)B * 16, hipMemcpyDeviceToHost, m->st));
+        HIPCHK(hipStreamSynchronize(m->st));
+        m->spec_last = true;
+        m->cur_pos = -1;       // the rows stand at different positions: the session's loop is closed
+        m->spec_closed = true;
+    } else if (max_new > 1 && !all_finished()) {
         const hipGraphExec_t exec = m->precision != 1 ? step_graph(m, want_lp || g.proc ? STEP_CALL : STEP_PLAIN, v, B) : nullptr;
         for (int step = 1; step < max_new; ++step) {
             if (m->precision == 1) enqueue_decode_step_strict(m, v, B);
@@ -989,7 +1057,11 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
         for (int e = 0; e < m->gproc_neos; ++e) g.proc_eos[e] = m->gproc_eos[e];
         g.proc_T = T;
     }
-    if (use_pool && m->precision != 1 && !m->glp_tok && !g.proc)
+    // vc_request_speculation: a served request runs on the session's own loop (the pool's steps are plain ones)
+    REQUIRE(m->spec_k == 0 || m->spec_lookup.empty() || m->spec_B == B, VC_ERR_INVALID, "lookup ids given for %d sequences, batch is %d",
+            m->spec_B, B);
+    m->spec_last = false;
+    if (use_pool && m->precision != 1 && !m->glp_tok && !g.proc && !spec_request_served(m, g, B))
         generate_on_pool(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids, n_generated);
     else
         generate_on_session(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids,
@@ -1019,6 +1091,7 @@ VC_API int vc_generate_beam(vc_model* m, const int64_t* ids, int B, int T, const
     REQUIRE(m->precision != 1, VC_ERR_STATE, "strict mode keeps beam search on the host loop (vc_decode_step + vc_reorder_cache)");
     REQUIRE(!m->glp_tok, VC_ERR_STATE, "per-token log-probs are not implemented for beam search: a vc_request_generate_logprobs is pending");
     REQUIRE(!m->gproc, VC_ERR_STATE, "logits processors are not implemented in the device beam loop: a vc_request_logits_processors is pending");
+    m->spec_last = false;   // (a pending vc_request_speculation is not served by beam search)
     {   // the tail permute moves 16-byte chunks of a cache row: the element size the prefill below will give the session's cache
         const int es = m->precision == 2 ? split_kv_es() : step_kv_es(m);
         REQUIRE((m->hd * es) % 16 == 0, VC_ERR_STATE, "the tail permute moves 16-byte chunks: head_dim %d x %d bytes", m->hd, es);

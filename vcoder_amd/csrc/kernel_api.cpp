@@ -77,11 +77,32 @@ VCK_EXPORT void vck_attention_decode_rows(const uint16_t* qkv, uint16_t* k, uint
     AttnDecodeFusedArgs a{qkv, k, v, out, B, H, hd, kv_stride, pos_rows, rope_cos, rope_sin, scale, pos_stride, active_rows};
     launch_attention_decode_fused(a, S(stream));
 }
+VCK_EXPORT int vck_attention_verify(const uint16_t* qkv, void* k, void* v, uint16_t* out, int B, int H, int hd, int kv_stride, int Q,
+                                    const int* pos_rows, int pos_stride, const int* nq, const float* rope_cos, const float* rope_sin,
+                                    float scale, int kv8, const uint8_t* key_mask, int mask_stride, void* stream) {
+    if (Q < 1 || Q > 8 || (hd != 128 && hd != 64) || attention_verify_lds_bytes(Q, hd, kv8, kv_stride) > ATTN_VERIFY_LDS_MAX) return -1;
+    AttnVerifyArgs a{qkv, k, v, out, B, H, hd, kv_stride, Q, pos_rows, pos_stride, nq, rope_cos, rope_sin, scale, kv8, key_mask, mask_stride};
+    launch_attention_verify(a, S(stream));
+    return 0;
+}
 VCK_EXPORT void vck_select_embed(const float* logits, int ldl, int* rows, int* next_tok, int* out_ids, const uint16_t* embed,
                                  float* x, float* ssq, const float* xg_w, uint16_t* xg, int D, int npart, int V, int nrows,
                                  int advance, void* stream) {
     SelectArgs a{logits, ldl, rows, next_tok, out_ids, embed, x, ssq, xg_w, xg, D, npart, V, nrows, advance, 0, 0};
     launch_select_embed(a, S(stream));
+}
+VCK_EXPORT void vck_spec_draft(const int* rows, const int* out_ids, const int* lookup, const int* lookup_len, int lookup_stride,
+                               const int* prompt, const int* prompt_len, int prompt_stride, int* tok, int* nq, int B, int Q, int k,
+                               int max_ngram, int V, void* stream) {
+    SpecDraftArgs a{rows, out_ids, lookup, lookup_len, lookup_stride, prompt, prompt_len, prompt_stride, tok, nq, B, Q, k, max_ngram, V};
+    launch_spec_draft(a, S(stream));
+}
+VCK_EXPORT void vck_spec_accept(const float* logits, int ldl, int V, int* rows, int* next_tok, int* out_ids, const int* tok, const int* nq,
+                                int B, int Q, int* counters, const float* scratch_lp, const int* scratch_ids, int scratch_k, float* lp_tok,
+                                float* lp_top, int* lp_ids, int lp_k, void* stream) {
+    SpecAcceptArgs a{logits, ldl, V, rows, next_tok, out_ids, tok, nq, B, Q, counters, scratch_lp, scratch_ids, scratch_k, lp_tok, lp_top,
+                     lp_ids, lp_k};
+    launch_spec_accept(a, S(stream));
 }
 VCK_EXPORT int vck_row_state_stride() { return RS_STRIDE; }
 VCK_EXPORT void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, void* stream) {

@@ -330,6 +330,33 @@ struct AttnDecodeFusedArgs {
 };
 void launch_attention_decode_fused(const AttnDecodeFusedArgs& a, hipStream_t s);
 
+// verify attention (speculative decoding): nq_dev[b] <= Q <= 8 consecutive query rows of sequence b — activation rows b * Q + j at
+// positions pos_dev[b * pos_stride] + j — roped, appended to the cache and attended in ONE launch that reads the K and the V stream
+// once.  Row j's output and the appended cache rows are the bits launch_attention_decode_fused gives that row in a step of its own
+// (attn.hip attention_verify_kernel; an exactly-zero output may differ in sign).  nq_dev[b] <= 0 skips the sequence; the queries are
+// cut at the cache capacity.  bf16 (kv8 == 0) and e4m3 (kv8 != 0) caches, head dims 128 and 64.
+struct AttnVerifyArgs {
+    const bf16_t* qkv;   // [B * Q, 3*H*hd]
+    void* k;             // [B,H,kv_stride,hd]   (rows pos .. pos + nq - 1 are written)
+    void* v;
+    bf16_t* out;         // [B * Q, H*hd]
+    int B, H, hd, kv_stride, Q;
+    const int* pos_dev;  // sequence b reads pos_dev[b * pos_stride]
+    int pos_stride;
+    const int* nq_dev;   // [B]
+    const float* rope_cos;
+    const float* rope_sin;
+    float scale;
+    int kv8;
+    const uint8_t* key_mask;   // key_mask[b * mask_stride + key] == 0 hides the key (nullptr = none)
+    int mask_stride;
+};
+// LDS of one workgroup (Q score rows of kv_stride + one round of the key stream, the queries, the cross-wave buffer); a launch whose
+// need exceeds ATTN_VERIFY_LDS_MAX (the 160 KiB of a CU) is refused — callers ask first
+constexpr size_t ATTN_VERIFY_LDS_MAX = 160 * 1024;
+size_t attention_verify_lds_bytes(int Q, int hd, int kv8, int kv_stride);
+void launch_attention_verify(const AttnVerifyArgs& a, hipStream_t s);
+
 // ---- splice / embedding (K10) ------------------------------------------------------------------
 // per destination row r of inputs_embeds [B*S, D]: row_src[2r] = kind (0 = token id -> embed_tokens row,
 // 1 = row of the projected feature buffer, 2 = zero padding row), row_src[2r+1] = token id / feature row.
@@ -426,6 +453,43 @@ void launch_stamp_accumulate(unsigned* stamps, int n, int layers, unsigned long 
 // embedding + sum-of-squares partials for tokens supplied by the host (vc_decode_step with explicit tokens)
 void launch_embed_tokens_ssq(const int* tok, const bf16_t* embed, float* x, float* ssq, const float* xg_w, bf16_t* xg, int B, int D, int npart,
                              hipStream_t s, int xg_G = 0, const bf16_t* embed_lo = nullptr);
+// ---- prompt-lookup speculation (select.hip spec_draft_kernel / spec_accept_kernel): a verify step runs Q = k + 1 token rows per
+// sequence (rows b * Q + j) through the linears; the draft kernel fills them in front of the embedding, the accept kernel reads the
+// lm_head's B * Q logits rows.  One workgroup per sequence; sequence b's record is rows[b].
+struct SpecDraftArgs {
+    const int* rows;         // [B][RS_STRIDE]
+    const int* out_ids;      // base of the id store (RS_OUT_OFF, RS_STEP ids generated so far)
+    const int* lookup;       // [B][lookup_stride] the caller's lookup ids, or nullptr
+    const int* lookup_len;   // [B] (lookup != nullptr)
+    int lookup_stride;
+    const int* prompt;       // [B][prompt_stride] the prompt ids as int32, placeholders and all
+    const int* prompt_len;   // [B], or nullptr: prompt_stride ids each
+    int prompt_stride;
+    int* tok;                // [B * Q] out: the step's token rows — last emitted id, the drafts, pad
+    int* nq;                 // [B] out: 1 + drafts; 0 for a row that is inactive, finished or full
+    int B, Q, k, max_ngram, V;
+};
+void launch_spec_draft(const SpecDraftArgs& a, hipStream_t s);
+struct SpecAcceptArgs {
+    const float* logits;     // [B * Q, ldl]
+    int ldl, V;
+    int* rows;
+    int* next_tok;           // [B] out: the last emitted id
+    int* out_ids;
+    const int* tok;          // [B * Q] the draft kernel's token rows
+    const int* nq;           // [B]
+    int B, Q;
+    int* counters;           // [B][4] += {steps, tokens emitted, drafts proposed, drafts emitted}, or nullptr
+    // log-probs: the scratch a launch_topk_logprob over the B * Q rows filled ([B * Q, scratch_k], scratch_k >= max(lp_k, 1)) and the
+    // call's slabs (TopkLogprobArgs with rows); lp_tok == nullptr: none
+    const float* scratch_lp;
+    const int* scratch_ids;
+    int scratch_k;
+    float *lp_tok, *lp_top;
+    int* lp_ids;
+    int lp_k;
+};
+void launch_spec_accept(const SpecAcceptArgs& a, hipStream_t s);
 void launch_advance(int* step_dev, int* pos_dev, int* ctx_dev, hipStream_t s);
 // scoring: logprob[r] = logits[r, target[r]] - logsumexp(logits[r, 0:V]) for `rows` rows of stride ldl floats (ldl >= V; any V, any
 // alignment), one workgroup per row, fp32 throughout (select.hip)

@@ -125,6 +125,40 @@ VC_DEV void embed_row_ssq(const bf16_t* sp, float* dp, float* ssq_row, const flo
     for (int q = lane; q < npart; q += 64) ssq_row[q] = q == 0 ? ss : 0.f;
 }
 
+// The bookkeeping ONE selected token `sel` goes through at step `step` of its row: pad behind a finished row, EOS, the row's slot
+// of the id store (`out`, RS_MAXNEW entries), the stop sequences as suffixes of (prompt tail | generated so far | the token).  -> the
+// token the row emits.  The plain selection applies it to its one token, spec_accept_kernel to every token of an accepted run.
+VC_DEV int emit_token(int* rs, int* out, int step, int sel) {
+    const int eos = rs[RS_EOS], pad = rs[RS_PAD], nstop = rs[RS_NSTOP], max_new = rs[RS_MAXNEW];
+    const bool can_finish = eos >= 0 || nstop > 0;
+    const int was_finished = can_finish ? rs[RS_FINISHED] : 0;
+    int tok = sel;
+    if (can_finish) {
+        if (was_finished) tok = pad;
+        if (eos >= 0 && tok == eos) rs[RS_FINISHED] = 1;
+    }
+    if (step < max_new) out[step] = tok;
+    if (nstop > 0 && !was_finished) {  // suffix match of the row's ids (prompt tail | generated so far | tok)
+        bool hit = false;
+        for (int sq = 0; sq < nstop; ++sq) {
+            const int* e = rs + RS_STOP + sq * (1 + VC_MAX_STOP_LEN);
+            const int L = e[0];
+            bool ok = L > 0;
+            for (int i = 0; i < L && ok; ++i) {
+                const int back = L - 1 - i;  // 0 = the token just selected
+                int v;
+                if (back == 0) v = tok;
+                else if (step - back >= 0) v = out[step - back];
+                else v = rs[RS_TAIL + (VC_MAX_STOP_LEN - 1) + (step - back)];
+                ok = v == e[1 + i];
+            }
+            hit = hit || ok;
+        }
+        if (hit) rs[RS_FINISHED] = 1;
+    }
+    return tok;
+}
+
 __global__ __launch_bounds__(1024) void select_embed_kernel(SelectArgs p) {
     VC_DYNAMIC_SMEM(float, zs);  // [V] scaled logits of the row (sampling only)
     __shared__ BlockRed red;
@@ -211,35 +245,8 @@ __global__ __launch_bounds__(1024) void select_embed_kernel(SelectArgs p) {
     }
     // ---- bookkeeping (one lane) ----------------------------------------------------------------------------------
     if (tid == 0) {
-        const int eos = rs[RS_EOS], pad = rs[RS_PAD], nstop = rs[RS_NSTOP], max_new = rs[RS_MAXNEW];
-        const bool can_finish = eos >= 0 || nstop > 0;
-        const int was_finished = can_finish ? rs[RS_FINISHED] : 0;
-        int tok = bi;
-        if (can_finish) {
-            if (was_finished) tok = pad;
-            if (eos >= 0 && tok == eos) rs[RS_FINISHED] = 1;
-        }
+        const int tok = emit_token(rs, p.out_ids + rs[RS_OUT_OFF], step, bi);
         p.next_tok[r] = tok;
-        int* out = p.out_ids + rs[RS_OUT_OFF];
-        if (step < max_new) out[step] = tok;
-        if (nstop > 0 && !was_finished) {  // suffix match of the row's ids (prompt tail | generated so far | tok)
-            bool hit = false;
-            for (int sq = 0; sq < nstop; ++sq) {
-                const int* e = rs + RS_STOP + sq * (1 + VC_MAX_STOP_LEN);
-                const int L = e[0];
-                bool ok = L > 0;
-                for (int i = 0; i < L && ok; ++i) {
-                    const int back = L - 1 - i;  // 0 = the token just selected
-                    int v;
-                    if (back == 0) v = tok;
-                    else if (step - back >= 0) v = out[step - back];
-                    else v = rs[RS_TAIL + (VC_MAX_STOP_LEN - 1) + (step - back)];
-                    ok = v == e[1 + i];
-                }
-                hit = hit || ok;
-            }
-            if (hit) rs[RS_FINISHED] = 1;
-        }
         tok_s = tok;
         if (p.advance & 1) rs[RS_STEP] = step + 1;
         if (p.advance & 2) rs[RS_POS] += 1;
@@ -866,6 +873,134 @@ __global__ __launch_bounds__(256) void embed_tokens_ssq_kernel(const int* tok, c
 void launch_embed_tokens_ssq(const int* tok, const bf16_t* embed, float* x, float* ssq, const float* xg_w, bf16_t* xg, int B,
                              int D, int npart, hipStream_t s, int xg_G, const bf16_t* embed_lo) {
     VC_LAUNCH(embed_tokens_ssq_kernel, dim3((B + 3) / 4), dim3(256), 0, s, tok, embed, x, ssq, xg_w, xg, B, D, npart, xg_G, embed_lo);
+}
+
+// ---- prompt-lookup speculation: the draft in front of a verify step, the acceptance behind its lm_head ---------------------------
+// The corpus of sequence b: its lookup ids | a separator no window may touch | its prompt ids | the ids it has generated.  For
+// ng = max_ngram .. 1 (an ng longer than prompt + generated is not tried) the last ng ids are sought at every earlier start; the
+// latest match of the first ng that has one decides, and the ids behind it are the drafts: at most k, cut at the corpus end and at the
+// first id that is no vocabulary id (the separator, a placeholder of the prompt).  One workgroup per sequence: every thread tries the
+// starts tid, tid + 256, ..., the largest matching start wins.
+constexpr int SPEC_DRAFT_THREADS = 256;
+__global__ __launch_bounds__(SPEC_DRAFT_THREADS) void spec_draft_kernel(SpecDraftArgs p) {
+    __shared__ int best;
+    const int b = blockIdx.x, tid = threadIdx.x, Q = p.Q;
+    const int* rs = p.rows + (size_t)b * RS_STRIDE;
+    const int step = rs[RS_STEP], max_new = rs[RS_MAXNEW];
+    int* tok = p.tok + (size_t)b * Q;
+    const int pad = (rs[RS_PAD] >= 0 && rs[RS_PAD] < p.V) ? rs[RS_PAD] : 0;
+    const bool live = rs[RS_ACTIVE] && !rs[RS_FINISHED] && step >= 1 && step < max_new;
+    if (!live) {   // a finished or full row: no queries; its token rows embed pad so that everything stays finite
+        if (tid < Q) tok[tid] = pad;
+        if (tid == 0) p.nq[b] = 0;
+        return;
+    }
+    const int L = p.lookup != nullptr ? p.lookup_len[b] : 0, T = p.prompt_len != nullptr ? p.prompt_len[b] : p.prompt_stride;
+    const int* lk = p.lookup != nullptr ? p.lookup + (size_t)b * p.lookup_stride : nullptr;
+    const int* pr = p.prompt + (size_t)b * p.prompt_stride;
+    const int* out = p.out_ids + rs[RS_OUT_OFF];
+    const int N = L + 1 + T + step;
+    // corpus entry i (i != L: the separator is never read — windows that would cover it are not compared)
+    auto at = [&](int i) { return i < L ? lk[i] : (i < L + 1 + T ? pr[i - L - 1] : out[i - L - 1 - T]); };
+    int start = -1, ngram = 0;
+    for (int ng = min(p.max_ngram, T + step); ng >= 1 && start < 0; --ng) {
+        if (tid == 0) best = -1;
+        __syncthreads();
+        int mine = -1;
+        for (int s = tid; s < N - ng; s += SPEC_DRAFT_THREADS) {
+            if (s <= L && s + ng > L) continue;   // the window would cover the separator
+            bool ok = true;
+            for (int i = 0; i < ng && ok; ++i) ok = at(s + i) == at(N - ng + i);
+            if (ok) mine = s;
+        }
+        if (mine >= 0) {
+#ifdef VC_EMU
+            __atomic_fetch_max(&best, mine, __ATOMIC_RELAXED);
+#else
+            atomicMax(&best, mine);
+#endif
+        }
+        __syncthreads();
+        start = best;
+        ngram = ng;
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const int room = min(min(p.k, Q - 1), max_new - step - 1);   // a row with one token left drafts nothing
+    int n = 0;
+    tok[0] = out[step - 1];   // the last emitted id
+    if (start >= 0) {
+        for (int i = start + ngram; n < room && i < N && i != L; ++i) {
+            const int d = at(i);
+            if (d < 0 || d >= p.V) break;
+            tok[1 + n++] = d;
+        }
+    }
+    for (int j = 1 + n; j < Q; ++j) tok[j] = pad;
+    p.nq[b] = 1 + n;
+}
+void launch_spec_draft(const SpecDraftArgs& a, hipStream_t s) {
+    VC_LAUNCH(spec_draft_kernel, dim3((unsigned)a.B), dim3(SPEC_DRAFT_THREADS), 0, s, a);
+}
+
+// Behind the lm_head over the B * Q rows: a_j = greedy argmax of row j (ties to the lower id, as select_embed_kernel); n = the leading
+// drafts d_j == a_(j-1); a_0 .. a_n go one by one through emit_token, the plain selection's own bookkeeping, so a finishing token or
+// the row's last slot cuts the rest; RS_STEP and RS_POS advance by the number emitted; the last emitted id is the next step's first
+// token.  With log-probs, the emitted rows' entries of the scratch a launch_topk_logprob over the B * Q rows filled (entry 0 of a row
+// is its argmax) are copied into the slabs.  counters [B][4] += {1, emitted, drafted, emitted - 1}.
+__global__ __launch_bounds__(1024) void spec_accept_kernel(SpecAcceptArgs p) {
+    __shared__ BlockRed red;
+    __shared__ int a_s[8];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, Q = p.Q;
+    const int nq = min(p.nq[b], min(Q, 8));
+    if (nq <= 0) return;
+    int* rs = p.rows + (size_t)b * RS_STRIDE;
+    for (int j = 0; j < nq; ++j) {
+        const float* lg = p.logits + ((size_t)b * Q + j) * p.ldl;
+        float best = -INFINITY;
+        int bi = 0x7FFFFFFF;
+        for (int i = tid * 4; i < p.V; i += 4096) {
+            const f32x4 v = ld16f(lg + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) argmax_combine2(best, bi, v[e], i + e);
+        }
+        block_argmax(best, bi, red, lane, wave);
+        if (tid == 0) a_s[j] = bi;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const int* tok = p.tok + (size_t)b * Q;
+    int* out = p.out_ids + rs[RS_OUT_OFF];
+    const int max_new = rs[RS_MAXNEW];
+    int emitted = 0, last = tok[0];
+    for (int j = 0; j < nq; ++j) {
+        if (j > 0 && tok[j] != a_s[j - 1]) break;   // draft j is not what the model says behind its predecessors
+        const int step = rs[RS_STEP];
+        last = emit_token(rs, out, step, a_s[j]);
+        if (p.lp_tok != nullptr && step < max_new) {
+            const size_t slot = (size_t)rs[RS_OUT_OFF] + step, src = ((size_t)b * Q + j) * p.scratch_k;
+            p.lp_tok[slot] = p.scratch_lp[src];
+            for (int t = 0; t < p.lp_k; ++t) {
+                p.lp_top[slot * p.lp_k + t] = p.scratch_lp[src + t];
+                p.lp_ids[slot * p.lp_k + t] = p.scratch_ids[src + t];
+            }
+        }
+        rs[RS_STEP] = step + 1;
+        rs[RS_POS] += 1;
+        emitted += 1;
+        if (rs[RS_FINISHED] || step + 1 >= max_new) break;
+    }
+    p.next_tok[b] = last;
+    if (p.counters != nullptr) {
+        int* c = p.counters + 4 * b;
+        c[0] += 1;
+        c[1] += emitted;
+        c[2] += nq - 1;
+        c[3] += emitted - 1;
+    }
+}
+void launch_spec_accept(const SpecAcceptArgs& a, hipStream_t s) {
+    VC_LAUNCH(spec_accept_kernel, dim3((unsigned)a.B), dim3(1024), 0, s, a);
 }
 
 }  // namespace vc

@@ -587,7 +587,8 @@ class HipEngine:
                  stop_sequences: Optional[Sequence[Sequence[int]]] = None, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                  on_tokens=None, stream_every: int = 1, attention_mask=None, logprobs: bool = False,
-                 top_logprobs: int = 0, processors=None, eos_extra: Sequence[int] = ()) -> np.ndarray:
+                 top_logprobs: int = 0, processors=None, eos_extra: Sequence[int] = (), speculate: Optional[int] = None,
+                 lookup_ngram: int = 2, lookup_ids=None) -> np.ndarray:
         """generate() on the device (vc_generate): greedy, or temperature / top-k / top-p sampling with a counter-based
         generator (same seed -> same tokens).  on_tokens(first_step, ids [B, n]) is called with every `stream_every` new
         columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32.
@@ -600,9 +601,31 @@ class HipEngine:
         words and min_new_tokens / min_length applied on the device in front of every selection, over the history input_ids +
         generated ids (ids outside the vocabulary — the image placeholders — are skipped, where HF would raise); eos_extra: the
         further ids of an EOS list, which min_new_tokens bans beside eos_token_id.  At most 32 bad words of at most 8 ids
-        (ValueError otherwise).  The call runs on the session's own loop; log-probs stay those of the raw logits."""
+        (ValueError otherwise).  The call runs on the session's own loop; log-probs stay those of the raw logits.
+        speculate = k (vc_request_speculation; 1 .. 7): prompt-lookup speculative decoding — every step drafts up to k ids behind
+        the latest earlier occurrence of the sequence's last lookup_ngram .. 1 ids (1 .. 4) in lookup_ids + input_ids + generated ids
+        and verifies them as k + 1 rows of one weight pass; the ids (and log-probs) are those of the call without it, in fewer
+        steps.  lookup_ids: per sequence (a list of B id lists, or one list for B = 1) what the answer is expected to resemble.
+        last_speculation = {"steps", "tokens", "drafted", "accepted"} per-row int arrays, or None when the request was not served:
+        sampling, processors, precision split / strict, B * (k + 1) > 32, a cache too long for the verify attention's LDS score
+        rows (the call then runs as without it).  ValueError for k or lookup_ngram outside their range."""
         ids = self._ids(input_ids)
         B, T = ids.shape
+        self.last_speculation = None
+        look = None
+        if speculate is not None:
+            k, ng = int(speculate), int(lookup_ngram)
+            if not 1 <= k <= 7:
+                raise ValueError(f"speculate (prompt_lookup_num_tokens) must be in 1 .. 7, got {speculate!r}")
+            if not 1 <= ng <= 4:
+                raise ValueError(f"lookup_ngram (max_matching_ngram_size) must be in 1 .. 4, got {lookup_ngram!r}")
+            if lookup_ids is not None:
+                flat_one = B == 1 and all(np.ndim(q) == 0 for q in lookup_ids)   # one sequence given as its ids
+                look = [np.asarray(q, dtype=np.int64).reshape(-1) for q in ([lookup_ids] if flat_one else lookup_ids)]
+                if len(look) != B:
+                    raise ValueError(f"lookup_ids holds {len(look)} sequences, the batch {B}")
+                if any(len(q) > self.cfg.max_position_embeddings for q in look):
+                    raise ValueError("a lookup sequence is longer than max_position_embeddings")
         if processors is not None and not processors.active:
             processors = None
         if processors is not None and (not processors.fits_device() or len(eos_extra) > _lp.MAX_EOS_EXTRA):
@@ -689,6 +712,19 @@ class HipEngine:
                 self.lib.vc_clear_attention_mask(self._model)
                 self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
                 raise
+        if speculate is not None and B <= self.MAX_BATCH:
+            lk_flat = lk_lens = None
+            if look is not None:
+                lk_flat = np.ascontiguousarray(np.concatenate(look + [np.zeros(1, np.int64)]).clip(-2 ** 31, 2 ** 31 - 1), dtype=np.int32)
+                lk_lens = np.ascontiguousarray([len(q) for q in look], dtype=np.int32)
+            try:
+                self._check(self.lib.vc_request_speculation(self._model, k, ng, None if look is None else lk_flat.ctypes.data_as(C.c_void_p),
+                                                            None if look is None else lk_lens.ctypes.data_as(C.c_void_p), B))
+            except BaseException:
+                self.lib.vc_clear_attention_mask(self._model)
+                self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
+                self.lib.vc_request_logits_processors(self._model, None)
+                raise
         self._check(self.lib.vc_generate(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev,
                                          int(max_new_tokens), eos, pad,
                                          flat.ctypes.data_as(C.c_void_p) if stops else None,
@@ -698,6 +734,10 @@ class HipEngine:
         if errs:
             raise errs[0]
         self._cur_batch = B
+        if speculate is not None:
+            cnt = np.zeros((B, 4), dtype=np.int32)
+            if self.lib.vc_last_speculation(self._model, cnt.ctypes.data_as(C.c_void_p), B) == 0:
+                self.last_speculation = {name: cnt[:, i].copy() for i, name in enumerate(("steps", "tokens", "drafted", "accepted"))}
         if want_lp:
             mn = int(max_new_tokens)
             self.last_generate_logprobs = (tok_lp.reshape(B, mn)[:, : n.value].copy(), top_lp.reshape(B, mn, K)[:, : n.value].copy(),
@@ -735,6 +775,7 @@ class HipEngine:
         return out[:, : min(int(lens.max()) + 1, mn)].copy(), lens, score
 
     last_beam_steps = 0
+    last_speculation = None
 
     # bookkeeping used by decode_step
     def note_prefill(self, B: int):

@@ -74,12 +74,15 @@ class GenerateOutput(dict):
     top_logprobs [B, n, K] float32 / top_token_ids [B, n, K] int64: the K most likely tokens of every step, ordered by (log-prob
     descending, id ascending); sequence_logprob [B]: row sums of token_logprobs.  n = generated columns.  A row's finishing token is
     scored; positions behind it hold 0.0 / 0.0 / -1.  sequences_scores [B] float32 (num_beams != 1; HF's name): the winning
-    hypothesis' sum_logprobs / len ** length_penalty.  Fields that were not requested are None."""
+    hypothesis' sum_logprobs / len ** length_penalty.  speculation (prompt_lookup_num_tokens, when the request was served): per-row
+    int arrays "steps", "tokens", "drafted", "accepted" of the verify loop (not part of the integer indexing).  Fields that were not
+    requested are None."""
 
     def __init__(self, sequences=None, token_logprobs=None, top_logprobs=None, top_token_ids=None, sequence_logprob=None,
-                 sequences_scores=None):
+                 sequences_scores=None, speculation=None):
         super().__init__(sequences=sequences, token_logprobs=token_logprobs, top_logprobs=top_logprobs,
-                         top_token_ids=top_token_ids, sequence_logprob=sequence_logprob, sequences_scores=sequences_scores)
+                         top_token_ids=top_token_ids, sequence_logprob=sequence_logprob, sequences_scores=sequences_scores,
+                         speculation=speculation)
         self.__dict__ = self
 
     def __getitem__(self, k):
@@ -450,7 +453,8 @@ class _HipCausalLMBase:
                  attention_mask=None, generator=None, seed: Optional[int] = None, return_dict_in_generate: bool = False,
                  output_logprobs: bool = False, top_logprobs: int = 0, repetition_penalty: Optional[float] = None,
                  no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
-                 bad_words_ids=None, processors_on_device: bool = True, **kwargs):
+                 bad_words_ids=None, processors_on_device: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
+                 max_matching_ngram_size: int = 2, lookup_ids=None, **kwargs):
         """Returns cat(input_ids, new_ids) [B, T+n] int64 — the prompt part keeps its negative placeholder ids,
         callers slice `[:, T:]` (serve/cli.py:135).
 
@@ -485,6 +489,19 @@ class _HipCausalLMBase:
         beam-sample, stopping criteria and strict mode — or beam_on_device=False — take the host loop `_beam_search`.  Both return
         the same tensor; with return_dict_in_generate the GenerateOutput carries `sequences_scores` [B].
 
+        prompt_lookup_num_tokens = k (1 .. 7; current Transformers' name), max_matching_ngram_size (1 .. 4, default 2), lookup_ids:
+        prompt-lookup speculative decoding inside the device loop.  Every step drafts up to k ids — those behind the latest earlier
+        occurrence of the sequence's last n-gram in lookup_ids + input_ids + generated ids — and verifies them as k + 1 rows of ONE
+        weight pass; as long as the drafts are what the model itself picks they are emitted together.  The returned ids,
+        their number and the log-probs are exactly (array_equal) those of the call without the argument; only the step count
+        drops.  lookup_ids (a list of B id lists; one list for B = 1) is what the caller expects the answer to resemble: the
+        previous turn, a class list.  A GenerateOutput carries `speculation` (per-row "steps", "tokens", "drafted", "accepted").
+        The request is NOT served — the call runs as without it, `speculation` is None — with: sampling; a logits-processor set;
+        num_beams > 1; precision "split" / "strict"; a stopping criterion that needs the host loop; B * (k + 1) > 32; a KV
+        capacity whose k + 1 score rows exceed a CU's LDS.  A speculated call runs on the session's own loop, not in the decode
+        pool, and closes it: decode_step / extend behind it refuse until the next prefill.  k or the n-gram size outside their
+        range raise ValueError before the engine is touched.
+
         Everything the reference's callers ask for runs on the device inside the hipGraph-replayed decode loop
         (vc_generate): greedy argmax; sampling with HF's warper order temperature -> top-k -> top-p -> multinomial
         (`top_k` defaults to 50 when sampling, HF's GenerationConfig default, which is what serve/cli.py:122-132 gets);
@@ -510,6 +527,12 @@ class _HipCausalLMBase:
                                       "output_logprobs=True / top_logprobs=K instead")
         if num_beams != 1 and want_lp:
             raise NotImplementedError("per-token log-probs (output_logprobs / top_logprobs) are not implemented for num_beams != 1")
+        if prompt_lookup_num_tokens is not None:
+            if not 1 <= int(prompt_lookup_num_tokens) <= 7:
+                raise ValueError(f"prompt_lookup_num_tokens must be in 1 .. 7, got {prompt_lookup_num_tokens!r}")
+            if not 1 <= int(max_matching_ngram_size) <= 4:
+                raise ValueError(f"max_matching_ngram_size must be in 1 .. 4, got {max_matching_ngram_size!r}")
+        self.engine.last_speculation = None
         eos_all = self.config.eos_token_id if eos_token_id is None else eos_token_id
         eos_all = [int(e) for e in (eos_all if isinstance(eos_all, (list, tuple)) else ([] if eos_all is None else [eos_all]))]
         proc = _lp.make(repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, bad_words_ids, eos_all)
@@ -588,7 +611,9 @@ class _HipCausalLMBase:
                                        top_k=top_k or 0, top_p=1.0 if top_p is None else top_p, seed=seed or 0,
                                        on_tokens=on_tokens, stream_every=kwargs.get("stream_every", 1),
                                        attention_mask=attention_mask, logprobs=want_lp, top_logprobs=K, processors=proc,
-                                       eos_extra=eos_more if proc is not None else ())
+                                       eos_extra=eos_more if proc is not None else (),
+                                       speculate=None if prompt_lookup_num_tokens is None else int(prompt_lookup_num_tokens),
+                                       lookup_ngram=int(max_matching_ngram_size), lookup_ids=lookup_ids)
             self._generation += 1
             out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
             if want_lp:
@@ -668,10 +693,11 @@ class _HipCausalLMBase:
             out = out.to(input_ids.device)
         if not as_dict:
             return out
+        spec = self.engine.last_speculation
         if not want_lp:
-            return GenerateOutput(sequences=out)
+            return GenerateOutput(sequences=out, speculation=spec)
         return GenerateOutput(sequences=out, token_logprobs=tok_lp, top_logprobs=top_lp if K else None,
-                              top_token_ids=top_id if K else None, sequence_logprob=tok_lp.sum(dim=1))
+                              top_token_ids=top_id if K else None, sequence_logprob=tok_lp.sum(dim=1), speculation=spec)
 
     _sample_calls = 0
 
