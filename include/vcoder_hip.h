@@ -358,6 +358,24 @@ int vc_request_speculation(vc_model* m, int k, int max_ngram, const int32_t* loo
  * drafts accepted}.  VC_ERR_STATE when that call did not speculate. */
 int vc_last_speculation(vc_model* m, int32_t* out /* [B][4] */, int B);
 
+/* num_return_sequences for the NEXT vc_generate call (one-shot): every prompt yields n sequences.  That call takes B prompts (ids and
+ * pixels of B samples) and returns out_ids [B n, max_new], rows b n + j; its log-prob buffers and the callback's columns are B n rows
+ * wide.  The result is, bit for bit, that of the same call on the prompts repeated n times (row r seeds its sampler with its own
+ * index).  Served — one prefill over the B prompts, whose keys and values every step of the B n rows reads once per prompt with the
+ * fan-out attention — on the session's own loop (whatever VC_POOL says) in the bf16 precision mode with head dim 128 or 64, a bf16
+ * or e4m3 cache, 2 <= n <= 8, n score rows over max_position_embeddings keys within a CU's LDS, and a prefill whose bits do not
+ * depend on the rows sharing its launch — vc_model_set_batch_invariant(1), or shapes at which no GEMM of the repeated call's prefill
+ * has more than one round of tiles (else the repeated call gives identical prompts different bits and no shared prefix equals it);
+ * every weight format, log-probs and logits processors included.  Otherwise the engine repeats the prompts, pixels, image counts and mask rows n times and runs the call
+ * as it would run B n prompts.  Behind a served call a cache row no longer holds one sequence: vc_decode_step and vc_extend refuse
+ * (VC_ERR_STATE) until the next prefill.  B n > 16 makes that call fail with VC_ERR_INVALID.  |n| above 16: VC_ERR_INVALID here,
+ * nothing changed.  n < -1: |n| sequences per prompt, never served (the repeated prompts: the reference of the served form).  Cleared
+ * when that call returns, also when it fails; -1 .. 1 cancels.  vc_generate_beam ignores it. */
+int vc_request_fanout(vc_model* m, int n);
+/* What the last vc_generate of this session made of a fan-out request: out = {n, shared (1: served; 0: the prompts were repeated),
+ * prompt rows the prefill ran over (B when served, B n otherwise)}.  VC_ERR_STATE when that call had no request. */
+int vc_last_fanout(vc_model* m, int32_t* out /* [3] */);
+
 /* Logits processors of the NEXT vc_generate / vc_generate_greedy* call (one-shot), applied on the device in front of every selection
  * of the loop, in HF 4.31's order (generation/logits_process.py):
  *   repetition_penalty p   RepetitionPenaltyLogitsProcessor: every id t of the row's history gets raw[t] < 0 ? raw[t] * p : raw[t] / p

@@ -100,6 +100,16 @@ void vck_attention_decode_rows(const uint16_t* qkv, uint16_t* k, uint16_t* v, ui
 int vck_attention_verify(const uint16_t* qkv, void* k, void* v, uint16_t* out, int B, int H, int hd, int kv_stride, int Q,
                          const int* pos_rows, int pos_stride, const int* nq, const float* rope_cos, const float* rope_sin,
                          float scale, int kv8, const uint8_t* key_mask, int mask_stride, void* stream);
+/* fan-out attention (generate(num_return_sequences = n)): rows g n .. g n + n - 1 of qkv / out (G groups, n <= 8) continue one prompt
+ * of prefix_len[g] keys held in positions [0, prefix_len[g]) of cache row prefix_row[g] (NULL: row g) of k / v
+ * [cache_rows,H,kv_stride,hd]; row r appends at position pos_rows[g n * pos_stride] (>= the prefix length, one position per group)
+ * of cache row r and reads its own keys behind the prefix from there.  A prefix key row is loaded once per (group, head).  Row r's
+ * output and appended cache rows are bit-identical to what vck_attention_decode_rows gives it over a cache row that holds prefix +
+ * own tail (an exactly-zero output may differ in sign).  hd 128 or 64.  Returns 0, or -1 when the score rows of n queries over
+ * kv_stride keys do not fit the LDS of a CU (nothing is launched). */
+int vck_attention_fanout(const uint16_t* qkv, void* k, void* v, uint16_t* out, int G, int H, int hd, int kv_stride, int n,
+                         int cache_rows, const int* pos_rows, int pos_stride, const int* prefix_len, const int* prefix_row,
+                         const float* rope_cos, const float* rope_sin, float scale, int kv8, void* stream);
 /* extend attention (a multi-token continuation of a cached sequence): n roped queries per (b, h) (q [B,H,q_stride,hd]) at
  * positions P .. P+n-1 over keys [0, P+n) of the key-major decode cache (k, v [B,H,kv_stride,hd]: bf16, or e4m3 bytes when
  * kv8), causal inside the chunk; key_mask [B][mask_stride] bytes (0 = hidden; key 0 must be visible) or NULL.  hd 128.

@@ -832,6 +832,39 @@ def bench_attention_verify():
                   f"{up:7.1f} us  (x{uv / up:4.2f}; {Q} plain launches {Q * up:7.1f} us)", flush=True)
 
 
+def bench_attention_fanout():
+    """attention_fanout_kernel (n rows per prompt; the prompt's keys and values read once per group and head) beside the fused decode
+    attention over the same n B rows: 7b heads, a prompt of 1216 keys and 64 tail keys, bf16 and e4m3 caches; B = 1 at n = 2 / 4 / 8
+    and B = 2 at n = 8"""
+    H, hd, Pn, pos, S = 32, 128, 1216, 1216 + 64, 1408
+    D = H * hd
+    cos, sin = torch.rand(S, hd // 2, device=dev), torch.rand(S, hd // 2, device=dev)
+    scale = C.c_float(1 / math.sqrt(hd))
+    for kv8 in (0, 1):
+        for B, n in ((1, 2), (1, 4), (1, 8), (2, 8)):
+            es, R = 1 if kv8 else 2, B * n
+            ks = [torch.randint(0, 120, (R, H, S, hd * es), dtype=torch.uint8, device=dev) for _ in range(4)]
+            vs = [torch.randint(0, 120, (R, H, S, hd * es), dtype=torch.uint8, device=dev) for _ in range(4)]
+            qkv = bf16(R, 3 * D)
+            out = torch.zeros((R, D), dtype=torch.bfloat16, device=dev)
+            rec = torch.tensor([[1, pos]] * R, dtype=torch.int32, device=dev)
+            plen = torch.full((B,), Pn, dtype=torch.int32, device=dev)
+            it = [0]
+
+            def fanout():
+                it[0] += 1
+                lib.vck_attention_fanout(P(qkv), P(ks[it[0] % 4]), P(vs[it[0] % 4]), P(out), B, H, hd, S, n, R, C.c_void_p(rec.data_ptr() + 4), 2,
+                                         P(plen), None, P(cos), P(sin), scale, 3 if kv8 else 0, None)
+
+            def plain():
+                it[0] += 1
+                lib.vck_attention_decode_masked(P(qkv), P(ks[it[0] % 4]), P(vs[it[0] % 4]), P(out), R, H, hd, S, C.c_void_p(rec.data_ptr() + 4),
+                                                2, C.c_void_p(rec.data_ptr()), P(cos), P(sin), scale, 3 if kv8 else 0, 0, None, 0, None)
+            uf, up = timeit(fanout, iters=40), timeit(plain, iters=40)
+            print(f"attention_fanout {'e4m3' if kv8 else 'bf16'} B {B} n {n} prompt {Pn} ctx {pos + 1}: {uf:7.1f} us | decode attention over {R} rows: "
+                  f"{up:7.1f} us  (x{uf / up:4.2f})", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["gemm", "gemv", "attn", "dattn"]
     table = {"gemm_qkv": bench_gemm_qkv, "gemm": bench_gemm, "gemv": bench_gemv, "attn": bench_attn, "dattn": bench_dattn, "gemv_fp8": bench_gemv_fp8,
@@ -840,6 +873,6 @@ if __name__ == "__main__":
              "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,
              "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn, "token_logprob": bench_token_logprob,
              "topk_logprob": bench_topk_logprob, "logits_process": bench_logits_process,
-             "score_head": bench_score_head, "attention_verify": bench_attention_verify, "gemv_formats": bench_gemv_formats, "gemv_w4": lambda: bench_gemv_formats(("w4",))}
+             "score_head": bench_score_head, "attention_verify": bench_attention_verify, "attention_fanout": bench_attention_fanout, "gemv_formats": bench_gemv_formats, "gemv_w4": lambda: bench_gemv_formats(("w4",))}
     for w in what:
         table[w]()

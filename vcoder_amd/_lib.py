@@ -124,6 +124,12 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_request_speculation.restype = C.c_int
     lib.vc_last_speculation.argtypes = [vp, vp, i32]
     lib.vc_last_speculation.restype = C.c_int
+    lib.vc_request_fanout.argtypes = [vp, i32]
+    lib.vc_request_fanout.restype = C.c_int
+    lib.vc_last_fanout.argtypes = [vp, vp]
+    lib.vc_last_fanout.restype = C.c_int
+    lib.vck_attention_fanout.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, C.c_float, i32, vp]
+    lib.vck_attention_fanout.restype = C.c_int
     lib.vck_topk_logprob.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     lib.vck_topk_logprob.restype = None
     lib.vc_request_logits_processors.argtypes = [vp, C.POINTER(LogitsProcessors)]

@@ -1406,4 +1406,353 @@ void launch_attention_verify(const AttnVerifyArgs& a, hipStream_t s) {
     }
 }
 
+// =============================================================================================
+// Fan-out attention (generate(num_return_sequences = n)): the n <= 8 rows g n .. g n + n - 1 of group g continue ONE prompt of P keys
+// that sits in positions [0, P) of cache row `prefix_row[g]`; every row keeps its own keys P .. pos in ITS cache row.  All rows of a
+// group stand at the same position pos >= P.  One workgroup per (group, head) is the verify kernel with a second, per-query stream
+// behind the shared one: a prefix key row is loaded once and dotted against / accumulated into all n queries, a tail key row is
+// loaded per query.  Row j's output and appended cache rows are the bits attention_decode_fused_kernel gives it over a cache row that
+// holds prefix + own tail, for the verify kernel's reasons: key -> (wave, window slot, key row) is the decode kernel's map (UK, KPW,
+// BATCH), lanes_sum, the stride-512 softmax reductions, the lane and wave order of the V pass, vacc.  A query's key sequence per
+// lane is round by round, slot by slot, in both kernels; which of the two streams a round comes from does not enter the arithmetic.
+// The split between the streams is per (wave, round): the KPW * UK keys a wave covers in one round are shared when all of them lie
+// below P, else the round is loaded per query, each lane taking its key from the prefix row (key < P) or the query's own row.
+// Keys behind pos, up to the padded end, carry -inf (the decode kernel's padded end is the same: one position for all queries).
+//   phase 0  64 threads per query: rotate q / k at pos, append K and V to the row's OWN cache row, q (bf16-rounded) to LDS
+//   phase 1  shared rounds: one load, n dots; tail rounds: per query — both as one rolling window of UK loads per lane
+//   phase 2  softmax per query
+//   phase 3  the V stream the same way into n accumulator sets; `part` serves the queries one after another
+// Scores: n rows of kv_stride + BATCH floats of dynamic LDS.  No key mask (generate()'s cached steps run under an all-ones mask).
+// =============================================================================================
+template <int HD, int UK, bool F8, int QM>
+__global__ __launch_bounds__(512) void attention_fanout_kernel(AttnFanoutArgs p) {
+    constexpr int EPL = F8 ? 16 : 8;
+    constexpr int ESZ = F8 ? 1 : 2;
+    constexpr int ROWB = HD * ESZ;
+    constexpr int LPK = HD / EPL;
+    constexpr int KPW = 64 / LPK;
+    constexpr int WR = KPW * UK;          // keys one wave covers per round
+    constexpr int BATCH = 8 * WR;
+    VC_DYNAMIC_SMEM(float, sc);   // [n][kv_stride + BATCH]
+    __shared__ __attribute__((aligned(16))) float q_s[QM][HD];
+    __shared__ __attribute__((aligned(16))) float part[8][HD];
+    __shared__ float red[QM][8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x, g = blockIdx.y;
+    const int nq = min(p.n, QM);
+    const int r0 = g * p.n;                                   // first row of the group
+    const int pos = p.pos_dev[(size_t)r0 * p.pos_stride];
+    const int P = p.P_dev[g];
+    const int prow = p.prefix_row_dev != nullptr ? p.prefix_row_dev[g] : g;
+    // nothing is touched for a group whose description does not fit the cache
+    if (nq <= 0 || P < 0 || pos < P || pos >= p.kv_stride || prow < 0 || prow >= p.cache_rows || r0 + nq > p.cache_rows) return;
+    const int srow = p.kv_stride + BATCH;
+    const int ctx = pos + 1;
+    const int D = p.H * HD;
+    const size_t head_bytes = (size_t)p.kv_stride * ROWB;
+    const char* kpre = reinterpret_cast<const char*>(p.k) + ((size_t)prow * p.H + h) * head_bytes;
+    const char* vpre = reinterpret_cast<const char*>(p.v) + ((size_t)prow * p.H + h) * head_bytes;
+    char* kown0 = reinterpret_cast<char*>(p.k) + ((size_t)r0 * p.H + h) * head_bytes;   // query j's own (row, head): + j * own_step
+    char* vown0 = reinterpret_cast<char*>(p.v) + ((size_t)r0 * p.H + h) * head_bytes;
+    const size_t own_step = (size_t)p.H * head_bytes;
+    const int krow = lane / LPK, kcol = (lane % LPK) * EPL;
+    // a shared round reads the prefix row (keys < P; the window's look-ahead is clamped into it); a tail round takes key < P from the
+    // prefix row and the others, clamped to pos, from the query's own row
+    auto pre_off = [&](int key) { return (uint32_t)(min(key, P - 1) * ROWB) + (uint32_t)(kcol * ESZ); };
+    auto tail_at = [&](const char* pre, const char* own, int key) {
+        const int kk = min(key, pos);
+        return (kk < P ? pre : own) + ((uint32_t)(kk * ROWB) + (uint32_t)(kcol * ESZ));
+    };
+    // ---- phase 0: query j = tid / 64, all at position pos
+    {
+        const int j = tid >> 6, d = tid & 63;
+        if (j < nq && d < HD / 2) {
+            const float c = p.rope_cos[(size_t)pos * (HD / 2) + d], s = p.rope_sin[(size_t)pos * (HD / 2) + d];
+            const bf16_t* row = p.qkv + (size_t)(r0 + j) * (3 * D) + h * HD;
+            const bf16_t rq0 = row[d], rq1 = row[d + HD / 2], rk0 = row[D + d], rk1 = row[D + d + HD / 2];
+            const bf16_t v0 = row[2 * D + d], v1 = row[2 * D + d + HD / 2];
+            const float q0 = bf2f(rq0), q1 = bf2f(rq1);
+            const float k0 = bf2f(rk0), k1 = bf2f(rk1);
+            q_s[j][d] = bf2f(f2bf(q0 * c - q1 * s));
+            q_s[j][d + HD / 2] = bf2f(f2bf(q1 * c + q0 * s));
+            char* kb_ = kown0 + j * own_step;
+            char* vb_ = vown0 + j * own_step;
+            if constexpr (F8) {
+                uint8_t* ko = reinterpret_cast<uint8_t*>(kb_) + (size_t)pos * HD;
+                ko[d] = f2fp8(bf2f(f2bf(k0 * c - k1 * s)));
+                ko[d + HD / 2] = f2fp8(bf2f(f2bf(k1 * c + k0 * s)));
+                uint8_t* vo = reinterpret_cast<uint8_t*>(vb_) + (size_t)pos * HD;
+                vo[d] = f2fp8(bf2f(v0));
+                vo[d + HD / 2] = f2fp8(bf2f(v1));
+            } else {
+                bf16_t* ko = reinterpret_cast<bf16_t*>(kb_) + (size_t)pos * HD;
+                ko[d] = f2bf(k0 * c - k1 * s);
+                ko[d + HD / 2] = f2bf(k1 * c + k0 * s);
+                bf16_t* vo = reinterpret_cast<bf16_t*>(vb_) + (size_t)pos * HD;
+                vo[d] = v0;
+                vo[d + HD / 2] = v1;
+            }
+        }
+    }
+    __syncthreads();  // workgroup-scope release/acquire: the appended K / V rows are visible to this block
+    const int ctx_pad = (ctx + BATCH - 1) / BATCH * BATCH;
+    // this wave's rounds start at keys wave * WR + r * BATCH; the first n_sh of them lie below P as a whole
+    const int kb0 = wave * WR;
+    const int n_sh = P >= kb0 + WR ? (P - kb0 - WR) / BATCH + 1 : 0;
+    const int kb_tail = kb0 + n_sh * BATCH;       // first tail round (>= ctx_pad: none)
+    // ---- phase 1: scores
+    u32x4 kv[UK];
+    {
+        constexpr bool PACKQ = F8 && QM == 8;   // as the verify kernel: 8 queries of 16 elements are held as operand-format pairs
+        float qv[PACKQ ? 1 : QM][EPL];
+        uint32_t qp[PACKQ ? QM : 1][EPL / 2];
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            const float* qj = q_s[j < nq ? j : 0] + (lane % LPK) * EPL;
+            if constexpr (PACKQ) {
+#pragma unroll
+                for (int e = 0; e < EPL / 2; ++e) qp[j][e] = pack_bf2(qj[2 * e], qj[2 * e + 1]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) qv[j][e] = qj[e];
+            }
+        }
+        auto qe = [&](int j, int e) {
+            if constexpr (PACKQ) return (e & 1) ? bf2f_hi(qp[j][e >> 1]) : bf2f_lo(qp[j][e >> 1]);
+            else return qv[j][e];
+        };
+        auto dot = [&](const u32x4& r, int j) {
+            float s = 0.f;
+            if constexpr (F8) {
+#pragma unroll
+                for (int w4 = 0; w4 < 4; ++w4) {
+                    const f32x4 f = fp8x4_to_f32x4(r[w4]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) s += qe(j, 4 * w4 + e) * f[e];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s += qe(j, 2 * e) * bf2f_lo(r[e]) + qe(j, 2 * e + 1) * bf2f_hi(r[e]);
+            }
+            return s;
+        };
+#pragma unroll
+        for (int u = 0; u < UK; ++u) {
+            const int key = kb0 + u * KPW + krow;
+            kv[u] = n_sh > 0 ? ld16_stream(kpre + pre_off(key)) : ld16_stream(tail_at(kpre, kown0, key));
+        }
+        for (int kb = kb0; kb < kb_tail; kb += BATCH) {
+            const bool last = kb + BATCH >= kb_tail;     // the look-ahead of the last shared round: query 0's first tail round
+#pragma unroll
+            for (int u = 0; u < UK; ++u) {
+                const int key = kb + u * KPW + krow;
+                const u32x4 r = kv[u];
+                kv[u] = last ? ld16_stream(tail_at(kpre, kown0, key + BATCH)) : ld16_stream(kpre + pre_off(key + BATCH));
+#pragma unroll
+                for (int j = 0; j < QM; ++j) {
+                    if (j < nq) {
+                        float s = dot(r, j);
+                        s = lanes_sum<LPK>(s);
+                        if ((lane % LPK) == 0) sc[j * srow + key] = s * p.scale;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            if (j < nq) {
+                const char* own = kown0 + j * own_step;
+                const char* nxt = kown0 + (j + 1 < nq ? j + 1 : j) * own_step;
+                for (int kb = kb_tail; kb < ctx_pad; kb += BATCH) {
+                    const bool last = kb + BATCH >= ctx_pad;   // look-ahead: the next query's first tail round
+#pragma unroll
+                    for (int u = 0; u < UK; ++u) {
+                        const int key = kb + u * KPW + krow;
+                        const u32x4 r = kv[u];
+                        kv[u] = ld16_stream(last ? tail_at(kpre, nxt, kb_tail + u * KPW + krow) : tail_at(kpre, own, key + BATCH));
+                        float s = dot(r, j);
+                        s = lanes_sum<LPK>(s);
+                        if ((lane % LPK) == 0) sc[j * srow + key] = key <= pos ? s * p.scale : -INFINITY;
+                    }
+                }
+            }
+        }
+    }
+    u32x4 vv[UK];
+#pragma unroll
+    for (int u = 0; u < UK; ++u) {
+        const int key = kb0 + u * KPW + krow;
+        vv[u] = n_sh > 0 ? ld16_stream(vpre + pre_off(key)) : ld16_stream(tail_at(vpre, vown0, key));
+    }
+    __syncthreads();
+    // ---- phase 2: softmax of every query over sc[j][0 .. ctx_pad)
+    float inv[QM];
+    {
+        float mx[QM];
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            mx[j] = -INFINITY;
+            if (j < nq) {
+                for (int i = tid; i < ctx_pad; i += 512) mx[j] = fmaxf(mx[j], sc[j * srow + i]);
+                mx[j] = wave_max(mx[j]);
+                if (lane == 0) red[j][wave] = mx[j];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            if (j < nq) {
+                mx[j] = red[j][0];
+#pragma unroll
+                for (int w = 1; w < 8; ++w) mx[j] = fmaxf(mx[j], red[j][w]);
+            }
+        }
+        __syncthreads();
+        float sum[QM];
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            sum[j] = 0.f;
+            if (j < nq) {
+                for (int i = tid; i < ctx_pad; i += 512) {
+                    const float e = __expf(sc[j * srow + i] - mx[j]);
+                    sc[j * srow + i] = e;
+                    sum[j] += e;
+                }
+                sum[j] = wave_sum(sum[j]);
+                if (lane == 0) red[j][wave] = sum[j];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QM; ++j) {
+            inv[j] = 0.f;
+            if (j < nq) {
+                float t = 0.f;
+#pragma unroll
+                for (int w = 0; w < 8; ++w) t += red[j][w];
+                inv[j] = 1.0f / t;
+            }
+        }
+    }
+    // ---- phase 3: the V stream into nq accumulator sets
+    float acc[QM][EPL];
+#pragma unroll
+    for (int j = 0; j < QM; ++j)
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) acc[j][e] = 0.f;
+    auto accum = [&](float* a, float pk, const u32x4& v) {   // the verify kernel's accumulation of one V row into one query's set
+        if constexpr (F8) {
+#pragma unroll
+            for (int w4 = 0; w4 < 4; ++w4) {
+                const f32x4 f = fp8x4_to_f32x4(v[w4]);
+                a[4 * w4] = vacc<false>(a[4 * w4], pk, f[0]);
+                a[4 * w4 + 1] = vacc<false>(a[4 * w4 + 1], pk, f[1]);
+                if (w4 == 3) {
+                    a[14] = vacc<true>(a[14], pk, f[2]);
+                    a[15] = vacc<true>(a[15], pk, f[3]);
+                } else {
+                    a[4 * w4 + 2] = vacc<false>(a[4 * w4 + 2], pk, f[2]);
+                    a[4 * w4 + 3] = vacc<false>(a[4 * w4 + 3], pk, f[3]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                a[2 * e] = vacc<false>(a[2 * e], pk, bf2f_lo(v[e]));
+                a[2 * e + 1] = vacc<false>(a[2 * e + 1], pk, bf2f_hi(v[e]));
+            }
+            a[6] = vacc<true>(a[6], pk, bf2f_lo(v[3]));
+            a[7] = vacc<true>(a[7], pk, bf2f_hi(v[3]));
+        }
+    };
+    for (int kb = kb0; kb < kb_tail; kb += BATCH) {
+        const bool last = kb + BATCH >= kb_tail;
+#pragma unroll
+        for (int u = 0; u < UK; ++u) {
+            const int key = kb + u * KPW + krow;
+            const u32x4 v = vv[u];
+            vv[u] = last ? ld16_stream(tail_at(vpre, vown0, key + BATCH)) : ld16_stream(vpre + pre_off(key + BATCH));
+#pragma unroll
+            for (int j = 0; j < QM; ++j) {
+                if (j < nq) accum(acc[j], sc[j * srow + key], v);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < QM; ++j) {
+        if (j < nq) {
+            const char* own = vown0 + j * own_step;
+            const char* nxt = vown0 + (j + 1 < nq ? j + 1 : j) * own_step;
+            for (int kb = kb_tail; kb < ctx_pad; kb += BATCH) {
+                const bool last = kb + BATCH >= ctx_pad;
+#pragma unroll
+                for (int u = 0; u < UK; ++u) {
+                    const int key = kb + u * KPW + krow;
+                    const u32x4 v = vv[u];
+                    vv[u] = ld16_stream(last ? tail_at(vpre, nxt, kb_tail + u * KPW + krow) : tail_at(vpre, own, key + BATCH));
+                    accum(acc[j], sc[j * srow + key], v);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < QM; ++j) {
+        if (j < nq) {   // block-uniform: the barriers below are reached by every thread
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) {
+                float a = acc[j][e];
+#pragma unroll
+                for (int mk = LPK; mk < 64; mk <<= 1) a += shfl_xor(a, mk);
+                acc[j][e] = a;
+            }
+            if (lane < LPK) {
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) part[wave][lane * EPL + e] = acc[j][e];
+            }
+            __syncthreads();
+            if (tid < HD) {
+                float a = 0.f;
+#pragma unroll
+                for (int w = 0; w < 8; ++w) a += part[w][tid];
+                a *= inv[j];
+                p.out[(size_t)(r0 + j) * D + h * HD + tid] = f2bf(a);
+            }
+            __syncthreads();   // `part` is free for the next query
+        }
+    }
+}
+
+template <int HD, int UK, bool F8, int QM>
+static void launch_attention_fanout_v(const AttnFanoutArgs& a, size_t lds, hipStream_t s) {
+#ifndef VC_EMU
+    static size_t allowed = 0;
+    if (lds > 48 * 1024 && lds > allowed) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_fanout_kernel<HD, UK, F8, QM>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        allowed = lds;
+    }
+#endif
+    VC_LAUNCH((attention_fanout_kernel<HD, UK, F8, QM>), dim3(a.H, a.G), dim3(512), lds, s, a);
+}
+
+// dynamic + static LDS of one workgroup of the fan-out attention; a launch needs it <= ATTN_VERIFY_LDS_MAX
+size_t attention_fanout_lds_bytes(int n, int hd, int kv8, int kv_stride) { return attention_verify_lds_bytes(n, hd, kv8, kv_stride); }
+
+void launch_attention_fanout(const AttnFanoutArgs& a, hipStream_t s) {
+    if (a.n < 1 || a.n > 8 || (a.hd != 128 && a.hd != 64)) throw std::runtime_error("attention_fanout: n in 1 .. 8, head dim 128 or 64");
+    if (attention_fanout_lds_bytes(a.n, a.hd, a.kv8, a.kv_stride) > ATTN_VERIFY_LDS_MAX)
+        throw std::runtime_error("attention_fanout: the score rows of n queries over this cache capacity exceed the LDS of a CU");
+    const int uk = a.kv8 ? (a.hd == 128 ? 6 : 4) : 8, epl = a.kv8 ? 16 : 8;
+    const size_t lds = (size_t)a.n * (a.kv_stride + 8 * (64 / (a.hd / epl)) * uk) * 4;
+    // the rows in flight per lane are the decode kernel's: they are part of the key -> lane map
+    const bool q4 = a.n <= 4;
+    if (a.kv8) {
+        if (a.hd == 128) q4 ? launch_attention_fanout_v<128, 6, true, 4>(a, lds, s) : launch_attention_fanout_v<128, 6, true, 8>(a, lds, s);
+        else q4 ? launch_attention_fanout_v<64, 4, true, 4>(a, lds, s) : launch_attention_fanout_v<64, 4, true, 8>(a, lds, s);
+    } else {
+        if (a.hd == 128) q4 ? launch_attention_fanout_v<128, 8, false, 4>(a, lds, s) : launch_attention_fanout_v<128, 8, false, 8>(a, lds, s);
+        else q4 ? launch_attention_fanout_v<64, 8, false, 4>(a, lds, s) : launch_attention_fanout_v<64, 8, false, 8>(a, lds, s);
+    }
+}
+
 }  // namespace vc

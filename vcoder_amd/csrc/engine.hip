@@ -133,7 +133,8 @@ struct LoopView {
     int capR, capS;
     int* rows;         // RowState records
     const uint8_t* kmask;  // keys hidden from the rows' decode steps ([rows][kmask_stride] bytes, 0 = hidden), or nullptr
-    int kmask_stride;      // (4 bytes of padding follow: a new 4-byte member here keeps sizeof — extend operator== below yourself)
+    int kmask_stride;
+    int fan_n;             // > 1: a fan-out step (vc_request_fanout) — rows g n .. g n + n - 1 share the prompt keys of cache row g
     float* x_dec;
     bf16_t *xg_dec, *qkv_dec, *attn_dec, *h_dec;
     float* logits;
@@ -157,16 +158,17 @@ struct LoopView {
     // processor launch, the selection reads the raw rows.
     const int *proc_prompt, *proc_bad;
     float* proc_logits;
+    const int* fan_P;      // fan-out step: the prompt length of every group (device ints), else nullptr
 };
 inline bool operator==(const LoopView& a, const LoopView& b) {
-    static_assert(sizeof(LoopView) == 240, "LoopView changed: compare the new member here");
+    static_assert(sizeof(LoopView) == 248, "LoopView changed: compare the new member here");
     return a.st == b.st && a.kc == b.kc && a.vc == b.vc && a.es == b.es && a.split_G == b.split_G && a.capR == b.capR &&
            a.capS == b.capS && a.rows == b.rows && a.kmask == b.kmask && a.kmask_stride == b.kmask_stride && a.x_dec == b.x_dec &&
            a.xg_dec == b.xg_dec && a.qkv_dec == b.qkv_dec && a.attn_dec == b.attn_dec && a.h_dec == b.h_dec && a.logits == b.logits &&
            a.next_tok == b.next_tok && a.out_ids == b.out_ids && a.ssq == b.ssq && a.sk_scratch == b.sk_scratch &&
            a.sk_counters == b.sk_counters && a.stamps == b.stamps && a.stamp_next == b.stamp_next && a.prof_acc == b.prof_acc &&
            a.stamp_scratch == b.stamp_scratch && a.lp_tok == b.lp_tok && a.lp_top == b.lp_top && a.lp_ids == b.lp_ids &&
-           a.lp_k == b.lp_k && a.proc_prompt == b.proc_prompt && a.proc_bad == b.proc_bad && a.proc_logits == b.proc_logits;
+           a.lp_k == b.lp_k && a.proc_prompt == b.proc_prompt && a.proc_bad == b.proc_bad && a.proc_logits == b.proc_logits && a.fan_n == b.fan_n && a.fan_P == b.fan_P;
 }
 
 // The buffers of the device beam loop (vc_generate_beam): the fixed-size part carved from m->bm_state, the tables from m->bm_tab /
@@ -219,6 +221,11 @@ inline bool operator==(const BeamLoop& a, const BeamLoop& b) {
 // A verify step of prompt-lookup speculation (STEP_SPEC) bakes in, beside its view (whose per-step buffers hold B * Q rows) and
 // nrows = B * Q: the draft's token rows, query counts, counters, the lookup / prompt id stores with their strides (the lengths are
 // read on the device), the log-prob scratch with its width, and B, Q, the n-gram size.
+// A fan-out step (STEP_FAN; vc_request_fanout) is a plain step over R = B n rows whose attention is launch_attention_fanout: beside
+// the view's members it bakes in the fan-out width (fan_n: the group of a row, the prefix row g of group g, the kernel's
+// instantiation) and the address of the groups' prompt lengths (fan_P; the lengths themselves are read on the device) — both are
+// LoopView members, so (b) covers them: another n, or another B at the same n (nrows), re-captures; the same (B, n) replays.  The
+// cache capacity in rows (capR) bounds the rows the kernel touches and is a member already.
 struct SpecLoop {
     int *tok, *nq, *counters;
     const int *lookup, *lookup_len, *prompt, *prompt_len;
@@ -250,7 +257,8 @@ enum StepKind {
     STEP_CALL = 1,   // a generate() call's own: log-probs and / or processors
     STEP_BEAM = 2,
     STEP_SPEC = 3,   // the verify step of prompt-lookup speculation
-    STEP_KINDS = 4
+    STEP_FAN = 4,    // the step of a fan-out call (num_return_sequences): the fan-out attention, with or without log-probs / processors
+    STEP_KINDS = 5
 };
 struct StepGraph {
     StepKey key{};
@@ -365,6 +373,16 @@ struct vc_model {
     bool spec_closed = false;     // a speculated call left the rows at different positions: the session's loop is closed
     std::vector<int> spec_counters;
     Buf sp_x, sp_xg, sp_qkv, sp_attn, sp_h, sp_logits, sp_ssq, sp_tok, sp_state, sp_lookup, sp_prompt, sp_lp, sp_ids;
+    // fan-out of the NEXT vc_generate (vc_request_fanout; one-shot): n sequences per prompt.  A served call prefills the B prompts
+    // once into rows 0 .. B - 1 of a cache of fan_rows = B n rows (fan_rows is set around that prefill only) and steps the B n rows with
+    // the fan-out attention; fan_P holds the groups' prompt lengths.  fan_last*: what the last vc_generate made of a request
+    int fan_n = 0, fan_rows = 0;
+    bool fan_share = true;        // false: the caller asked for the repeated prompts (vc_request_fanout(-n))
+    Buf fan_P;
+    Buf fan_px[3];                // the pixels of a request that is not served, every sample's images n times
+    bool fan_closed = false;      // a served fan-out call ran: cache row r no longer holds one sequence — the session's loop is closed
+    bool fan_last = false, fan_last_shared = false;
+    int fan_last_n = 0, fan_last_B = 0;
     bool tok_stale = false;       // vc_rewind ran: the token the last step selected on the device no longer continues the sequence
     bool plan_only = false;       // do_prefill stops behind the splice plan (vc_plan_spliced_len): no tower pass, no state change
     int reserve_new = 64;         // KV slots a vc_prefill keeps free behind the prompt (vc_model_reserve_decode)
@@ -463,6 +481,8 @@ struct OneShotReset {
         clear_generate_logprobs_request(m);
         clear_logits_processors_request(m);
         clear_speculation_request(m);
+        m->fan_n = 0;
+        m->fan_rows = 0;
     }
 };
 

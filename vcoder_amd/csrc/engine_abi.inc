@@ -188,7 +188,8 @@ VC_API void vc_model_destroy(vc_model* m) {
                    &m->s_q, &m->s_attn, &m->s_h, &m->s_kc, &m->s_vc, &m->s_xl, &m->pp_src, &m->pp_sq, &m->pp_tmp, &m->pp_out,
                    &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre,
                    &m->ext_tok, &m->sc_idx, &m->sc_lp, &m->sc_xn, &m->sc_logits, &m->sc_tlp, &m->sc_tid, &m->lp_tok, &m->lp_top,
-                   &m->lp_ids, &m->proc_prompt, &m->proc_bad, &m->proc_logits, &m->bm_state, &m->bm_tab, &m->bm_den, &m->bm_tmp})
+                   &m->lp_ids, &m->proc_prompt, &m->proc_bad, &m->proc_logits, &m->bm_state, &m->bm_tab, &m->bm_den, &m->bm_tmp, &m->fan_P,
+                   &m->fan_px[0], &m->fan_px[1], &m->fan_px[2]})
         b->release();
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
@@ -700,6 +701,32 @@ VC_API int vc_last_speculation(vc_model* m, int32_t* out, int B) {
     return VC_OK;
 }
 
+/* Fan-out of the NEXT vc_generate call (one-shot): n returned sequences per prompt, rows b n + j.  n <= 1 cancels.  See
+ * include/vcoder_hip.h. */
+VC_API int vc_request_fanout(vc_model* m, int n) {
+    if (!m) return VC_ERR_INVALID;
+    if (n < -VC_MAX_ROWS || n > VC_MAX_ROWS) {
+        m->ctx->err = "vc_request_fanout needs |n| <= 16 (batch x n rows: at most 16 sequences per GPU replica)";
+        return VC_ERR_INVALID;
+    }
+    m->fan_n = abs(n) <= 1 ? 0 : abs(n);
+    m->fan_share = n > 0;   // n < -1: |n| sequences per prompt with the prompts repeated (the request is not served)
+    return VC_OK;
+}
+/* what the last vc_generate of this session made of a fan-out request: out = {n, shared (1: one prefill, the fan-out attention; 0:
+ * the prompts were expanded), prompt rows prefilled}; VC_OK, or VC_ERR_STATE (no request) */
+VC_API int vc_last_fanout(vc_model* m, int32_t* out) {
+    if (!m || !out) return VC_ERR_INVALID;
+    if (!m->fan_last) {
+        m->ctx->err = "the last generate call of this session had no fan-out request";
+        return VC_ERR_STATE;
+    }
+    out[0] = m->fan_last_n;
+    out[1] = m->fan_last_shared ? 1 : 0;
+    out[2] = m->fan_last_B;
+    return VC_OK;
+}
+
 /* Logits processors of the NEXT vc_generate* call (one-shot): repetition penalty, no-repeat n-gram, bad words, minimum new tokens,
  * applied on the device in front of every selection.  p == NULL cancels.  See include/vcoder_hip.h. */
 VC_API int vc_request_logits_processors(vc_model* m, const vc_logits_processors* p) {
@@ -920,6 +947,8 @@ VC_API int vc_rewind(vc_model* m, int P) {
 void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* next_tok) {
     REQUIRE(!(m->cur_pos < 0 && m->spec_closed), VC_ERR_STATE,
             "vc_decode_step behind a speculated generate: its rows stand at different positions (prefill again)");
+    REQUIRE(!(m->cur_pos < 0 && m->fan_closed), VC_ERR_STATE,
+            "vc_decode_step behind a fan-out generate: a cache row no longer holds one sequence (prefill again)");
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_decode_step before vc_prefill");
     REQUIRE(tok || !m->tok_stale, VC_ERR_STATE,
             "vc_decode_step(tok = NULL) after vc_rewind: the token selected on the device belongs to the rows that were dropped");
@@ -990,6 +1019,8 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
     // every check before anything is enqueued: a refused call leaves the cache and the loop's state as they were
     REQUIRE(!(m->cur_pos < 0 && m->spec_closed), VC_ERR_STATE,
             "vc_extend behind a speculated generate: its rows stand at different positions (prefill again)");
+    REQUIRE(!(m->cur_pos < 0 && m->fan_closed), VC_ERR_STATE,
+            "vc_extend behind a fan-out generate: a cache row no longer holds one sequence (prefill again)");
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_extend before vc_prefill");
     REQUIRE(tok && n >= 1, VC_ERR_INVALID, "vc_extend needs n >= 1 tokens per row");
     REQUIRE(B == m->curB, VC_ERR_INVALID, "vc_extend: %d rows given, the session's loop has %d", B, m->curB);

@@ -595,7 +595,13 @@ void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_
         [&](int l) {
             AttnDecodeFusedArgs da = decode_attn_args(m, v, l, nrows);
             da.stamp = next_stamp(v);
-            launch_attention_decode_fused(da, v.st);
+            if (v.fan_n > 1) {   // rows g n .. g n + n - 1 over the prompt keys of cache row g, read once per (group, head)
+                AttnFanoutArgs fa{v.qkv_dec, da.k, da.v, v.attn_dec, nrows / v.fan_n, c.heads, m->hd, v.capS, v.fan_n, v.capR, v.rows + RS_POS,
+                                  RS_STRIDE, v.fan_P, nullptr, m->rope_cos, m->rope_sin, da.scale, v.es == 1 ? 3 : 0};
+                launch_attention_fanout(fa, v.st);
+            } else {
+                launch_attention_decode_fused(da, v.st);
+            }
             if (hooks && m->attn_out) {
                 m->attn_q.ensure((size_t)nrows * c.hidden * 4);
                 launch_rope_q_decode(v.qkv_dec, v.split_G != 0, m->attn_q.as<float>(), nrows, c.heads, m->hd, hook_pos, m->rope_cos,
@@ -923,8 +929,10 @@ uint32_t mix_seed(uint64_t seed, uint32_t row, uint32_t salt) {
 }
 
 // records of the B rows of one request (row b of the request = record b); `tail` = last prompt ids per row, right-aligned
-void fill_rows(int* rec, int B, const GenParams& g, int pos, const int* tail /*[B][VC_MAX_STOP_LEN-1] or null*/, int out_off0,
-               int out_stride) {
+// fan > 1 (a served vc_request_fanout): B = prompts x fan rows; row b continues prompt b / fan — its stop-sequence tail and its
+// processor history are that prompt's, its seed and its out_ids slot its own
+void fill_rows(int* rec, int B, const GenParams& g, int pos, const int* tail /*[B / fan][VC_MAX_STOP_LEN-1] or null*/, int out_off0,
+               int out_stride, int fan = 1) {
     memset(rec, 0, (size_t)B * RS_STRIDE * sizeof(int));
     const float inv_t = 1.0f / g.temperature;
     for (int b = 0; b < B; ++b) {
@@ -942,14 +950,14 @@ void fill_rows(int* rec, int B, const GenParams& g, int pos, const int* tail /*[
         r[RS_SEED_LO] = (int)mix_seed(g.seed, (uint32_t)b, 0x51u);  // per-row streams: independent of the row's slot
         r[RS_SEED_HI] = (int)mix_seed(g.seed, (uint32_t)b, 0xA7u);
         r[RS_OUT_OFF] = out_off0 + b * out_stride;
-        for (int j = 0; j < VC_MAX_STOP_LEN - 1; ++j) r[RS_TAIL + j] = tail ? tail[b * (VC_MAX_STOP_LEN - 1) + j] : INT32_MIN;
+        for (int j = 0; j < VC_MAX_STOP_LEN - 1; ++j) r[RS_TAIL + j] = tail ? tail[(b / fan) * (VC_MAX_STOP_LEN - 1) + j] : INT32_MIN;
         for (int q = 0; q < g.n_stop; ++q)
             for (int j = 0; j < 1 + VC_MAX_STOP_LEN; ++j) r[RS_STOP + q * (1 + VC_MAX_STOP_LEN) + j] = g.stop[q][j];
         if (g.proc) {
             memcpy(&r[RS_LP_PENALTY], &g.proc_penalty, 4);
             r[RS_LP_NGRAM] = g.proc_ngram;
             r[RS_LP_MINNEW] = g.proc_minnew;
-            r[RS_LP_HIST_OFF] = b * g.proc_T;
+            r[RS_LP_HIST_OFF] = (b / fan) * g.proc_T;
             r[RS_LP_HIST_LEN] = g.proc_T;
             r[RS_LP_NBAD] = g.proc_nbad;
             r[RS_LP_NEOS] = g.proc_neos;
@@ -1100,7 +1108,7 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
         // reserve_new >= 0: required (generate) — exceeding max_position_embeddings is an error
         int want = (int)S + std::max(reserve_new < 0 ? -reserve_new : reserve_new, 1);
         if (reserve_new < 0) want = std::max((int)S + 1, std::min(want, c.max_positions / 64 * 64));
-        if (own_kv) ensure_llm(m, B, want);
+        if (own_kv) ensure_llm(m, std::max(B, m->fan_rows), want);   // a served fan-out call: the cache and the loop of B n rows
         else ensure_prefill_ws(m, B, (int)rup(S, 64));
     }
     std::vector<int> flat((size_t)B * S * 2);
@@ -1334,16 +1342,18 @@ void finish_prefill(vc_model* m, const KvTarget& kv, float* logits_all_host) {
     m->attn_out = nullptr;
 }
 
-// arm the session's own loop for the B rows just prefilled: every row at position S, step 0
-void arm_session_rows(vc_model* m, const GenParams& g, const int* tail) {
-    const int B = m->curB, S = m->curS;
+// arm the session's own loop for the B rows just prefilled (fan > 1: the B x fan rows that continue them): every row at position S,
+// step 0
+void arm_session_rows(vc_model* m, const GenParams& g, const int* tail, int fan = 1) {
+    const int B = m->curB * fan, S = m->curS;
     std::vector<int> rec((size_t)B * RS_STRIDE);
-    fill_rows(rec.data(), B, g, S, tail, 0, m->out_stride);
+    fill_rows(rec.data(), B, g, S, tail, 0, m->out_stride, fan);
     HIPCHK(hipMemsetAsync(m->rows.p, 0, m->rows.cap, m->st));
     HIPCHK(hipMemcpyAsync(m->rows.p, rec.data(), rec.size() * 4, hipMemcpyHostToDevice, m->st));
     HIPCHK(hipStreamSynchronize(m->st));
     m->cur_pos = S;
     m->spec_closed = false;
+    m->fan_closed = false;
     m->tok_stale = false;
 }
 

@@ -605,17 +605,25 @@ bool spec_request_served(const vc_model* m, const GenParams& g, int B) {
 }
 
 // generate() on the session's own loop: prefill, then max_new - 1 graph-replayed (strict: eagerly enqueued) decode steps — or, with a
-// served speculation request, verify steps until every row is finished or full
+// served speculation request, verify steps until every row is finished or full.
+// fan > 1 (a served vc_request_fanout): the B prompts are prefilled once, into rows 0 .. B - 1 of a cache of R = B fan rows; the loop
+// runs over the R rows b fan + j, whose step 0 reads prompt b's logits row and whose steps attend with the fan-out kernel — prompt
+// keys from cache row b, own keys from cache row b fan + j (positions >= S: the two regions of a cache row never overlap).  ids,
+// log-probs and the callback's columns are R rows wide; the session's loop is closed behind the call.
 void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
                          int on_dev, const GenParams& g, const std::vector<int>& tail, vc_token_cb cb, void* cb_user,
-                         int cb_every, int32_t* out_ids, int* n_generated) {
+                         int cb_every, int32_t* out_ids, int* n_generated, int fan = 1) {
     const int max_new = g.max_new;
+    const int R = B * fan;   // rows of the loop
     m->spec_closed = false;
+    m->fan_closed = false;
+    m->fan_rows = fan > 1 ? R : 0;   // the prefill sizes the cache and the loop's buffers for R rows
     std::unique_lock<std::mutex> gate = prefill_on_session(m, ids, B, T, img, seg, depth, on_dev, max_new);
-    ensure_out_ids(m, B, max_new);
+    m->fan_rows = 0;
+    ensure_out_ids(m, R, max_new);
     // vc_request_speculation: served when the call's form allows (spec_request_served) and the score rows of Q queries over this
     // cache fit a CU's LDS.  (A row drafts no further than its last slot, so the prefill's reserve of max_new positions holds.)
-    const int Q = spec_request_served(m, g, B) ? m->spec_k + 1 : 0;
+    const int Q = fan == 1 && spec_request_served(m, g, B) ? m->spec_k + 1 : 0;
     const bool spec = Q > 0 && (m->hd == 128 || m->hd == 64) && (m->kv_es == 2 || m->kv_es == 1) &&
                       attention_verify_lds_bytes(Q, m->hd, m->kv_es == 1, m->capS) <= ATTN_VERIFY_LDS_MAX;
     // the steps of this call: the session's plain view, plus what the call asked for — the view goes to the step-0 selection, to the
@@ -625,7 +633,7 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     const bool want_lp = m->glp_tok != nullptr;
     const int K = m->glp_k;
     if (want_lp) {
-        ensure_logprob_slabs(m, B, K);
+        ensure_logprob_slabs(m, R, K);
         v.lp_tok = m->lp_tok.as<float>();
         v.lp_top = m->lp_top.as<float>();
         v.lp_ids = m->lp_ids.as<int>();
@@ -639,7 +647,7 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     // prompt ids (as int32, placeholders and all) and the bad-word table
     std::vector<int> ids32;
     if (g.proc) {
-        ensure_processor_buffers(m, B, T);
+        ensure_processor_buffers(m, R, T);
         ids32.resize((size_t)B * T);
         for (size_t i = 0; i < ids32.size(); ++i) ids32[i] = (int)std::max<int64_t>(std::min<int64_t>(ids[i], INT32_MAX), INT32_MIN);
         HIPCHK(hipMemcpyAsync(m->proc_prompt.p, ids32.data(), ids32.size() * 4, hipMemcpyHostToDevice, m->st));
@@ -649,31 +657,55 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
         v.proc_bad = m->proc_bad.as<int>();
         v.proc_logits = m->proc_logits.as<float>();
     }
-    arm_session_rows(m, g, tail.data());
+    // the stop-sequence tails of the loop's rows on the host (row r: prompt r / fan)
+    std::vector<int> tail_rows;
+    if (fan > 1) {
+        constexpr int TL = VC_MAX_STOP_LEN - 1;
+        tail_rows.resize((size_t)R * TL);
+        for (int r = 0; r < R; ++r) std::copy(tail.begin() + (size_t)(r / fan) * TL, tail.begin() + (size_t)(r / fan + 1) * TL, tail_rows.begin() + (size_t)r * TL);
+    }
+    const std::vector<int>& tails = fan > 1 ? tail_rows : tail;
+    std::vector<int> fan_len(VC_MAX_ROWS, m->last_S);   // every group's prompt length (lives until the synchronize below)
+    if (fan > 1) {
+        m->fan_P.ensure(fan_len.size() * 4);
+        HIPCHK(hipMemcpyAsync(m->fan_P.p, fan_len.data(), fan_len.size() * 4, hipMemcpyHostToDevice, m->st));
+        v.fan_n = fan;
+        v.fan_P = m->fan_P.as<int>();
+    }
+    arm_session_rows(m, g, tail.data(), fan);
     // token 0 comes from the prefill logits
-    std::vector<int> fill((size_t)B * m->out_stride, g.pad);
+    std::vector<int> fill((size_t)R * m->out_stride, g.pad);
     HIPCHK(hipMemcpyAsync(m->out_ids.p, fill.data(), fill.size() * 4, hipMemcpyHostToDevice, m->st));
-    enqueue_selection(m, v, v.logits, B, 1);   // step 0 -> 1; the position stays at S
+    if (fan > 1) {
+        // row r selects from prompt r / fan's logits row: the rows spread in place, last first (a source row r / fan <= r is only
+        // overwritten by the copy for row r / fan itself, which comes later)
+        const size_t rowb = (size_t)m->c.vocab * 4;
+        for (int r = R - 1; r >= 1; --r)
+            if (r / fan != r)
+                HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(v.logits) + r * rowb, reinterpret_cast<char*>(v.logits) + (r / fan) * rowb, rowb,
+                                      hipMemcpyDeviceToDevice, m->st));
+    }
+    enqueue_selection(m, v, v.logits, R, 1);   // step 0 -> 1; the position stays at S
     HIPCHK(hipStreamSynchronize(m->st));
     gate.unlock();
     int produced = 1, reported = 0;
     const bool can_finish = g.eos >= 0 || g.n_stop > 0;
-    std::vector<int> rec((size_t)B * RS_STRIDE), part;
+    std::vector<int> rec((size_t)R * RS_STRIDE), part;
     auto all_finished = [&]() {
         if (!can_finish) return false;
         HIPCHK(hipMemcpyAsync(rec.data(), m->rows.p, rec.size() * 4, hipMemcpyDeviceToHost, m->st));
         HIPCHK(hipStreamSynchronize(m->st));
-        for (int b = 0; b < B; ++b)
+        for (int b = 0; b < R; ++b)
             if (!rec[(size_t)b * RS_STRIDE + RS_FINISHED]) return false;
         return true;
     };
     auto report = [&](int upto) {  // streamer callback: columns [reported, upto) of every row
         if (!cb || upto <= reported) return;
-        part.resize((size_t)B * (upto - reported));
+        part.resize((size_t)R * (upto - reported));
         HIPCHK(hipMemcpy2DAsync(part.data(), (size_t)(upto - reported) * 4, m->out_ids.as<int>() + reported,
-                                (size_t)m->out_stride * 4, (size_t)(upto - reported) * 4, B, hipMemcpyDeviceToHost, m->st));
+                                (size_t)m->out_stride * 4, (size_t)(upto - reported) * 4, R, hipMemcpyDeviceToHost, m->st));
         HIPCHK(hipStreamSynchronize(m->st));
-        cb(cb_user, reported, upto - reported, B, part.data());
+        cb(cb_user, reported, upto - reported, R, part.data());
         reported = upto;
     };
     const int every = cb ? std::max(cb_every, 1) : 8;
@@ -734,7 +766,7 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
         m->cur_pos = -1;       // the rows stand at different positions: the session's loop is closed
         m->spec_closed = true;
     } else if (max_new > 1 && !all_finished()) {
-        const hipGraphExec_t exec = m->precision != 1 ? step_graph(m, want_lp || g.proc ? STEP_CALL : STEP_PLAIN, v, B) : nullptr;
+        const hipGraphExec_t exec = m->precision != 1 ? step_graph(m, fan > 1 ? STEP_FAN : (want_lp || g.proc ? STEP_CALL : STEP_PLAIN), v, R) : nullptr;
         for (int step = 1; step < max_new; ++step) {
             if (m->precision == 1) enqueue_decode_step_strict(m, v, B);
             else HIPCHK(hipGraphLaunch(exec, m->st));
@@ -752,24 +784,24 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
         }
     }
     if (m->ev[3]) HIPCHK(hipEventRecord(m->ev[3], m->st));
-    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, m->out_ids.p, (size_t)m->out_stride * 4, (size_t)max_new * 4, B,
+    HIPCHK(hipMemcpy2DAsync(out_ids, (size_t)max_new * 4, m->out_ids.p, (size_t)m->out_stride * 4, (size_t)max_new * 4, R,
                             hipMemcpyDeviceToHost, m->st));
     if (want_lp) {   // the slabs come back once, beside out_ids
-        HIPCHK(hipMemcpy2DAsync(m->glp_tok, (size_t)max_new * 4, m->lp_tok.p, (size_t)m->out_stride * 4, (size_t)max_new * 4, B,
+        HIPCHK(hipMemcpy2DAsync(m->glp_tok, (size_t)max_new * 4, m->lp_tok.p, (size_t)m->out_stride * 4, (size_t)max_new * 4, R,
                                 hipMemcpyDeviceToHost, m->st));
         if (K > 0) {
             HIPCHK(hipMemcpy2DAsync(m->glp_top, (size_t)max_new * K * 4, m->lp_top.p, (size_t)m->out_stride * K * 4,
-                                    (size_t)max_new * K * 4, B, hipMemcpyDeviceToHost, m->st));
+                                    (size_t)max_new * K * 4, R, hipMemcpyDeviceToHost, m->st));
             HIPCHK(hipMemcpy2DAsync(m->glp_ids, (size_t)max_new * K * 4, m->lp_ids.p, (size_t)m->out_stride * K * 4,
-                                    (size_t)max_new * K * 4, B, hipMemcpyDeviceToHost, m->st));
+                                    (size_t)max_new * K * 4, R, hipMemcpyDeviceToHost, m->st));
         }
     }
     HIPCHK(hipStreamSynchronize(m->st));
     if (want_lp) {
         // a row's finishing token (its EOS, or the token completing a stop sequence) is scored; behind it the row emitted pad: those
         // positions, and the columns the loop never reached, hold 0.0 / 0.0 / -1
-        for (int b = 0; b < B; ++b) {
-            const int e = row_finish_end(g, out_ids + (size_t)b * max_new, tail.data() + (size_t)b * (VC_MAX_STOP_LEN - 1), produced);
+        for (int b = 0; b < R; ++b) {
+            const int e = row_finish_end(g, out_ids + (size_t)b * max_new, tails.data() + (size_t)b * (VC_MAX_STOP_LEN - 1), produced);
             for (int s_ = e; s_ < max_new; ++s_) {
                 const size_t i = (size_t)b * max_new + s_;
                 m->glp_tok[i] = 0.f;
@@ -780,8 +812,12 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
             }
         }
     }
-    produced = trim_columns(g, out_ids, max_new, tail.data(), B, produced);
+    produced = trim_columns(g, out_ids, max_new, tails.data(), R, produced);
     if (cb) report(produced);
+    if (fan > 1) {
+        m->cur_pos = -1;       // cache row r holds prompt r's keys and sequence r's own: the session's loop is closed
+        m->fan_closed = true;
+    }
     if (n_generated) *n_generated = produced;
     read_phase_times(m, m->ev[2], m->ev[3]);
 }
@@ -994,6 +1030,108 @@ void generate_beam_on_session(vc_model* m, const int64_t* ids, int B, int T, con
     read_phase_times(m, m->ev[2], m->ev[3]);
 }
 
+// Whether one prefill of a prompt yields the bits every one of its `fan` copies gets in the repeated call — what the fan-out form rests
+// on, since the repeated call defines the result.  The prefill's rows are independent of what shares their launch except in the GEMMs'
+// split-K remainder round (attach_splitk_ws: its k-slices depend on the tile a row falls into, so identical prompts of one batch may
+// even differ among themselves).  True in the batch-invariant mode, which has no such round, and when no GEMM of the REPEATED call's
+// encode + prefill can have more than one round of 256 x 256 tiles: then none gets the workspace either.  The spliced length is not
+// known yet: the rows are bounded as generate_on_pool bounds them, and the widest GEMM is paired with the longest.
+bool fanout_prefill_bits_shared(const vc_model* m, int B, int T, int fan) {
+    if (batch_invariant(m)) return true;
+    const vc_model_cfg& c = m->c;
+    long images = 0, per_sample = 3;
+    for (int k = 0; k < 3; ++k) {
+        const std::vector<int>& cnt = m->img_counts[k];
+        long n_k = B;
+        if ((int)cnt.size() == B) {
+            n_k = 0;
+            for (int b = 0; b < B; ++b) n_k += cnt[b];
+        }
+        images += n_k;
+    }
+    for (int b = 0; b < B; ++b) {
+        long n_b = 0;
+        for (int k = 0; k < 3; ++k) n_b += (int)m->img_counts[k].size() == B ? m->img_counts[k][b] : 1;
+        per_sample = std::max(per_sample, n_b);
+    }
+    const long S_bound = std::min<long>(c.max_positions, T + per_sample * m->Tv);
+    const long rows = std::max<long>((long)B * fan * (long)rup((size_t)S_bound, 32), images * fan * m->Tv);
+    const long wide = std::max({3L * c.hidden, 2L * c.ffn, 3L * c.vit_hidden, (long)c.vit_ffn});
+    return ((rows + 255) / 256) * ((wide + 255) / 256) <= 256;
+}
+
+// a fan-out request that is not served: the call's inputs with every prompt repeated fan times (HF's _expand_inputs_for_generation)
+struct FanExpanded {
+    std::vector<int64_t> ids;
+    std::vector<float> host_px[3];
+    const float* px[3] = {nullptr, nullptr, nullptr};
+    std::vector<int> tail;
+};
+FanExpanded expand_for_fanout(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
+                              int on_dev, int fan, const std::vector<int>& tail) {
+    FanExpanded x;
+    const int R = B * fan;
+    constexpr int TL = VC_MAX_STOP_LEN - 1;
+    x.ids.resize((size_t)R * T);
+    x.tail.resize((size_t)R * TL);
+    for (int r = 0; r < R; ++r) {
+        std::copy(ids + (size_t)(r / fan) * T, ids + (size_t)(r / fan + 1) * T, x.ids.begin() + (size_t)r * T);
+        std::copy(tail.begin() + (size_t)(r / fan) * TL, tail.begin() + (size_t)(r / fan + 1) * TL, x.tail.begin() + (size_t)r * TL);
+    }
+    const size_t img_elems = (size_t)3 * m->c.vit_image * m->c.vit_image;
+    const float* src[3] = {img, seg, depth};
+    for (int k = 0; k < 3; ++k) {
+        if (!src[k]) continue;
+        std::vector<int>& cnt = m->img_counts[k];
+        REQUIRE(cnt.empty() || (int)cnt.size() == B, VC_ERR_INVALID, "image counts given for %zu samples, batch is %d", cnt.size(), B);
+        std::vector<size_t> first(B + 1, 0);   // first image of every sample
+        for (int b = 0; b < B; ++b) first[b + 1] = first[b] + (cnt.empty() ? 1 : cnt[b]);
+        const size_t total = first[B] * fan * img_elems;
+        float* dst = nullptr;
+        if (on_dev) {
+            m->fan_px[k].ensure(std::max<size_t>(total, 1) * 4);
+            dst = m->fan_px[k].as<float>();
+        } else {
+            x.host_px[k].resize(total);
+            dst = x.host_px[k].data();
+        }
+        size_t at = 0;
+        for (int r = 0; r < R; ++r) {
+            const int b = r / fan;
+            const size_t n = (first[b + 1] - first[b]) * img_elems;
+            if (on_dev) HIPCHK(hipMemcpyAsync(dst + at, src[k] + first[b] * img_elems, n * 4, hipMemcpyDeviceToDevice, m->st));
+            else std::copy(src[k] + first[b] * img_elems, src[k] + first[b] * img_elems + n, dst + at);
+            at += n;
+        }
+        x.px[k] = dst;
+        if (!cnt.empty()) {
+            std::vector<int> c2((size_t)R);
+            for (int r = 0; r < R; ++r) c2[r] = cnt[r / fan];
+            cnt.swap(c2);
+        }
+    }
+    if (on_dev) HIPCHK(hipStreamSynchronize(m->st));
+    if (!m->mask_next.empty()) {
+        REQUIRE(m->mask_B == B && m->mask_T == T, VC_ERR_INVALID, "attention_mask is [%d, %d], input_ids [%d, %d]", m->mask_B, m->mask_T, B, T);
+        std::vector<uint8_t> mk((size_t)R * T);
+        for (int r = 0; r < R; ++r) std::copy(m->mask_next.begin() + (size_t)(r / fan) * T, m->mask_next.begin() + (size_t)(r / fan + 1) * T, mk.begin() + (size_t)r * T);
+        m->mask_next.swap(mk);
+        m->mask_B = R;
+    }
+    if (m->spec_k > 0 && !m->spec_lookup.empty()) {
+        const size_t st = (size_t)std::max(m->spec_lookup_stride, 1);
+        std::vector<int> lk((size_t)R * st), ln((size_t)R);
+        for (int r = 0; r < R; ++r) {
+            std::copy(m->spec_lookup.begin() + (size_t)(r / fan) * st, m->spec_lookup.begin() + (size_t)(r / fan + 1) * st, lk.begin() + (size_t)r * st);
+            ln[r] = m->spec_lookup_len[r / fan];
+        }
+        m->spec_lookup.swap(lk);
+        m->spec_lookup_len.swap(ln);
+        m->spec_B = R;
+    }
+    return x;
+}
+
 }  // namespace
 
 /* generate(): encode + splice + prefill + (max_new - 1) decode steps with the token selection on the device — greedy
@@ -1008,6 +1146,11 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
     GUARD_BEGIN
     USE_DEVICE(m->ctx);
     REQUIRE(max_new >= 1 && out_ids, VC_ERR_INVALID, "bad max_new/out_ids");
+    // vc_request_fanout: n rows per prompt, out_ids / the log-prob buffers / the callback's columns B n rows wide
+    const int fan = m->fan_n > 1 ? m->fan_n : 1;
+    m->fan_last = false;
+    REQUIRE(B >= 1 && (long long)B * fan <= VC_MAX_ROWS, VC_ERR_INVALID,
+            "batch %d x num_return_sequences %d exceeds the %d rows a replica decodes at a time", B, fan, VC_MAX_ROWS);
     REQUIRE(n_stop >= 0 && n_stop <= VC_MAX_STOP && (n_stop == 0 || (stop_ids && stop_lens)), VC_ERR_INVALID,
             "at most %d stop sequences", VC_MAX_STOP);
     // finished rows are fed the pad token's embedding: it must be a real row of embed_tokens
@@ -1042,8 +1185,8 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
     // loop); strict mode keeps fp32 caches of its own
     static const bool use_pool = !(getenv("VC_POOL") && atoi(getenv("VC_POOL")) == 0);
     // vc_request_generate_logprobs: the call runs on the session's own loop, whose steps carry the log-prob launch
-    REQUIRE(!m->glp_tok || m->glp_cap >= (size_t)B * max_new, VC_ERR_INVALID,
-            "log-prob buffers hold %zu rows, the call yields [%d, %d]", m->glp_cap, B, max_new);
+    REQUIRE(!m->glp_tok || m->glp_cap >= (size_t)B * fan * max_new, VC_ERR_INVALID,
+            "log-prob buffers hold %zu rows, the call yields [%d, %d]", m->glp_cap, B * fan, max_new);
     // vc_request_logits_processors: likewise (the pool's steps carry no processor launch)
     if (m->gproc) {
         REQUIRE(m->gproc_bad.size() == (size_t)VC_MAX_BAD_WORDS * (1 + VC_MAX_BAD_WORD_LEN), VC_ERR_STATE, "bad-word table of %zu ints",
@@ -1061,7 +1204,34 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
     REQUIRE(m->spec_k == 0 || m->spec_lookup.empty() || m->spec_B == B, VC_ERR_INVALID, "lookup ids given for %d sequences, batch is %d",
             m->spec_B, B);
     m->spec_last = false;
-    if (use_pool && m->precision != 1 && !m->glp_tok && !g.proc && !spec_request_served(m, g, B))
+    if (fan > 1) {
+        // served: the bf16 step over a bf16 or e4m3 cache, head dim 128 or 64, up to 8 rows per prompt, n score rows over the
+        // longest cache this model can ask for within a CU's LDS (the capacity itself is known behind the prefill only), and a
+        // prefill whose bits do not depend on the rows that share its launch (else no shared prefix equals the repeated call)
+        const int es = m->precision == 0 ? step_kv_es(m) : 0;
+        const bool served = m->fan_share && m->precision == 0 && (m->hd == 128 || m->hd == 64) && (es == 2 || es == 1) && fan <= 8 &&
+                            attention_fanout_lds_bytes(fan, m->hd, es == 1, m->c.max_positions / 64 * 64) <= ATTN_VERIFY_LDS_MAX &&
+                            fanout_prefill_bits_shared(m, B, T, fan);
+        m->fan_last = true;
+        m->fan_last_n = fan;
+        m->fan_last_shared = served;
+        m->fan_last_B = served ? B : B * fan;
+        if (served) {
+            generate_on_session(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids, n_generated, fan);
+        } else {
+            // not served: the replicated call, which defines the result — every prompt's ids, images, image counts, mask row,
+            // lookup ids and stop tail fan times (rows b fan + j), then the existing path over B fan rows
+            FanExpanded x = expand_for_fanout(m, ids, B, T, img, seg, depth, pixels_on_device, fan, tail);
+            g.proc_T = T;
+            const int R = B * fan;
+            if (use_pool && m->precision != 1 && !m->glp_tok && !g.proc && !spec_request_served(m, g, R))
+                generate_on_pool(m, x.ids.data(), R, T, x.px[0], x.px[1], x.px[2], pixels_on_device, g, x.tail, cb, cb_user, cb_every, out_ids,
+                                 n_generated);
+            else
+                generate_on_session(m, x.ids.data(), R, T, x.px[0], x.px[1], x.px[2], pixels_on_device, g, x.tail, cb, cb_user, cb_every,
+                                    out_ids, n_generated);
+        }
+    } else if (use_pool && m->precision != 1 && !m->glp_tok && !g.proc && !spec_request_served(m, g, B))
         generate_on_pool(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids, n_generated);
     else
         generate_on_session(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids,

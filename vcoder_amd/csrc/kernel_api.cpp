@@ -85,6 +85,15 @@ VCK_EXPORT int vck_attention_verify(const uint16_t* qkv, void* k, void* v, uint1
     launch_attention_verify(a, S(stream));
     return 0;
 }
+VCK_EXPORT int vck_attention_fanout(const uint16_t* qkv, void* k, void* v, uint16_t* out, int G, int H, int hd, int kv_stride, int n,
+                                    int cache_rows, const int* pos_rows, int pos_stride, const int* prefix_len, const int* prefix_row,
+                                    const float* rope_cos, const float* rope_sin, float scale, int kv8, void* stream) {
+    if (n < 1 || n > 8 || (hd != 128 && hd != 64) || attention_fanout_lds_bytes(n, hd, kv8, kv_stride) > ATTN_VERIFY_LDS_MAX) return -1;
+    AttnFanoutArgs a{qkv, k, v, out, G, H, hd, kv_stride, n, cache_rows, pos_rows, pos_stride, prefix_len, prefix_row, rope_cos, rope_sin,
+                     scale, kv8};
+    launch_attention_fanout(a, S(stream));
+    return 0;
+}
 VCK_EXPORT void vck_select_embed(const float* logits, int ldl, int* rows, int* next_tok, int* out_ids, const uint16_t* embed,
                                  float* x, float* ssq, const float* xg_w, uint16_t* xg, int D, int npart, int V, int nrows,
                                  int advance, void* stream) {

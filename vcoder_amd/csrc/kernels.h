@@ -357,6 +357,30 @@ constexpr size_t ATTN_VERIFY_LDS_MAX = 160 * 1024;
 size_t attention_verify_lds_bytes(int Q, int hd, int kv8, int kv_stride);
 void launch_attention_verify(const AttnVerifyArgs& a, hipStream_t s);
 
+// fan-out attention (generate(num_return_sequences = n)): the n <= 8 rows g n .. g n + n - 1 of group g continue one prompt of
+// P_dev[g] keys held in positions [0, P) of cache row prefix_row_dev[g]; row r appends at, and reads its keys P .. pos from, cache row
+// r.  All rows of a group stand at pos_dev[g n * pos_stride] >= P.  Row r's output and appended cache rows are the bits
+// launch_attention_decode_fused gives it over a cache row holding prefix + own tail (attn.hip attention_fanout_kernel; an
+// exactly-zero output may differ in sign).  A group whose P, position or rows do not fit the cache is left untouched.  No key mask.
+struct AttnFanoutArgs {
+    const bf16_t* qkv;   // [G * n, 3*H*hd]
+    void* k;             // [cache_rows,H,kv_stride,hd]   (position pos of rows g n .. g n + n - 1 is written)
+    void* v;
+    bf16_t* out;         // [G * n, H*hd]
+    int G, H, hd, kv_stride, n, cache_rows;
+    const int* pos_dev;  // group g reads pos_dev[g * n * pos_stride]
+    int pos_stride;
+    const int* P_dev;            // [G] prefix lengths
+    const int* prefix_row_dev;   // [G] cache row of the group's prefix, or nullptr: row g
+    const float* rope_cos;
+    const float* rope_sin;
+    float scale;
+    int kv8;
+};
+// LDS of one workgroup (the verify attention's with Q = n); refused above ATTN_VERIFY_LDS_MAX — callers ask first
+size_t attention_fanout_lds_bytes(int n, int hd, int kv8, int kv_stride);
+void launch_attention_fanout(const AttnFanoutArgs& a, hipStream_t s);
+
 // ---- splice / embedding (K10) ------------------------------------------------------------------
 // per destination row r of inputs_embeds [B*S, D]: row_src[2r] = kind (0 = token id -> embed_tokens row,
 // 1 = row of the projected feature buffer, 2 = zero padding row), row_src[2r+1] = token id / feature row.

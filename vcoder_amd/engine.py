@@ -588,7 +588,7 @@ class HipEngine:
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                  on_tokens=None, stream_every: int = 1, attention_mask=None, logprobs: bool = False,
                  top_logprobs: int = 0, processors=None, eos_extra: Sequence[int] = (), speculate: Optional[int] = None,
-                 lookup_ngram: int = 2, lookup_ids=None) -> np.ndarray:
+                 lookup_ngram: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False) -> np.ndarray:
         """generate() on the device (vc_generate): greedy, or temperature / top-k / top-p sampling with a counter-based
         generator (same seed -> same tokens).  on_tokens(first_step, ids [B, n]) is called with every `stream_every` new
         columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32.
@@ -608,10 +608,24 @@ class HipEngine:
         steps.  lookup_ids: per sequence (a list of B id lists, or one list for B = 1) what the answer is expected to resemble.
         last_speculation = {"steps", "tokens", "drafted", "accepted"} per-row int arrays, or None when the request was not served:
         sampling, processors, precision split / strict, B * (k + 1) > 32, a cache too long for the verify attention's LDS score
-        rows (the call then runs as without it).  ValueError for k or lookup_ngram outside their range."""
+        rows (the call then runs as without it).  ValueError for k or lookup_ngram outside their range.
+        num_return_sequences = n (vc_request_fanout): n sequences per prompt -> [B n, n_generated], rows b n + j, log-probs and
+        on_tokens columns B n rows wide — bit for bit the call on the prompts repeated n times (np.repeat(.., n, axis=0)) with the
+        same seed.  By default the engine repeats the prompts itself.
+        fan_out=True: the B prompts are encoded and prefilled once and every decode step reads a prompt's keys and values once for
+        its n rows (the fan-out attention), when the engine serves that: the bf16 precision mode, 2 <= n <= 8, and a prefill whose
+        bits do not depend on the rows sharing its launch (at 7b dims: set_batch_invariant(True); the tiny models always).  Measured at 7b it
+        wins for B = 2, n = 8 and loses for B = 1 (profiles/fanout_wall_times.md), hence not the default.  last_fanout = {"n",
+        "shared", "prefill_rows"} of the call (None without n > 1).  B n above MAX_BATCH: ValueError."""
         ids = self._ids(input_ids)
         B, T = ids.shape
         self.last_speculation = None
+        self.last_fanout = None
+        nret = int(num_return_sequences)
+        if nret < 1:
+            raise ValueError(f"num_return_sequences must be at least 1, got {num_return_sequences!r}")
+        if nret > 1 and B * nret > self.MAX_BATCH:
+            raise ValueError(f"batch {B} x num_return_sequences {nret} exceeds the {self.MAX_BATCH} rows a replica decodes at a time")
         look = None
         if speculate is not None:
             k, ng = int(speculate), int(lookup_ngram)
@@ -661,7 +675,8 @@ class HipEngine:
                                                     for i, fill in enumerate((0.0, 0.0, -1)))
             return np.concatenate([np.pad(p, ((0, 0), (0, n - p.shape[1])), constant_values=pad) for p in parts], axis=0)
         (pi, ps, pd), on_dev, keep = self._pixels(*self._image_blocks(B, images, segs, depths))
-        out = np.empty((B, max_new_tokens), dtype=np.int32)
+        R = B * nret   # rows the call returns
+        out = np.empty((R, max_new_tokens), dtype=np.int32)
         n = C.c_int(0)
         eos = -1 if eos_token_id is None else int(eos_token_id)
         stops = [list(map(int, q)) for q in (stop_sequences or [])]
@@ -685,7 +700,7 @@ class HipEngine:
         self._announce_mask(attention_mask, B, T)
         tok_lp = top_lp = top_id = None
         if want_lp:
-            rows = B * int(max_new_tokens)
+            rows = R * int(max_new_tokens)
             tok_lp = np.zeros((rows,), dtype=np.float32)
             top_lp = np.zeros((rows * K,), dtype=np.float32)
             top_id = np.full((rows * K,), -1, dtype=np.int32)
@@ -725,6 +740,15 @@ class HipEngine:
                 self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
                 self.lib.vc_request_logits_processors(self._model, None)
                 raise
+        if nret > 1:
+            try:
+                self._check(self.lib.vc_request_fanout(self._model, nret if fan_out else -nret))   # (-n: the engine repeats the prompts)
+            except BaseException:
+                self.lib.vc_clear_attention_mask(self._model)
+                self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
+                self.lib.vc_request_logits_processors(self._model, None)
+                self.lib.vc_request_speculation(self._model, 0, 0, None, None, 0)
+                raise
         self._check(self.lib.vc_generate(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev,
                                          int(max_new_tokens), eos, pad,
                                          flat.ctypes.data_as(C.c_void_p) if stops else None,
@@ -733,15 +757,19 @@ class HipEngine:
                                          out.ctypes.data_as(C.c_void_p), C.byref(n)))
         if errs:
             raise errs[0]
-        self._cur_batch = B
+        self._cur_batch = R
+        if nret > 1:
+            lf = np.zeros((3,), dtype=np.int32)
+            if self.lib.vc_last_fanout(self._model, lf.ctypes.data_as(C.c_void_p)) == 0:
+                self.last_fanout = {"n": int(lf[0]), "shared": bool(lf[1]), "prefill_rows": int(lf[2])}
         if speculate is not None:
-            cnt = np.zeros((B, 4), dtype=np.int32)
-            if self.lib.vc_last_speculation(self._model, cnt.ctypes.data_as(C.c_void_p), B) == 0:
+            cnt = np.zeros((R, 4), dtype=np.int32)
+            if self.lib.vc_last_speculation(self._model, cnt.ctypes.data_as(C.c_void_p), R) == 0:
                 self.last_speculation = {name: cnt[:, i].copy() for i, name in enumerate(("steps", "tokens", "drafted", "accepted"))}
         if want_lp:
             mn = int(max_new_tokens)
-            self.last_generate_logprobs = (tok_lp.reshape(B, mn)[:, : n.value].copy(), top_lp.reshape(B, mn, K)[:, : n.value].copy(),
-                                           top_id.reshape(B, mn, K)[:, : n.value].copy())
+            self.last_generate_logprobs = (tok_lp.reshape(R, mn)[:, : n.value].copy(), top_lp.reshape(R, mn, K)[:, : n.value].copy(),
+                                           top_id.reshape(R, mn, K)[:, : n.value].copy())
         return out[:, : n.value].copy()
 
     def generate_beam(self, input_ids, images, segs=None, depths=None, num_beams: int = 2, max_new_tokens: int = 128,
@@ -776,6 +804,7 @@ class HipEngine:
 
     last_beam_steps = 0
     last_speculation = None
+    last_fanout = None       # {"n", "shared", "prefill_rows"} of the last generate(num_return_sequences > 1), else None
 
     # bookkeeping used by decode_step
     def note_prefill(self, B: int):

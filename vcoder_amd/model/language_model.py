@@ -454,7 +454,7 @@ class _HipCausalLMBase:
                  output_logprobs: bool = False, top_logprobs: int = 0, repetition_penalty: Optional[float] = None,
                  no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
                  bad_words_ids=None, processors_on_device: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
-                 max_matching_ngram_size: int = 2, lookup_ids=None, **kwargs):
+                 max_matching_ngram_size: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False, **kwargs):
         """Returns cat(input_ids, new_ids) [B, T+n] int64 — the prompt part keeps its negative placeholder ids,
         callers slice `[:, T:]` (serve/cli.py:135).
 
@@ -502,6 +502,20 @@ class _HipCausalLMBase:
         pool, and closes it: decode_step / extend behind it refuse until the next prefill.  k or the n-gram size outside their
         range raise ValueError before the engine is touched.
 
+        num_return_sequences = n (HF 4.31's semantics): with do_sample=True `sequences` is [B n, T + L], rows b n + j, each carrying
+        its prompt's input_ids; every GenerateOutput field is B n rows wide and the streamer receives B n-wide columns.  The result
+        is exactly (array_equal) that of the call on input_ids.repeat_interleave(n, 0) with the images repeated and the same seed.
+        By default the engine repeats the prompts itself.  fan_out=True: the B prompts are encoded and prefilled ONCE and each
+        decode step reads a prompt's keys and values once for its n rows (the fan-out attention; engine.last_fanout["shared"]);
+        that form is served for 2 <= n <= 8 in the bf16 precision mode, runs on the session's own loop and closes it (decode_step /
+        extend refuse until the next prefill); otherwise — precision "split" / "strict", n > 8 — the prompts are repeated as by
+        default.  It is not the default because at 7b it is faster only for B = 2, n = 8 of the shapes measured
+        (profiles/fanout_wall_times.md); at 7b dims it is served only under engine.set_batch_invariant(True), the mode in which one
+        prefill has the bits of each repeated copy.  The host loop (a stopping criterion that needs host code, processors_on_device=False)
+        expands its inputs n times as `_beam_search` does.  n > 1 without sampling and
+        num_beams == 1 raises HF's ValueError; with num_beams > 1 NotImplementedError (returning the n best beams is the beam
+        scorer's business); B n above 16 ValueError.  n == 1 (the default) is the call it always was.
+
         Everything the reference's callers ask for runs on the device inside the hipGraph-replayed decode loop
         (vc_generate): greedy argmax; sampling with HF's warper order temperature -> top-k -> top-p -> multinomial
         (`top_k` defaults to 50 when sampling, HF's GenerationConfig default, which is what serve/cli.py:122-132 gets);
@@ -532,7 +546,20 @@ class _HipCausalLMBase:
                 raise ValueError(f"prompt_lookup_num_tokens must be in 1 .. 7, got {prompt_lookup_num_tokens!r}")
             if not 1 <= int(max_matching_ngram_size) <= 4:
                 raise ValueError(f"max_matching_ngram_size must be in 1 .. 4, got {max_matching_ngram_size!r}")
+        nrs = int(num_return_sequences)
+        if nrs < 1:
+            raise ValueError(f"`num_return_sequences` has to be at least 1, got {num_return_sequences!r}")
+        if nrs > 1:
+            if num_beams != 1:
+                raise NotImplementedError("num_return_sequences > 1 is not implemented for num_beams > 1: returning the n best beams "
+                                          "is the beam scorer's business")
+            if not do_sample:
+                raise ValueError(f"`num_return_sequences` has to be 1, but is {nrs} when doing greedy search.")   # HF's own
+            if input_ids.shape[0] * nrs > self.engine.MAX_BATCH:
+                raise ValueError(f"batch {input_ids.shape[0]} x num_return_sequences {nrs} exceeds the {self.engine.MAX_BATCH} rows a "
+                                 "replica decodes at a time")
         self.engine.last_speculation = None
+        self.engine.last_fanout = None
         eos_all = self.config.eos_token_id if eos_token_id is None else eos_token_id
         eos_all = [int(e) for e in (eos_all if isinstance(eos_all, (list, tuple)) else ([] if eos_all is None else [eos_all]))]
         proc = _lp.make(repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, bad_words_ids, eos_all)
@@ -597,6 +624,26 @@ class _HipCausalLMBase:
         on_device = stops is not None and len(stops) <= 8
         if proc is not None:   # what the device kernel does not hold, or the caller's wish: the host loop applies them
             on_device = on_device and bool(processors_on_device) and proc.fits_device() and len(eos_more) <= _lp.MAX_EOS_EXTRA
+        if nrs > 1:
+            rep = np.repeat(np.arange(B), nrs)   # rows b n + j, as HF's _expand_inputs_for_generation
+
+            def expand(a):
+                if a is None:
+                    return None
+                if isinstance(a, (list, tuple)):
+                    return [a[i] for i in rep]
+                return a[torch.as_tensor(rep, device=a.device)] if hasattr(a, "detach") else np.asarray(a)[rep]
+
+            prompts = ids_cpu
+            ids_cpu = ids_cpu[torch.as_tensor(rep)]   # what the returned rows carry in front
+            if not on_device:   # the host loop runs over the expanded batch
+                images, segs, depths, attention_mask = expand(images), expand(segs), expand(depths), expand(attention_mask)
+                if lookup_ids is not None and not (B == 1 and all(np.ndim(q) == 0 for q in lookup_ids)):
+                    lookup_ids = expand(list(lookup_ids))
+                B = B * nrs
+                prompts = ids_cpu
+        else:
+            prompts = ids_cpu
         if streamer is not None:
             streamer.put(ids_cpu)
         if on_device:
@@ -605,7 +652,7 @@ class _HipCausalLMBase:
                 def on_tokens(first, new_ids):   # HF feeds the streamer one [B] tensor per step
                     for j in range(new_ids.shape[1]):
                         streamer.put(torch.from_numpy(new_ids[:, j].astype(np.int64)))
-            new = self.engine.generate(ids_cpu.numpy(), images, segs, depths, max_new_tokens=max_new_tokens,
+            new = self.engine.generate(prompts.numpy(), images, segs, depths, max_new_tokens=max_new_tokens,
                                        eos_token_id=eos, pad_token_id=pad, stop_sequences=stops or None,
                                        do_sample=bool(do_sample), temperature=float(temperature or 1.0),
                                        top_k=top_k or 0, top_p=1.0 if top_p is None else top_p, seed=seed or 0,
@@ -613,7 +660,8 @@ class _HipCausalLMBase:
                                        attention_mask=attention_mask, logprobs=want_lp, top_logprobs=K, processors=proc,
                                        eos_extra=eos_more if proc is not None else (),
                                        speculate=None if prompt_lookup_num_tokens is None else int(prompt_lookup_num_tokens),
-                                       lookup_ngram=int(max_matching_ngram_size), lookup_ids=lookup_ids)
+                                       lookup_ngram=int(max_matching_ngram_size), lookup_ids=lookup_ids,
+                                       **(dict(num_return_sequences=nrs, fan_out=bool(fan_out)) if nrs > 1 else {}))
             self._generation += 1
             out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
             if want_lp:
