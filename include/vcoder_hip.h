@@ -354,6 +354,16 @@ int vc_request_generate_logprobs(vc_model* m, int top_k, float* token_logprobs /
  * 0 .. max_position_embeddings or more than 16 sequences: VC_ERR_INVALID here, nothing changed; a B other than the call's makes that
  * call fail with VC_ERR_INVALID.  Cleared when that call returns, also when it fails; k == 0 cancels. */
 int vc_request_speculation(vc_model* m, int k, int max_ngram, const int32_t* lookup_ids, const int32_t* lookup_lens, int B);
+/* The selections the pending vc_request_speculation is served for (one-shot: it travels with that request, is cleared with it, and
+ * VC_ERR_STATE without one).  any == 0, the default: greedy calls without logits processors, as above.  any != 0: sampled calls
+ * (temperature / top-k / top-p, any seed) and calls with a vc_request_logits_processors set are served too, greedy ones through the
+ * same step.  The device sampler is a Gumbel-max keyed by (seed, generated index, vocabulary id): the verify step samples query row j
+ * with the key of the token it would become and accepts a draft while it equals the token sampled in front of it, and it processes
+ * row j over the row's history plus the j drafts in front of it — so ids, n_generated and log-probs (those of the raw rows) are
+ * still those of the same call, same seed, without the request: no acceptance probability is involved.  Opt-in because a served call
+ * leaves the decode pool and closes the session's loop, which a sampled caller has to ask for.  The other conditions stand: the bf16
+ * precision mode, B * (k + 1) <= 32, the LDS bound; vc_generate_beam and a served vc_request_fanout ignore the request. */
+int vc_request_speculation_selection(vc_model* m, int any);
 /* Per-sequence counters of the last vc_generate* call of this session: out[b] = {verify steps, tokens they emitted, drafts proposed,
  * drafts accepted}.  VC_ERR_STATE when that call did not speculate. */
 int vc_last_speculation(vc_model* m, int32_t* out /* [B][4] */, int B);

@@ -152,6 +152,18 @@ void vck_spec_draft(const int* rows, const int* out_ids, const int* lookup, cons
 void vck_spec_accept(const float* logits, int ldl, int V, int* rows, int* next_tok, int* out_ids, const int* tok, const int* nq, int B,
                      int Q, int* counters, const float* scratch_lp, const int* scratch_ids, int scratch_k, float* lp_tok, float* lp_top,
                      int* lp_ids, int lp_k, void* stream);
+/* vck_spec_accept with the rows' selections given: sel [B * Q] != NULL replaces the argmax (a_j = sel[b * Q + j]: what vck_spec_select
+ * chose under sampling or on processed rows); scratch_chosen [B * Q] != NULL is the log-prob lp_tok takes for a_j (a vck_topk_logprob
+ * with chosen = sel) instead of entry 0 of the scratch row.  Both NULL: vck_spec_accept. */
+void vck_spec_accept_sel(const float* logits, int ldl, int V, int* rows, int* next_tok, int* out_ids, const int* tok, const int* nq, int B,
+                         int Q, int* counters, const float* scratch_lp, const int* scratch_ids, int scratch_k, float* lp_tok, float* lp_top,
+                         int* lp_ids, int lp_k, const int* sel, const float* scratch_chosen, void* stream);
+/* the selections of a verify step: sel[b * Q + j] (j < nq[b]; other entries are not written) = what vck_select_embed would select from
+ * logits row b * Q + j under record b with word 2 of the record (the step, the sampler's key) raised by j — greedy argmax or
+ * temperature / top-k / top-p / Gumbel-max; no bookkeeping, the records are only read.  One workgroup per row, the rows side by side.
+ * lds_floats: -1 = the scaled row is staged in LDS when the device allows, 0 = never (every pass re-reads global memory). */
+void vck_spec_select(const float* logits, int ldl, int V, const int* rows, const int* nq, int* sel, int B, int Q, int lds_floats,
+                     void* stream);
 /* test hook of the sampler: u[i] = the uniform in (0,1) the Gumbel-max draw derives from 32-bit hash h[i] (strictly
  * inside the interval for EVERY h, so the Gumbel term -log(-log(u)) written to gumbel[i] is finite) */
 void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, void* stream);
@@ -209,6 +221,11 @@ void vck_kv_permute_tail(void* kcache, void* vcache, void* tmp, const int* perm,
  * the EOS ids before min_new_tokens.  History and banned ids outside [0, V) are skipped (image placeholders). */
 void vck_logits_process(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
                         const int* out_ids, const int* bad_words, int nrows, int V, void* stream);
+/* the verify form (prompt-lookup speculation): logits / out hold B * Q rows; row b * Q + j (j < nq[b]; the others are not written) is
+ * processed under record b with the drafts tok[b * Q + 1 .. b * Q + j] behind the record's history and step + j in place of its step
+ * (min_new_tokens) — what vck_logits_process would write j steps later, had the drafts been emitted. */
+void vck_logits_process_verify(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
+                               const int* out_ids, const int* bad_words, const int* tok, const int* nq, int B, int Q, int V, void* stream);
 void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w, uint16_t* xg, int B,
                           int D, int npart, void* stream);
 void vck_advance(int* step_dev, int* pos_dev, int* ctx_dev, void* stream);

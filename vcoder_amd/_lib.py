@@ -122,6 +122,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_request_generate_logprobs.restype = C.c_int
     lib.vc_request_speculation.argtypes = [vp, i32, i32, vp, vp, i32]
     lib.vc_request_speculation.restype = C.c_int
+    lib.vc_request_speculation_selection.argtypes = [vp, i32]
+    lib.vc_request_speculation_selection.restype = C.c_int
     lib.vc_last_speculation.argtypes = [vp, vp, i32]
     lib.vc_last_speculation.restype = C.c_int
     lib.vc_request_fanout.argtypes = [vp, i32]

@@ -220,7 +220,10 @@ inline bool operator==(const BeamLoop& a, const BeamLoop& b) {
 // on the kernels it was captured with.
 // A verify step of prompt-lookup speculation (STEP_SPEC) bakes in, beside its view (whose per-step buffers hold B * Q rows) and
 // nrows = B * Q: the draft's token rows, query counts, counters, the lookup / prompt id stores with their strides (the lengths are
-// read on the device), the log-prob scratch with its width, and B, Q, the n-gram size.
+// read on the device), the log-prob scratch with its width, and B, Q, the n-gram size.  A step of the wider scope
+// (vc_request_speculation_selection) additionally holds the spec_select launch — `sel` — the verify form of the processors when the
+// view carries their buffers (proc_prompt / proc_bad are view members) — `proc_out`, the B * Q processed rows — and, with log-probs,
+// the chosen-token scratch `s_chosen`; nullptr each in a step that lacks the launch, so the three say which launches it holds.
 // A fan-out step (STEP_FAN; vc_request_fanout) is a plain step over R = B n rows whose attention is launch_attention_fanout: beside
 // the view's members it bakes in the fan-out width (fan_n: the group of a row, the prefix row g of group g, the kernel's
 // instantiation) and the address of the groups' prompt lengths (fan_P; the lengths themselves are read on the device) — both are
@@ -231,11 +234,14 @@ struct SpecLoop {
     const int *lookup, *lookup_len, *prompt, *prompt_len;
     float* s_lp;
     int* s_ids;
+    int* sel;           // [B * Q] the rows' selections (launch_spec_select), or nullptr: the accept kernel takes the argmax itself
+    float* s_chosen;    // [B * Q] log-prob of sel[..] (log-probs with sel), else nullptr
+    float* proc_out;    // [B * Q, V] the processed rows spec_select reads (sel with a processor set), else nullptr
     int lookup_stride, prompt_stride, s_k, B, Q, ngram;
 };
 inline bool operator==(const SpecLoop& a, const SpecLoop& b) {
-    static_assert(sizeof(SpecLoop) == 96, "SpecLoop changed: compare the new member here");
-    return a.tok == b.tok && a.nq == b.nq && a.counters == b.counters && a.lookup == b.lookup && a.lookup_len == b.lookup_len &&
+    static_assert(sizeof(SpecLoop) == 120, "SpecLoop changed: compare the new member here");
+    return a.sel == b.sel && a.s_chosen == b.s_chosen && a.proc_out == b.proc_out && a.tok == b.tok && a.nq == b.nq && a.counters == b.counters && a.lookup == b.lookup && a.lookup_len == b.lookup_len &&
            a.prompt == b.prompt && a.prompt_len == b.prompt_len && a.s_lp == b.s_lp && a.s_ids == b.s_ids &&
            a.lookup_stride == b.lookup_stride && a.prompt_stride == b.prompt_stride && a.s_k == b.s_k && a.B == b.B && a.Q == b.Q &&
            a.ngram == b.ngram;
@@ -366,13 +372,16 @@ struct vc_model {
     Buf proc_prompt, proc_bad, proc_logits;
     // prompt-lookup speculation of the NEXT vc_generate* (vc_request_speculation; one-shot): k drafts per step, the largest n-gram,
     // the caller's lookup ids [B][spec_lookup_stride] with their lengths.  A call that serves it runs verify steps (STEP_SPEC) over
-    // B * (k + 1) rows on the sp_* buffers; spec_counters [B][4] (steps, tokens, drafted, accepted) of the last call when spec_last
+    // B * (k + 1) rows on the sp_* buffers; spec_counters [B][4] (steps, tokens, drafted, accepted) of the last call when spec_last.
+    // spec_any (vc_request_speculation_selection; travels with the request): sampled calls and calls with processors are served too
     int spec_k = 0, spec_ngram = 0, spec_B = 0, spec_lookup_stride = 0;
+    bool spec_any = false;
     std::vector<int> spec_lookup, spec_lookup_len;
     bool spec_last = false;
     bool spec_closed = false;     // a speculated call left the rows at different positions: the session's loop is closed
     std::vector<int> spec_counters;
     Buf sp_x, sp_xg, sp_qkv, sp_attn, sp_h, sp_logits, sp_ssq, sp_tok, sp_state, sp_lookup, sp_prompt, sp_lp, sp_ids;
+    Buf sp_sel, sp_chosen, sp_proc;   // the wider scope: selections and their log-probs [B * Q], processed rows [B * Q, V]
     // fan-out of the NEXT vc_generate (vc_request_fanout; one-shot): n sequences per prompt.  A served call prefills the B prompts
     // once into rows 0 .. B - 1 of a cache of fan_rows = B n rows (fan_rows is set around that prefill only) and steps the B n rows with
     // the fan-out attention; fan_P holds the groups' prompt lengths.  fan_last*: what the last vc_generate made of a request
@@ -455,6 +464,7 @@ static void clear_logits_processors_request(vc_model* m) {
 }
 static void clear_speculation_request(vc_model* m) {
     m->spec_k = m->spec_ngram = m->spec_B = m->spec_lookup_stride = 0;
+    m->spec_any = false;
     m->spec_lookup.clear();
     m->spec_lookup_len.clear();
 }

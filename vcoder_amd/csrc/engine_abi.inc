@@ -189,7 +189,8 @@ VC_API void vc_model_destroy(vc_model* m) {
                    &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre,
                    &m->ext_tok, &m->sc_idx, &m->sc_lp, &m->sc_xn, &m->sc_logits, &m->sc_tlp, &m->sc_tid, &m->lp_tok, &m->lp_top,
                    &m->lp_ids, &m->proc_prompt, &m->proc_bad, &m->proc_logits, &m->bm_state, &m->bm_tab, &m->bm_den, &m->bm_tmp, &m->fan_P,
-                   &m->fan_px[0], &m->fan_px[1], &m->fan_px[2]})
+                   &m->fan_px[0], &m->fan_px[1], &m->fan_px[2], &m->sp_x, &m->sp_xg, &m->sp_qkv, &m->sp_attn, &m->sp_h, &m->sp_logits, &m->sp_ssq,
+                   &m->sp_tok, &m->sp_state, &m->sp_lookup, &m->sp_prompt, &m->sp_lp, &m->sp_ids, &m->sp_sel, &m->sp_chosen, &m->sp_proc})
         b->release();
     for (auto& e : m->ev)
         if (e) (void)hipEventDestroy(e);
@@ -687,6 +688,17 @@ VC_API int vc_request_speculation(vc_model* m, int k, int max_ngram, const int32
             off += lookup_lens[b];
         }
     }
+    return VC_OK;
+}
+/* The selections a pending vc_request_speculation is served for: 0 greedy calls without logits processors, != 0 sampled calls and
+ * calls with processors as well.  Travels with the request.  See include/vcoder_hip.h. */
+VC_API int vc_request_speculation_selection(vc_model* m, int any) {
+    if (!m) return VC_ERR_INVALID;
+    if (m->spec_k == 0) {
+        m->ctx->err = "vc_request_speculation_selection: no vc_request_speculation is pending";
+        return VC_ERR_STATE;
+    }
+    m->spec_any = any != 0;
     return VC_OK;
 }
 /* the counters of the last vc_generate* call if it speculated: out [B][4] = steps, tokens emitted, drafts proposed, drafts accepted per

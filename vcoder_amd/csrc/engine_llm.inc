@@ -783,8 +783,9 @@ hipGraphExec_t step_graph(vc_model* m, StepKind kind, const LoopView& view, int 
 constexpr int SPEC_STATE_INTS = VC_MAX_ROWS * (1 + 4 + 1 + 1);
 constexpr int SPEC_MAX_ROWS = VC_GEMV_MAX_M;   // B * (k + 1) rows ride one weight pass
 // the buffers of a speculated call of B sequences, Q rows each: the per-step buffers of R = B * Q rows, the id stores (strides
-// max_positions: no call's lengths are baked into the step), the log-prob scratch of the widest K
-void ensure_spec(vc_model* m, int R) {
+// max_positions: no call's lengths are baked into the step), the log-prob scratch of the widest K; any: the selections and their
+// log-probs; proc: the processed rows of the verify form of the processors
+void ensure_spec(vc_model* m, int R, bool any = false, bool proc = false) {
     const vc_model_cfg& c = m->c;
     const size_t Rp = rup(R, 16), D = c.hidden;
     m->sp_x.ensure(Rp * D * 4, true);
@@ -800,8 +801,13 @@ void ensure_spec(vc_model* m, int R) {
     m->sp_prompt.ensure((size_t)VC_MAX_ROWS * c.max_positions * 4);
     m->sp_lp.ensure((size_t)SPEC_MAX_ROWS * VC_MAX_TOP_LOGPROBS * 4);
     m->sp_ids.ensure((size_t)SPEC_MAX_ROWS * VC_MAX_TOP_LOGPROBS * 4);
+    if (any) {
+        m->sp_sel.ensure((size_t)SPEC_MAX_ROWS * 4, true);
+        m->sp_chosen.ensure((size_t)SPEC_MAX_ROWS * 4, true);
+    }
+    if (any && proc) m->sp_proc.ensure(Rp * c.vocab * 4, true);
 }
-SpecLoop spec_view(vc_model* m, int B, int Q, int ngram, bool lookup, int lp_k) {
+SpecLoop spec_view(vc_model* m, int B, int Q, int ngram, bool lookup, int lp_k, bool any = false, bool proc = false) {
     SpecLoop sl{};
     int* st = m->sp_state.as<int>();
     sl.tok = m->sp_tok.as<int>();
@@ -820,6 +826,11 @@ SpecLoop spec_view(vc_model* m, int B, int Q, int ngram, bool lookup, int lp_k) 
         sl.s_ids = m->sp_ids.as<int>();
         sl.s_k = std::max(lp_k, 1);
     }
+    if (any) {   // the wider scope: the rows are selected by launch_spec_select (on processed rows with a processor set)
+        sl.sel = m->sp_sel.as<int>();
+        if (lp_k >= 0) sl.s_chosen = m->sp_chosen.as<float>();
+        if (proc) sl.proc_out = m->sp_proc.as<float>();
+    }
     sl.B = B;
     sl.Q = Q;
     sl.ngram = ngram;
@@ -837,7 +848,8 @@ LoopView spec_loop_view(vc_model* m, const LoopView& call) {
     v.ssq = m->sp_ssq.as<float>();
     return v;
 }
-// draft + embedding of the B * Q token rows -> the linears with the verify attention between -> (log-probs of every row) -> accept
+// draft + embedding of the B * Q token rows -> the linears with the verify attention between -> (the wider scope: the processors'
+// verify form, the rows' selections) -> (log-probs of every row, always of the raw rows) -> accept
 void enqueue_spec_step(vc_model* m, const LoopView& v, const SpecLoop& sl) {
     const vc_model_cfg& c = m->c;
     const int R = sl.B * sl.Q;
@@ -852,12 +864,23 @@ void enqueue_spec_step(vc_model* m, const LoopView& v, const SpecLoop& sl) {
                           v.kmask, v.kmask_stride};
         launch_attention_verify(va, v.st);
     });
-    if (v.lp_tok) {
-        TopkLogprobArgs ta{v.logits, c.vocab, nullptr, nullptr, sl.s_lp, sl.s_ids, c.vocab, sl.s_k, nullptr, nullptr, 0};
+    if (sl.sel) {
+        const float* lg = v.logits;
+        if (sl.proc_out) {
+            LogitsProcessArgs pa{v.logits, c.vocab, sl.proc_out, c.vocab, v.rows, v.proc_prompt, v.out_ids, v.proc_bad, c.vocab, sl.Q, sl.tok, sl.nq};
+            launch_logits_process(pa, R, v.st);
+            lg = sl.proc_out;
+        }
+        SpecSelectArgs sa{lg, c.vocab, c.vocab, v.rows, sl.nq, sl.sel, sl.B, sl.Q, 0};
+        launch_spec_select(sa, -1, v.st);
+    }
+    if (v.lp_tok) {   // (rows behind a sequence's queries hold a stale selection: any id, scored and never read)
+        TopkLogprobArgs ta{v.logits, c.vocab, sl.sel, sl.s_chosen, sl.s_lp, sl.s_ids, c.vocab, sl.s_k, nullptr, nullptr, 0};
         launch_topk_logprob(ta, R, -1, v.st);
     }
     SpecAcceptArgs aa{v.logits, c.vocab, c.vocab, v.rows, v.next_tok, v.out_ids, sl.tok, sl.nq, sl.B, sl.Q, sl.counters,
-                      v.lp_tok ? sl.s_lp : nullptr, v.lp_tok ? sl.s_ids : nullptr, sl.s_k, v.lp_tok, v.lp_top, v.lp_ids, v.lp_k};
+                      v.lp_tok ? sl.s_lp : nullptr, v.lp_tok ? sl.s_ids : nullptr, sl.s_k, v.lp_tok, v.lp_top, v.lp_ids, v.lp_k,
+                      sl.sel, v.lp_tok ? sl.s_chosen : nullptr};
     launch_spec_accept(aa, v.st);
 }
 // the session's captured verify step for this view and loop: replayed while both equal what it was captured from

@@ -599,9 +599,10 @@ std::unique_lock<std::mutex> prefill_on_session(vc_model* m, const int64_t* ids,
 }
 
 // whether the pending vc_request_speculation is served by a call of this form (the LDS bound of the verify attention is known
-// behind the prefill only): greedy, no processors, the bf16 step, B * (k + 1) rows in one weight pass
+// behind the prefill only): greedy and no processors — or any selection, with vc_request_speculation_selection — the bf16 step,
+// B * (k + 1) rows in one weight pass
 bool spec_request_served(const vc_model* m, const GenParams& g, int B) {
-    return m->spec_k > 0 && !g.do_sample && !g.proc && m->precision == 0 && B * (m->spec_k + 1) <= SPEC_MAX_ROWS;
+    return m->spec_k > 0 && (m->spec_any || (!g.do_sample && !g.proc)) && m->precision == 0 && B * (m->spec_k + 1) <= SPEC_MAX_ROWS;
 }
 
 // generate() on the session's own loop: prefill, then max_new - 1 graph-replayed (strict: eagerly enqueued) decode steps — or, with a
@@ -712,7 +713,8 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     if (cb && every == 1) report(1);
     if (spec) {
         // the verify loop: every replay emits 1 .. Q tokens per row, so a row's progress is its record's, not the host's step count
-        ensure_spec(m, B * Q);
+        const bool any = m->spec_any;
+        ensure_spec(m, B * Q, any, g.proc != 0);
         const int ld = m->c.max_positions;
         const bool lookup = !m->spec_lookup.empty();
         std::vector<int> ids32((size_t)B * T), st(SPEC_STATE_INTS, 0);
@@ -728,7 +730,7 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
                                     (size_t)m->spec_lookup_stride * 4, B, hipMemcpyHostToDevice, m->st));
         HIPCHK(hipMemcpyAsync(m->sp_state.p, st.data(), st.size() * 4, hipMemcpyHostToDevice, m->st));
         HIPCHK(hipStreamSynchronize(m->st));   // the host vectors
-        const SpecLoop sl = spec_view(m, B, Q, m->spec_ngram, lookup, want_lp ? K : -1);
+        const SpecLoop sl = spec_view(m, B, Q, m->spec_ngram, lookup, want_lp ? K : -1, any, g.proc != 0);
         const LoopView sv = spec_loop_view(m, v);
         // -> every row finished or full; least tokens an unfinished row still has to emit; least step over the unfinished rows
         int left = 0, low = 0;

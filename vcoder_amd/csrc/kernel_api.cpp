@@ -113,6 +113,18 @@ VCK_EXPORT void vck_spec_accept(const float* logits, int ldl, int V, int* rows, 
                      lp_ids, lp_k};
     launch_spec_accept(a, S(stream));
 }
+VCK_EXPORT void vck_spec_accept_sel(const float* logits, int ldl, int V, int* rows, int* next_tok, int* out_ids, const int* tok, const int* nq,
+                                    int B, int Q, int* counters, const float* scratch_lp, const int* scratch_ids, int scratch_k, float* lp_tok,
+                                    float* lp_top, int* lp_ids, int lp_k, const int* sel, const float* scratch_chosen, void* stream) {
+    SpecAcceptArgs a{logits, ldl, V, rows, next_tok, out_ids, tok, nq, B, Q, counters, scratch_lp, scratch_ids, scratch_k, lp_tok, lp_top,
+                     lp_ids, lp_k, sel, scratch_chosen};
+    launch_spec_accept(a, S(stream));
+}
+VCK_EXPORT void vck_spec_select(const float* logits, int ldl, int V, const int* rows, const int* nq, int* sel, int B, int Q, int lds_floats,
+                                void* stream) {
+    SpecSelectArgs a{logits, ldl, V, rows, nq, sel, B, Q, 0};
+    launch_spec_select(a, lds_floats, S(stream));
+}
 VCK_EXPORT int vck_row_state_stride() { return RS_STRIDE; }
 VCK_EXPORT void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, void* stream) {
     launch_uniform_probe(h, u, gumbel, n, S(stream));
@@ -142,6 +154,13 @@ VCK_EXPORT void vck_logits_process(const float* logits, int ldl, float* out, int
                                    const int* out_ids, const int* bad_words, int nrows, int V, void* stream) {
     LogitsProcessArgs a{logits, ldl, out, ldo, rows, prompt_ids, out_ids, bad_words, V};
     launch_logits_process(a, nrows, S(stream));
+}
+VCK_EXPORT void vck_logits_process_verify(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
+                                          const int* out_ids, const int* bad_words, const int* tok, const int* nq, int B, int Q, int V,
+                                          void* stream) {
+    if (B < 1 || Q < 1) return;   // nothing is launched, nothing written
+    LogitsProcessArgs a{logits, ldl, out, ldo, rows, prompt_ids, out_ids, bad_words, V, Q, tok, nq};
+    launch_logits_process(a, B * Q, S(stream));
 }
 VCK_EXPORT void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w,
                                      uint16_t* xg, int B, int D, int npart, void* stream) {

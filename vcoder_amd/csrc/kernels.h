@@ -512,8 +512,24 @@ struct SpecAcceptArgs {
     float *lp_tok, *lp_top;
     int* lp_ids;
     int lp_k;
+    const int* sel;               // [B * Q] the rows' selections (launch_spec_select), or nullptr: the argmax is computed here
+    const float* scratch_chosen;  // [B * Q] log-prob of sel[..] (launch_topk_logprob with chosen = sel), or nullptr: scratch_lp entry 0
 };
 void launch_spec_accept(const SpecAcceptArgs& a, hipStream_t s);
+// the selections of a verify step's rows (select.hip spec_select_kernel): sel[b * Q + j] = the raw selection — greedy argmax, or
+// temperature / top-k / top-p / Gumbel-max, the body launch_select_embed runs — of logits row b * Q + j under record b with the
+// sampler key RS_STEP + j, for j < nq[b]; other entries of sel are not written.  One workgroup per row.
+struct SpecSelectArgs {
+    const float* logits;     // [B * Q, ldl]
+    int ldl, V;
+    const int* rows;         // [B][RS_STRIDE]
+    const int* nq;           // [B]
+    int* sel;                // [B * Q] out
+    int B, Q;
+    int lds_floats;          // filled by the launcher
+};
+// lds_floats < 0: stage the scaled row in LDS when the device allows; 0 (or < V): every pass re-reads the row from global memory
+void launch_spec_select(const SpecSelectArgs& a, int lds_floats, hipStream_t s);
 void launch_advance(int* step_dev, int* pos_dev, int* ctx_dev, hipStream_t s);
 // scoring: logprob[r] = logits[r, target[r]] - logsumexp(logits[r, 0:V]) for `rows` rows of stride ldl floats (ldl >= V; any V, any
 // alignment), one workgroup per row, fp32 throughout (select.hip)
@@ -552,6 +568,12 @@ struct LogitsProcessArgs {
     const int* out_ids;      // base of the id store; row r: out_ids[RS_OUT_OFF .. + RS_STEP)
     const int* bad_words;    // [VC_MAX_BAD_WORDS][1 + VC_MAX_BAD_WORD_LEN]: (length, ids); nullptr when no row has RS_LP_NBAD > 0
     int V;
+    // the verify form (prompt-lookup speculation; zeroes: the plain form above).  Q > 0: nrows = B * Q, logits / out row b * Q + j is
+    // processed under record b with the drafts tok[b * Q + 1 .. b * Q + j] behind its history and RS_STEP + j as its step, for
+    // j < nq[b]; the other rows are not written
+    int Q;
+    const int* tok;          // [B * Q] the draft kernel's token rows
+    const int* nq;           // [B]
 };
 void launch_logits_process(const LogitsProcessArgs& a, int nrows, hipStream_t s);
 // one beam-search step of B sequences of n beams each (rows b * n .. b * n + n - 1; R = B * n <= 16) behind a launch_topk_logprob

@@ -159,16 +159,13 @@ VC_DEV int emit_token(int* rs, int* out, int step, int sel) {
     return tok;
 }
 
-__global__ __launch_bounds__(1024) void select_embed_kernel(SelectArgs p) {
-    VC_DYNAMIC_SMEM(float, zs);  // [V] scaled logits of the row (sampling only)
-    __shared__ BlockRed red;
-    __shared__ int tok_s;
-    const int r = p.row0 + (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int* rs = p.rows + (size_t)r * RS_STRIDE;
-    if (!rs[RS_ACTIVE]) return;
-    const int step = rs[RS_STEP];
-    const float* lg = p.logits + (size_t)blockIdx.x * p.ldl;
-    const int V = p.V;
+// The raw selection of ONE logits row `lg` under the record `rs` with the sampler key `step` (the generated index the token will
+// have): greedy — the argmax, lowest id on ties; sampled — temperature -> top-k -> top-p -> Gumbel-max.  -> the id, in every thread.
+// Called by all 1024 threads of a workgroup; the block shape is part of the arithmetic (the loop strides, block_sum_f's order for the
+// top-p mass), so select_embed_kernel and spec_select_kernel share this one body.  zs: the [V] LDS staging of the scaled row, used
+// when lds_floats >= V (sampling only).
+VC_DEV int select_row(const float* lg, int V, const int* rs, int step, float* zs, int lds_floats, BlockRed& red, int tid, int lane,
+                      int wave) {
     float best = -INFINITY;
     int bi = 0x7FFFFFFF;
     if (!rs[RS_SAMPLE]) {
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(1024) void select_embed_kernel(SelectArgs p) {
         const int top_k = rs[RS_TOPK];
         const float top_p = __builtin_bit_cast(float, rs[RS_TOPP]);
         const uint32_t seed_lo = (uint32_t)rs[RS_SEED_LO], seed_hi = (uint32_t)rs[RS_SEED_HI];
-        const bool staged = p.lds_floats >= V;
+        const bool staged = lds_floats >= V;
         auto z = [&](int i) { return staged ? zs[i] : lg[i] * inv_t; };
         if (staged) {
             for (int i = tid; i < V; i += 1024) zs[i] = lg[i] * inv_t;
@@ -243,6 +240,19 @@ __global__ __launch_bounds__(1024) void select_embed_kernel(SelectArgs p) {
         }
         block_argmax(best, bi, red, lane, wave);
     }
+    return bi;
+}
+
+__global__ __launch_bounds__(1024) void select_embed_kernel(SelectArgs p) {
+    VC_DYNAMIC_SMEM(float, zs);  // [V] scaled logits of the row (sampling only)
+    __shared__ BlockRed red;
+    __shared__ int tok_s;
+    const int r = p.row0 + (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int* rs = p.rows + (size_t)r * RS_STRIDE;
+    if (!rs[RS_ACTIVE]) return;
+    const int step = rs[RS_STEP];
+    const float* lg = p.logits + (size_t)blockIdx.x * p.ldl;
+    const int bi = select_row(lg, p.V, rs, step, zs, p.lds_floats, red, tid, lane, wave);
     // ---- bookkeeping (one lane) ----------------------------------------------------------------------------------
     if (tid == 0) {
         const int tok = emit_token(rs, p.out_ids + rs[RS_OUT_OFF], step, bi);
@@ -394,6 +404,38 @@ void launch_select_embed(const SelectArgs& a0, hipStream_t s) {
     }
 #endif
     VC_LAUNCH(select_embed_kernel, dim3(a.nrows), dim3(1024), lds, s, a);
+}
+
+// The selections of a verify step (prompt-lookup speculation under sampling or logits processors): one workgroup per verify row
+// (b, j), j < nq[b], writes sel[b * Q + j] = select_row of logits row b * Q + j under record b with the sampler key RS_STEP + j — the
+// key a plain step of its own would have used for the token at that generated index, so an accepted run reproduces the plain loop's
+// draws id for id.  No bookkeeping: spec_accept_kernel walks `sel`.  The B * Q rows run side by side (a loop over a sequence's Q rows
+// would put Q full sampler passes on the step's critical path); rows j >= nq[b] write nothing.
+__global__ __launch_bounds__(1024) void spec_select_kernel(SpecSelectArgs p) {
+    VC_DYNAMIC_SMEM(float, zs);  // [V] scaled logits of the row (sampling only)
+    __shared__ BlockRed red;
+    const int b = (int)blockIdx.x / p.Q, j = (int)blockIdx.x % p.Q, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (j >= min(p.nq[b], min(p.Q, 8))) return;
+    const int* rs = p.rows + (size_t)b * RS_STRIDE;
+    const int bi = select_row(p.logits + (size_t)blockIdx.x * p.ldl, p.V, rs, rs[RS_STEP] + j, zs, p.lds_floats, red, tid, lane, wave);
+    if (tid == 0) p.sel[blockIdx.x] = bi;
+}
+void launch_spec_select(const SpecSelectArgs& a0, int lds_floats, hipStream_t s) {
+    if (a0.B <= 0 || a0.Q <= 0) return;
+    SpecSelectArgs a = a0;
+    // staged in LDS as launch_select_embed stages its row; lds_floats < 0: what the device allows, 0 (or < V): never
+    size_t lds = (size_t)a.V * 4;
+    if (lds > 150 * 1024 || (lds_floats >= 0 && lds_floats < a.V)) lds = 0;
+    a.lds_floats = (int)(lds / 4);
+#ifndef VC_EMU
+    static size_t allowed = 0;
+    if (lds > 48 * 1024 && lds > allowed) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spec_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        allowed = lds;
+    }
+#endif
+    VC_LAUNCH(spec_select_kernel, dim3((unsigned)(a.B * a.Q)), dim3(1024), lds, s, a);
 }
 
 // test hook: the sampler's hash -> uniform map on explicit hash values (the extreme h = 0xFFFFFFFF must stay below 1)
@@ -674,10 +716,16 @@ void launch_topk_logprob(const TopkLogprobArgs& a0, int nrows, int lds_floats, h
 //        history ends with the ids in front of it (a tail that may reach into the prompt)
 //      MinNewTokensLengthLogitsProcessor / MinLengthLogitsProcessor (folded on the host): RS_EOS and RS_LP_EOS while RS_STEP < m
 // Ids outside [0, V) are never written.  Rows are independent; pad columns V .. ldo are not touched.
+// The verify form (p.Q > 0; prompt-lookup speculation): workgroup r = b * Q + j, j < nq[b], processes logits row r under record b as
+// the plain loop would j steps later, if the j drafts in front of the row are accepted — the history is followed by the drafts
+// tok[b * Q + 1 .. b * Q + j] (tok[b * Q] is out_ids[RS_STEP - 1], in the store already) and MinNewTokens compares RS_STEP + j.  Rows
+// j >= nq[b] write nothing.  A row behind a rejected draft holds what nobody reads.
 constexpr int LPROC_THREADS = 1024;
 __global__ __launch_bounds__(LPROC_THREADS) void logits_process_kernel(LogitsProcessArgs p) {
     const int r = blockIdx.x, tid = threadIdx.x;
-    const int* rs = p.rows + (size_t)r * RS_STRIDE;
+    const int rec = p.Q > 0 ? r / p.Q : r, nd = p.Q > 0 ? r % p.Q : 0;   // the row's record; the drafts behind its history
+    if (p.Q > 0 && nd >= min(p.nq[rec], p.Q)) return;
+    const int* rs = p.rows + (size_t)rec * RS_STRIDE;
     if (!rs[RS_ACTIVE]) return;
     const int V = p.V;
     const float* lg = p.logits + (size_t)r * p.ldl;
@@ -693,10 +741,11 @@ __global__ __launch_bounds__(LPROC_THREADS) void logits_process_kernel(LogitsPro
     // ---- the row's history ------------------------------------------------------------------------------------------------------
     const int P = max(rs[RS_LP_HIST_LEN], 0);
     const int step = max(min(rs[RS_STEP], rs[RS_MAXNEW]), 0);
-    const int L = P + step;
+    const int G = P + step, L = G + nd;
     const int* hp = p.prompt_ids + rs[RS_LP_HIST_OFF];
     const int* hg = p.out_ids + rs[RS_OUT_OFF];
-    auto h = [&](int j) { return j < P ? hp[j] : hg[j - P]; };
+    const int* hd = nd > 0 ? p.tok + (size_t)rec * p.Q + 1 : nullptr;
+    auto h = [&](int j) { return j < P ? hp[j] : (j < G ? hg[j - P] : hd[j - G]); };
     const float pen = __builtin_bit_cast(float, rs[RS_LP_PENALTY]);
     const int n = rs[RS_LP_NGRAM], nbad = p.bad_words != nullptr ? min(rs[RS_LP_NBAD], VC_MAX_BAD_WORDS) : 0;
     __syncthreads();
@@ -727,7 +776,7 @@ __global__ __launch_bounds__(LPROC_THREADS) void logits_process_kernel(LogitsPro
         for (int k = 0; k < len - 1 && ok; ++k) ok = h(L - (len - 1) + k) == e[1 + k];
         if (ok && (unsigned)e[len] < (unsigned)V) out[e[len]] = -INFINITY;
     }
-    if (rs[RS_STEP] < rs[RS_LP_MINNEW]) {
+    if (rs[RS_STEP] + nd < rs[RS_LP_MINNEW]) {
         const int neos = min(rs[RS_LP_NEOS], VC_MAX_EOS_EXTRA);
         if (tid <= neos) {
             const int t = tid == 0 ? rs[RS_EOS] : rs[RS_LP_EOS + tid - 1];
@@ -948,6 +997,8 @@ void launch_spec_draft(const SpecDraftArgs& a, hipStream_t s) {
 // the row's last slot cuts the rest; RS_STEP and RS_POS advance by the number emitted; the last emitted id is the next step's first
 // token.  With log-probs, the emitted rows' entries of the scratch a launch_topk_logprob over the B * Q rows filled (entry 0 of a row
 // is its argmax) are copied into the slabs.  counters [B][4] += {1, emitted, drafted, emitted - 1}.
+// sel != nullptr: a_j = sel[b * Q + j], what spec_select_kernel chose for the row (sampling, processed rows) — nothing is reduced here.
+// scratch_chosen != nullptr: the log-prob of a_j is scratch_chosen[b * Q + j] (a sampled token is not entry 0 of its top-K row).
 __global__ __launch_bounds__(1024) void spec_accept_kernel(SpecAcceptArgs p) {
     __shared__ BlockRed red;
     __shared__ int a_s[8];
@@ -955,7 +1006,7 @@ __global__ __launch_bounds__(1024) void spec_accept_kernel(SpecAcceptArgs p) {
     const int nq = min(p.nq[b], min(Q, 8));
     if (nq <= 0) return;
     int* rs = p.rows + (size_t)b * RS_STRIDE;
-    for (int j = 0; j < nq; ++j) {
+    for (int j = 0; j < nq && p.sel == nullptr; ++j) {
         const float* lg = p.logits + ((size_t)b * Q + j) * p.ldl;
         float best = -INFINITY;
         int bi = 0x7FFFFFFF;
@@ -969,6 +1020,8 @@ __global__ __launch_bounds__(1024) void spec_accept_kernel(SpecAcceptArgs p) {
     }
     __syncthreads();
     if (tid != 0) return;
+    if (p.sel != nullptr)
+        for (int j = 0; j < nq; ++j) a_s[j] = p.sel[(size_t)b * Q + j];
     const int* tok = p.tok + (size_t)b * Q;
     int* out = p.out_ids + rs[RS_OUT_OFF];
     const int max_new = rs[RS_MAXNEW];
@@ -979,7 +1032,7 @@ __global__ __launch_bounds__(1024) void spec_accept_kernel(SpecAcceptArgs p) {
         last = emit_token(rs, out, step, a_s[j]);
         if (p.lp_tok != nullptr && step < max_new) {
             const size_t slot = (size_t)rs[RS_OUT_OFF] + step, src = ((size_t)b * Q + j) * p.scratch_k;
-            p.lp_tok[slot] = p.scratch_lp[src];
+            p.lp_tok[slot] = p.scratch_chosen != nullptr ? p.scratch_chosen[(size_t)b * Q + j] : p.scratch_lp[src];
             for (int t = 0; t < p.lp_k; ++t) {
                 p.lp_top[slot * p.lp_k + t] = p.scratch_lp[src + t];
                 p.lp_ids[slot * p.lp_k + t] = p.scratch_ids[src + t];

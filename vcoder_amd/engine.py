@@ -588,7 +588,8 @@ class HipEngine:
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                  on_tokens=None, stream_every: int = 1, attention_mask=None, logprobs: bool = False,
                  top_logprobs: int = 0, processors=None, eos_extra: Sequence[int] = (), speculate: Optional[int] = None,
-                 lookup_ngram: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False) -> np.ndarray:
+                 lookup_ngram: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False,
+                 speculate_selection: str = "greedy") -> np.ndarray:
         """generate() on the device (vc_generate): greedy, or temperature / top-k / top-p sampling with a counter-based
         generator (same seed -> same tokens).  on_tokens(first_step, ids [B, n]) is called with every `stream_every` new
         columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32.
@@ -609,6 +610,14 @@ class HipEngine:
         last_speculation = {"steps", "tokens", "drafted", "accepted"} per-row int arrays, or None when the request was not served:
         sampling, processors, precision split / strict, B * (k + 1) > 32, a cache too long for the verify attention's LDS score
         rows (the call then runs as without it).  ValueError for k or lookup_ngram outside their range.
+        speculate_selection = "greedy" (the default: the scope above) | "any" (vc_request_speculation_selection): sampled calls
+        (temperature / top-k / top-p, any seed) and calls with a processor set are served as well — also with log-probs, EOS ids,
+        stop sequences, on_tokens and num_return_sequences in its repeated form while B n (k + 1) <= 32.  The sampler is a Gumbel-max
+        keyed by (seed, generated index, vocabulary id): the verify step samples every query row with the key of the token it would
+        become, processes it over the history plus the drafts in front of it, and accepts a draft while it equals the token selected
+        in front of it — the ids and log-probs are array_equal to the same call with the same seed without `speculate`.  Opt-in: a
+        served call leaves the decode pool and closes the session's loop.  Still not served under "any": precision split / strict,
+        fan_out=True, B (k + 1) > 32, the LDS bound.  Any other value: ValueError.
         num_return_sequences = n (vc_request_fanout): n sequences per prompt -> [B n, n_generated], rows b n + j, log-probs and
         on_tokens columns B n rows wide — bit for bit the call on the prompts repeated n times (np.repeat(.., n, axis=0)) with the
         same seed.  By default the engine repeats the prompts itself.
@@ -627,6 +636,8 @@ class HipEngine:
         if nret > 1 and B * nret > self.MAX_BATCH:
             raise ValueError(f"batch {B} x num_return_sequences {nret} exceeds the {self.MAX_BATCH} rows a replica decodes at a time")
         look = None
+        if speculate_selection not in ("greedy", "any"):
+            raise ValueError(f"speculate_selection must be 'greedy' or 'any', got {speculate_selection!r}")
         if speculate is not None:
             k, ng = int(speculate), int(lookup_ngram)
             if not 1 <= k <= 7:
@@ -735,6 +746,8 @@ class HipEngine:
             try:
                 self._check(self.lib.vc_request_speculation(self._model, k, ng, None if look is None else lk_flat.ctypes.data_as(C.c_void_p),
                                                             None if look is None else lk_lens.ctypes.data_as(C.c_void_p), B))
+                if speculate_selection == "any":
+                    self._check(self.lib.vc_request_speculation_selection(self._model, 1))
             except BaseException:
                 self.lib.vc_clear_attention_mask(self._model)
                 self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))

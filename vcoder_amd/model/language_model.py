@@ -454,7 +454,8 @@ class _HipCausalLMBase:
                  output_logprobs: bool = False, top_logprobs: int = 0, repetition_penalty: Optional[float] = None,
                  no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
                  bad_words_ids=None, processors_on_device: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
-                 max_matching_ngram_size: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False, **kwargs):
+                 max_matching_ngram_size: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False,
+                 speculate_selection: str = "greedy", **kwargs):
         """Returns cat(input_ids, new_ids) [B, T+n] int64 — the prompt part keeps its negative placeholder ids,
         callers slice `[:, T:]` (serve/cli.py:135).
 
@@ -502,6 +503,21 @@ class _HipCausalLMBase:
         pool, and closes it: decode_step / extend behind it refuse until the next prefill.  k or the n-gram size outside their
         range raise ValueError before the engine is touched.
 
+        speculate_selection = "greedy" (the default) | "any": the selections prompt_lookup_num_tokens is served for.  "greedy" is the
+        scope above, bit for bit: a sampled call, or one with a processor set, runs as without the argument.  "any" also serves
+        sampled calls (temperature / top-k / top-p, any seed) and calls with a device-resident processor set (greedy or sampled),
+        with log-probs, EOS ids, stop sequences, a streamer, and num_return_sequences = n in its default (repeated-prompt) form while
+        B n (k + 1) <= 32.  The device sampler is a Gumbel-max keyed by (seed, generated index, vocabulary id), so the token a row
+        emits at index t is a pure function of that step's logits row, the row's parameters and t: the verify step samples query row
+        j with the key of index t + j, processes it over the history plus the j drafts in front of it, and accepts a draft while it
+        equals the token selected in front of it.  No acceptance probability is involved: `sequences`, their number, the log-probs
+        and the streamer's pieces are exactly (array_equal) those of the same call with the same `seed` without
+        prompt_lookup_num_tokens.  It is opt-in because a served call leaves the decode pool and closes the session's loop (above),
+        which a sampled caller has to ask for.  Still NOT served under "any" (the call runs as without the argument, `speculation` is
+        None): num_beams > 1; precision "split" / "strict"; a stopping criterion that needs the host loop;
+        processors_on_device=False or a processor set that does not fit the device; fan_out=True; B (k + 1) > 32; the LDS bound of
+        the verify attention.  Any other value raises ValueError before the engine is touched.
+
         num_return_sequences = n (HF 4.31's semantics): with do_sample=True `sequences` is [B n, T + L], rows b n + j, each carrying
         its prompt's input_ids; every GenerateOutput field is B n rows wide and the streamer receives B n-wide columns.  The result
         is exactly (array_equal) that of the call on input_ids.repeat_interleave(n, 0) with the images repeated and the same seed.
@@ -546,6 +562,8 @@ class _HipCausalLMBase:
                 raise ValueError(f"prompt_lookup_num_tokens must be in 1 .. 7, got {prompt_lookup_num_tokens!r}")
             if not 1 <= int(max_matching_ngram_size) <= 4:
                 raise ValueError(f"max_matching_ngram_size must be in 1 .. 4, got {max_matching_ngram_size!r}")
+        if speculate_selection not in ("greedy", "any"):
+            raise ValueError(f"speculate_selection must be 'greedy' or 'any', got {speculate_selection!r}")
         nrs = int(num_return_sequences)
         if nrs < 1:
             raise ValueError(f"`num_return_sequences` has to be at least 1, got {num_return_sequences!r}")
@@ -661,6 +679,7 @@ class _HipCausalLMBase:
                                        eos_extra=eos_more if proc is not None else (),
                                        speculate=None if prompt_lookup_num_tokens is None else int(prompt_lookup_num_tokens),
                                        lookup_ngram=int(max_matching_ngram_size), lookup_ids=lookup_ids,
+                                       speculate_selection=speculate_selection,
                                        **(dict(num_return_sequences=nrs, fan_out=bool(fan_out)) if nrs > 1 else {}))
             self._generation += 1
             out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
