@@ -422,6 +422,33 @@ typedef struct vc_logits_processors {
 } vc_logits_processors;
 int vc_request_logits_processors(vc_model* m, const vc_logits_processors* p);
 
+/* Constrained decoding of the NEXT vc_generate / vc_generate_greedy* call (one-shot): a deterministic automaton over token ids.
+ * State s owns the edges state_off[s] .. state_off[s + 1] (CSR); edge_tok is ascending and unique within a state, edge_next the state
+ * behind an edge; default_next[s] >= 0: every id without an edge is allowed too and leads there (free text), -1: only the ids with
+ * an edge are allowed.  State 0 is the start state, -1 the dead state (nothing is allowed).  A row starts in state 0 at its first
+ * generated token; in front of every selection the ids its state does not allow are set to -inf in the processed copy of the
+ * step's logits row, behind the processors of vc_request_logits_processors (HF 4.31's place of PrefixConstrainedLogitsProcessor);
+ * edge ids outside [0, vocab) are ignored; a finished row keeps emitting pad.  The call runs on the session's own loop (every
+ * precision mode, greedy or sampled, with or without processors, log-probs — which stay those of the RAW rows — EOS ids, stop
+ * sequences, a callback, vc_request_fanout in both forms); a pending vc_request_speculation is not served beside it (the call
+ * runs as without it).
+ * Refused with VC_ERR_INVALID, nothing changed: more than 65536 states or 1 << 20 edges, a missing table, a state_off that does not
+ * rise from 0 to n_edges, edge ids that are not ascending and unique within a state, a target outside [-1, n_states), a state
+ * reachable from 0 that allows no token.  The tables are copied here and uploaded when the call is armed.  Cleared when that call
+ * returns, also when it fails; every other entry point ignores and clears it — except vc_generate_beam, which refuses to run with
+ * VC_ERR_STATE while one is pending (and clears it); a == NULL cancels. */
+#define VC_MAX_AUTOMATON_STATES 65536
+#define VC_MAX_AUTOMATON_EDGES (1 << 20)
+typedef struct vc_token_automaton {
+    int32_t n_states;
+    int32_t n_edges;
+    const int32_t* state_off;     /* [n_states + 1] */
+    const int32_t* edge_tok;      /* [n_edges] */
+    const int32_t* edge_next;     /* [n_edges] */
+    const int32_t* default_next;  /* [n_states] */
+} vc_token_automaton;
+int vc_request_constraint(vc_model* m, const vc_token_automaton* a);
+
 /* spliced sequence length (text rows + feature rows) of the last vc_generate_greedy* call: lets a caller that splits a large
  * batch into replica-sized pieces reproduce the reference's whole-batch behaviour for unequal lengths (quirk 6) */
 int vc_last_spliced_len(vc_model* m);

@@ -221,6 +221,16 @@ void vck_kv_permute_tail(void* kcache, void* vcache, void* tmp, const int* perm,
  * the EOS ids before min_new_tokens.  History and banned ids outside [0, V) are skipped (image placeholders). */
 void vck_logits_process(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
                         const int* out_ids, const int* bad_words, int nrows, int V, void* stream);
+/* vck_logits_process with a token automaton behind the processors (constrained decoding; vcoder_amd/constraints.py): CSR tables —
+ * state s owns the edges state_off[s] .. state_off[s + 1], edge_tok ascending and unique within a state, edge_next / default_next in
+ * [-1, n_states).  Further record slots: [110] != 0: the automaton applies to the row; [111] / [112] the state behind the first
+ * [112] ids of the row's out_ids (zeroes: the start state; -1: dead) — a cache the kernel advances to `step` and WRITES BACK, so
+ * `rows` is not const here.  Unfinished rows only: every id without an edge in the row's state becomes -inf; a state whose
+ * default_next >= 0 masks nothing; the dead state masks [0, V).  Edge ids outside [0, V) are ignored.  Null tables: exactly
+ * vck_logits_process. */
+void vck_logits_process_constrained(const float* logits, int ldl, float* out, int ldo, int* rows, const int* prompt_ids,
+                                    const int* out_ids, const int* bad_words, const int* state_off, const int* edge_tok,
+                                    const int* edge_next, const int* default_next, int n_states, int nrows, int V, void* stream);
 /* the verify form (prompt-lookup speculation): logits / out hold B * Q rows; row b * Q + j (j < nq[b]; the others are not written) is
  * processed under record b with the drafts tok[b * Q + 1 .. b * Q + j] behind the record's history and step + j in place of its step
  * (min_new_tokens) — what vck_logits_process would write j steps later, had the drafts been emitted. */

@@ -733,6 +733,46 @@ def bench_logits_process():
             print(f"logits_process rows {rows:3d} V {V} {'all on, step %3d' % step if on else 'all off (copy) '}: {us:7.1f} us", flush=True)
 
 
+def bench_logits_process_constrained():
+    """logits_process_kernel with a token automaton (phase 4) over [rows, 32000] fp32 logits, the other processors off: the launch
+    without tables (the copy), a free-text state, and states of 1 / 133 / 4096 / 32000 edges (ids spread evenly over the vocabulary);
+    the stored state is current (one launch of a decode step: nothing to walk)"""
+    V = 32000
+    stride = int(lib.vck_row_state_stride())
+    counts = (1, 133, 4096, 32000)
+    off, tok, dflt = [0], [], []
+    for n in counts:
+        tok += sorted({int(t) for t in torch.linspace(0, V - 1, n, dtype=torch.float64).round().tolist()}) if n > 1 else [V // 2]
+        off.append(len(tok))
+        dflt.append(-1)
+    off.append(len(tok))          # the free-text state: no edges, default_next = itself
+    dflt.append(len(counts))
+    t_off, t_tok, t_dflt = (torch.tensor(a, dtype=torch.int32, device=dev) for a in (off, tok, dflt))
+    t_next = torch.zeros(len(tok), dtype=torch.int32, device=dev)
+    gen = torch.zeros(16 * 128, dtype=torch.int32, device=dev)
+    for rows in (1, 8, 16):
+        lg = [torch.randn(rows, V, device=dev) * 3 for _ in range(4)]
+        out = torch.empty(rows, V, device=dev)
+        it = [0]
+        for name, state in [("no tables (copy)", None), ("free-text state", len(counts))] + [(f"{n:5d} edges", i) for i, n in enumerate(counts)]:
+            rs = torch.zeros((rows, stride), dtype=torch.int32, device=dev)
+            rs[:, 0] = 1                  # RS_ACTIVE
+            rs[:, 2] = 64                 # RS_STEP
+            rs[:, 4] = 128                # RS_MAXNEW
+            rs[:, 5] = -1                 # RS_EOS
+            rs[:, 14] = torch.arange(rows, dtype=torch.int32, device=dev) * 128   # RS_OUT_OFF
+            if state is not None:
+                rs[:, 110] = 1            # RS_CN_ON
+                rs[:, 111] = state        # RS_CN_STATE
+                rs[:, 112] = 64           # RS_CN_POS = RS_STEP
+            tabs = (P(t_off), P(t_tok), P(t_next), P(t_dflt), len(dflt)) if state is not None else (None, None, None, None, 0)
+
+            def f():
+                it[0] += 1
+                lib.vck_logits_process_constrained(P(lg[it[0] % 4]), V, P(out), V, P(rs), None, P(gen), None, *tabs, rows, V, None)
+            print(f"logits_process_constrained rows {rows:3d} V {V} {name:17s}: {timeit(f, iters=40):7.1f} us", flush=True)
+
+
 def bench_score_head():
     """The score path's chunk at 7b dims (D 4096, V 32000): gathered final RMSNorm + lm_head + token_logprob over M scored rows (16 .. 1024), the
     lm_head as ceil(M / 32) passes of the weight-streaming GEMV (packed weights) against one GEMM — the crossover behind
@@ -873,6 +913,7 @@ if __name__ == "__main__":
              "dattn_split": bench_dattn_split, "dattn_kv8": bench_dattn_kv8, "gemv_wg": bench_gemv_wg, "gemv_fp8_ks": bench_gemv_fp8_ks,
              "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn, "token_logprob": bench_token_logprob,
              "topk_logprob": bench_topk_logprob, "logits_process": bench_logits_process,
+             "logits_process_constrained": bench_logits_process_constrained,
              "score_head": bench_score_head, "attention_verify": bench_attention_verify, "attention_fanout": bench_attention_fanout, "gemv_formats": bench_gemv_formats, "gemv_w4": lambda: bench_gemv_formats(("w4",))}
     for w in what:
         table[w]()

@@ -40,6 +40,11 @@ class LogitsProcessors(C.Structure):   # vc_logits_processors
                 ("n_eos_extra", C.c_int32), ("eos_extra", C.c_void_p)]
 
 
+class TokenAutomatonTables(C.Structure):   # vc_token_automaton
+    _fields_ = [("n_states", C.c_int32), ("n_edges", C.c_int32), ("state_off", C.c_void_p), ("edge_tok", C.c_void_p),
+                ("edge_next", C.c_void_p), ("default_next", C.c_void_p)]
+
+
 TOKEN_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32))
 
 
@@ -138,6 +143,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_request_logits_processors.restype = C.c_int
     lib.vck_logits_process.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp]
     lib.vck_logits_process.restype = None
+    lib.vck_logits_process_constrained.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.vck_logits_process_constrained.restype = None
+    lib.vc_request_constraint.argtypes = [vp, C.POINTER(TokenAutomatonTables)]
+    lib.vc_request_constraint.restype = C.c_int
     lib.vc_rewind.argtypes = [vp, i32]
     lib.vc_rewind.restype = C.c_int
     lib.vc_request_attentions.argtypes = [vp, vp, C.c_size_t]

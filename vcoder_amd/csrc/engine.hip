@@ -159,16 +159,23 @@ struct LoopView {
     const int *proc_prompt, *proc_bad;
     float* proc_logits;
     const int* fan_P;      // fan-out step: the prompt length of every group (device ints), else nullptr
+    // the token automaton of a generate() call (vc_request_constraint): its tables on the device (LogitsProcessArgs::cn_*); the rows'
+    // switch and state travel in their records (RS_CN_*).  nullptr / 0 (every view but the one such a call makes for itself): the
+    // processor launch, if the step holds one, has no fourth phase
+    const int *cn_state_off, *cn_edge_tok, *cn_edge_next, *cn_default_next;
+    int cn_states;         // (padding follows)
 };
 inline bool operator==(const LoopView& a, const LoopView& b) {
-    static_assert(sizeof(LoopView) == 248, "LoopView changed: compare the new member here");
+    static_assert(sizeof(LoopView) == 288, "LoopView changed: compare the new member here");
     return a.st == b.st && a.kc == b.kc && a.vc == b.vc && a.es == b.es && a.split_G == b.split_G && a.capR == b.capR &&
            a.capS == b.capS && a.rows == b.rows && a.kmask == b.kmask && a.kmask_stride == b.kmask_stride && a.x_dec == b.x_dec &&
            a.xg_dec == b.xg_dec && a.qkv_dec == b.qkv_dec && a.attn_dec == b.attn_dec && a.h_dec == b.h_dec && a.logits == b.logits &&
            a.next_tok == b.next_tok && a.out_ids == b.out_ids && a.ssq == b.ssq && a.sk_scratch == b.sk_scratch &&
            a.sk_counters == b.sk_counters && a.stamps == b.stamps && a.stamp_next == b.stamp_next && a.prof_acc == b.prof_acc &&
            a.stamp_scratch == b.stamp_scratch && a.lp_tok == b.lp_tok && a.lp_top == b.lp_top && a.lp_ids == b.lp_ids &&
-           a.lp_k == b.lp_k && a.proc_prompt == b.proc_prompt && a.proc_bad == b.proc_bad && a.proc_logits == b.proc_logits && a.fan_n == b.fan_n && a.fan_P == b.fan_P;
+           a.lp_k == b.lp_k && a.proc_prompt == b.proc_prompt && a.proc_bad == b.proc_bad && a.proc_logits == b.proc_logits && a.fan_n == b.fan_n && a.fan_P == b.fan_P &&
+           a.cn_state_off == b.cn_state_off && a.cn_edge_tok == b.cn_edge_tok && a.cn_edge_next == b.cn_edge_next &&
+           a.cn_default_next == b.cn_default_next && a.cn_states == b.cn_states;
 }
 
 // The buffers of the device beam loop (vc_generate_beam): the fixed-size part carved from m->bm_state, the tables from m->bm_tab /
@@ -201,7 +208,8 @@ inline bool operator==(const BeamLoop& a, const BeamLoop& b) {
 //       (functions of the config), the RS_* / B?_* record layouts, the `advance` constant of a captured step (3);
 //   (b) a member of the key: every LoopView member (the stream, the caches with es / capR / capS, the RowState records, the key mask
 //       pointer — nullptr for an unmasked step — and its stride, the per-step buffers, out_ids, the split-K scratch and counters, the
-//       timing pointers, the log-prob slabs with lp_k, the processor buffers), nrows, and for a beam step every BeamLoop member (the
+//       timing pointers, the log-prob slabs with lp_k, the processor buffers, the token automaton's tables with their state
+//       count), nrows, and for a beam step every BeamLoop member (the
 //       state pointers, the tables, the staging with its span capacity, B, n, cap_new); or
 //   (c) derived from (a) and (b) alone: the per-layer cache addresses (kc / vc, capR, capS, es, heads, hd), the attention's cache
 //       format (split_G, es), the GEMV pass layout (split_G, nrows), which launches the tail holds (lp_tok, proc_logits, has_beam),
@@ -370,6 +378,13 @@ struct vc_model {
     int gproc_eos[VC_MAX_EOS_EXTRA] = {};
     std::vector<int> gproc_bad;
     Buf proc_prompt, proc_bad, proc_logits;
+    // token automaton of the NEXT vc_generate (vc_request_constraint; one-shot), validated and copied from the caller's tables:
+    // state_off [S + 1] | edge_tok [E] | edge_next [E] | default_next [S] in one vector, uploaded as it stands to cn_tab when a
+    // call is armed.  Such a call runs on the session's loop with the processor launch in its steps (GenParams::cn), whose fourth
+    // phase masks the processed rows
+    std::vector<int> gcn_tab;
+    int gcn_S = 0, gcn_E = 0;
+    Buf cn_tab;
     // prompt-lookup speculation of the NEXT vc_generate* (vc_request_speculation; one-shot): k drafts per step, the largest n-gram,
     // the caller's lookup ids [B][spec_lookup_stride] with their lengths.  A call that serves it runs verify steps (STEP_SPEC) over
     // B * (k + 1) rows on the sp_* buffers; spec_counters [B][4] (steps, tokens, drafted, accepted) of the last call when spec_last.
@@ -462,6 +477,10 @@ static void clear_logits_processors_request(vc_model* m) {
     m->gproc = false;
     m->gproc_bad.clear();
 }
+static void clear_constraint_request(vc_model* m) {
+    m->gcn_tab.clear();
+    m->gcn_S = m->gcn_E = 0;
+}
 static void clear_speculation_request(vc_model* m) {
     m->spec_k = m->spec_ngram = m->spec_B = m->spec_lookup_stride = 0;
     m->spec_any = false;
@@ -490,6 +509,7 @@ struct OneShotReset {
         clear_score_request(m);
         clear_generate_logprobs_request(m);
         clear_logits_processors_request(m);
+        clear_constraint_request(m);
         clear_speculation_request(m);
         m->fan_n = 0;
         m->fan_rows = 0;

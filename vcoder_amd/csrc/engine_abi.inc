@@ -188,7 +188,7 @@ VC_API void vc_model_destroy(vc_model* m) {
                    &m->s_q, &m->s_attn, &m->s_h, &m->s_kc, &m->s_vc, &m->s_xl, &m->pp_src, &m->pp_sq, &m->pp_tmp, &m->pp_out,
                    &m->pp_tab, &m->pp_f32, &m->kmask, &m->hidden_tmp, &m->attn_q, &m->a8, &m->a8_scale, &m->p_ssq, &m->p_rstd, &m->k_pre,
                    &m->ext_tok, &m->sc_idx, &m->sc_lp, &m->sc_xn, &m->sc_logits, &m->sc_tlp, &m->sc_tid, &m->lp_tok, &m->lp_top,
-                   &m->lp_ids, &m->proc_prompt, &m->proc_bad, &m->proc_logits, &m->bm_state, &m->bm_tab, &m->bm_den, &m->bm_tmp, &m->fan_P,
+                   &m->lp_ids, &m->proc_prompt, &m->proc_bad, &m->proc_logits, &m->cn_tab, &m->bm_state, &m->bm_tab, &m->bm_den, &m->bm_tmp, &m->fan_P,
                    &m->fan_px[0], &m->fan_px[1], &m->fan_px[2], &m->sp_x, &m->sp_xg, &m->sp_qkv, &m->sp_attn, &m->sp_h, &m->sp_logits, &m->sp_ssq,
                    &m->sp_tok, &m->sp_state, &m->sp_lookup, &m->sp_prompt, &m->sp_lp, &m->sp_ids, &m->sp_sel, &m->sp_chosen, &m->sp_proc})
         b->release();
@@ -780,6 +780,64 @@ VC_API int vc_request_logits_processors(vc_model* m, const vc_logits_processors*
         for (int j = 0; j < e[0]; ++j) e[1 + j] = p->bad_words_ids[off + j];
         off += e[0];
     }
+    return VC_OK;
+}
+
+/* Token automaton of the NEXT vc_generate call (one-shot): constrained decoding on the device, behind the logits processors.
+ * a == NULL cancels.  See include/vcoder_hip.h. */
+VC_API int vc_request_constraint(vc_model* m, const vc_token_automaton* a) {
+    if (!m) return VC_ERR_INVALID;
+    if (!a) {
+        clear_constraint_request(m);
+        return VC_OK;
+    }
+    // (a refusal leaves a pending request as it was: nothing touched)
+    auto refuse = [&](const char* why) {
+        m->ctx->err = std::string("vc_request_constraint: ") + why;
+        return VC_ERR_INVALID;
+    };
+    const int S = a->n_states, E = a->n_edges;
+    if (S < 1 || S > VC_MAX_AUTOMATON_STATES || E < 0 || E > VC_MAX_AUTOMATON_EDGES) return refuse("1 .. 65536 states and at most 1 << 20 edges");
+    if (!a->state_off || !a->default_next || (E > 0 && (!a->edge_tok || !a->edge_next))) return refuse("a table is missing");
+    if (a->state_off[0] != 0 || a->state_off[S] != E) return refuse("state_off must run from 0 to n_edges");
+    for (int s = 0; s < S; ++s) {
+        const int e0 = a->state_off[s], e1 = a->state_off[s + 1];
+        if (e0 > e1 || e1 > E) return refuse("state_off must not fall");
+        for (int e = e0 + 1; e < e1; ++e)
+            if (a->edge_tok[e - 1] >= a->edge_tok[e]) return refuse("the edge ids of a state must be ascending and unique");
+        if (a->default_next[s] < -1 || a->default_next[s] >= S) return refuse("default_next outside [-1, n_states)");
+    }
+    for (int e = 0; e < E; ++e)
+        if (a->edge_next[e] < -1 || a->edge_next[e] >= S) return refuse("edge_next outside [-1, n_states)");
+    {   // every state reachable from 0 allows at least one token
+        std::vector<char> seen((size_t)S, 0);
+        std::vector<int> todo{0};
+        seen[0] = 1;
+        while (!todo.empty()) {
+            const int s = todo.back();
+            todo.pop_back();
+            const int e0 = a->state_off[s], e1 = a->state_off[s + 1];
+            if (e0 == e1 && a->default_next[s] < 0) return refuse("a reachable state allows no token");
+            auto visit = [&](int t) {
+                if (t >= 0 && !seen[t]) {
+                    seen[t] = 1;
+                    todo.push_back(t);
+                }
+            };
+            for (int e = e0; e < e1; ++e) visit(a->edge_next[e]);
+            visit(a->default_next[s]);
+        }
+    }
+    m->gcn_tab.resize((size_t)2 * S + 1 + 2 * (size_t)E);
+    int* t = m->gcn_tab.data();
+    std::copy(a->state_off, a->state_off + S + 1, t);
+    if (E > 0) {
+        std::copy(a->edge_tok, a->edge_tok + E, t + S + 1);
+        std::copy(a->edge_next, a->edge_next + E, t + S + 1 + E);
+    }
+    std::copy(a->default_next, a->default_next + S, t + S + 1 + 2 * (size_t)E);
+    m->gcn_S = S;
+    m->gcn_E = E;
     return VC_OK;
 }
 

@@ -497,6 +497,11 @@ void enqueue_step_logprobs(vc_model* m, const LoopView& v, const float* logits, 
 const float* enqueue_step_processors(vc_model* m, const LoopView& v, const float* logits, int nrows) {
     if (!v.proc_logits) return logits;
     LogitsProcessArgs a{logits, m->c.vocab, v.proc_logits, m->c.vocab, v.rows, v.proc_prompt, v.out_ids, v.proc_bad, m->c.vocab};
+    a.cn_state_off = v.cn_state_off;   // (nullptr / 0 without a token automaton)
+    a.cn_edge_tok = v.cn_edge_tok;
+    a.cn_edge_next = v.cn_edge_next;
+    a.cn_default_next = v.cn_default_next;
+    a.cn_states = v.cn_states;
     launch_logits_process(a, nrows, v.st);
     return v.proc_logits;
 }
@@ -942,6 +947,7 @@ struct GenParams {  // what a generate() call asks for (HF GenerationMixin subse
     int proc = 0, proc_ngram = 0, proc_minnew = 0, proc_nbad = 0, proc_neos = 0, proc_T = 0;
     float proc_penalty = 1.f;
     int proc_eos[VC_MAX_EOS_EXTRA] = {};
+    int cn = 0;   // a token automaton masks the rows (vc_request_constraint): RS_CN_ON; implies proc — the launch that carries it
 };
 
 uint32_t mix_seed(uint64_t seed, uint32_t row, uint32_t salt) {
@@ -986,6 +992,7 @@ void fill_rows(int* rec, int B, const GenParams& g, int pos, const int* tail /*[
             r[RS_LP_NEOS] = g.proc_neos;
             for (int e = 0; e < g.proc_neos; ++e) r[RS_LP_EOS + e] = g.proc_eos[e];
         }
+        r[RS_CN_ON] = g.cn;   // (RS_CN_STATE / RS_CN_POS zero: the start state, nothing consumed)
     }
 }
 

@@ -602,7 +602,7 @@ std::unique_lock<std::mutex> prefill_on_session(vc_model* m, const int64_t* ids,
 // behind the prefill only): greedy and no processors — or any selection, with vc_request_speculation_selection — the bf16 step,
 // B * (k + 1) rows in one weight pass
 bool spec_request_served(const vc_model* m, const GenParams& g, int B) {
-    return m->spec_k > 0 && (m->spec_any || (!g.do_sample && !g.proc)) && m->precision == 0 && B * (m->spec_k + 1) <= SPEC_MAX_ROWS;
+    return m->spec_k > 0 && !g.cn && (m->spec_any || (!g.do_sample && !g.proc)) && m->precision == 0 && B * (m->spec_k + 1) <= SPEC_MAX_ROWS;
 }
 
 // generate() on the session's own loop: prefill, then max_new - 1 graph-replayed (strict: eagerly enqueued) decode steps — or, with a
@@ -652,11 +652,24 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
         ids32.resize((size_t)B * T);
         for (size_t i = 0; i < ids32.size(); ++i) ids32[i] = (int)std::max<int64_t>(std::min<int64_t>(ids[i], INT32_MAX), INT32_MIN);
         HIPCHK(hipMemcpyAsync(m->proc_prompt.p, ids32.data(), ids32.size() * 4, hipMemcpyHostToDevice, m->st));
-        HIPCHK(hipMemcpyAsync(m->proc_bad.p, m->gproc_bad.data(), m->gproc_bad.size() * 4, hipMemcpyHostToDevice, m->st));
+        if (!m->gproc_bad.empty())   // (a call with a token automaton alone brings no table: RS_LP_NBAD is 0)
+            HIPCHK(hipMemcpyAsync(m->proc_bad.p, m->gproc_bad.data(), m->gproc_bad.size() * 4, hipMemcpyHostToDevice, m->st));
         // (both host vectors live until the synchronize behind the step-0 selection)
         v.proc_prompt = m->proc_prompt.as<int>();
         v.proc_bad = m->proc_bad.as<int>();
         v.proc_logits = m->proc_logits.as<float>();
+    }
+    // vc_request_constraint: the processor launch masks the processed rows by the rows' automaton states (RS_CN_*)
+    if (g.cn) {
+        const size_t S = (size_t)m->gcn_S, E = (size_t)m->gcn_E;
+        REQUIRE(g.proc && m->gcn_tab.size() == 2 * S + 1 + 2 * E, VC_ERR_STATE, "token automaton tables of %zu ints", m->gcn_tab.size());
+        m->cn_tab.ensure(m->gcn_tab.size() * 4);
+        HIPCHK(hipMemcpyAsync(m->cn_tab.p, m->gcn_tab.data(), m->gcn_tab.size() * 4, hipMemcpyHostToDevice, m->st));   // (lives as above)
+        v.cn_state_off = m->cn_tab.as<int>();
+        v.cn_edge_tok = v.cn_state_off + S + 1;
+        v.cn_edge_next = v.cn_edge_tok + E;
+        v.cn_default_next = v.cn_edge_next + E;
+        v.cn_states = m->gcn_S;
     }
     // the stop-sequence tails of the loop's rows on the host (row r: prompt r / fan)
     std::vector<int> tail_rows;
@@ -1202,6 +1215,13 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
         for (int e = 0; e < m->gproc_neos; ++e) g.proc_eos[e] = m->gproc_eos[e];
         g.proc_T = T;
     }
+    // vc_request_constraint: likewise, and the processor launch is what applies it — also when no processor is on (the RS_LP_* slots
+    // of such a call hold their off values).  A pending vc_request_speculation is not served beside it (spec_request_served)
+    if (!m->gcn_tab.empty()) {
+        g.proc = 1;
+        g.proc_T = T;
+        g.cn = 1;
+    }
     // vc_request_speculation: a served request runs on the session's own loop (the pool's steps are plain ones)
     REQUIRE(m->spec_k == 0 || m->spec_lookup.empty() || m->spec_B == B, VC_ERR_INVALID, "lookup ids given for %d sequences, batch is %d",
             m->spec_B, B);
@@ -1263,6 +1283,7 @@ VC_API int vc_generate_beam(vc_model* m, const int64_t* ids, int B, int T, const
     REQUIRE(m->precision != 1, VC_ERR_STATE, "strict mode keeps beam search on the host loop (vc_decode_step + vc_reorder_cache)");
     REQUIRE(!m->glp_tok, VC_ERR_STATE, "per-token log-probs are not implemented for beam search: a vc_request_generate_logprobs is pending");
     REQUIRE(!m->gproc, VC_ERR_STATE, "logits processors are not implemented in the device beam loop: a vc_request_logits_processors is pending");
+    REQUIRE(m->gcn_tab.empty(), VC_ERR_STATE, "constrained decoding is not implemented in the device beam loop: a vc_request_constraint is pending");
     m->spec_last = false;   // (a pending vc_request_speculation is not served by beam search)
     {   // the tail permute moves 16-byte chunks of a cache row: the element size the prefill below will give the session's cache
         const int es = m->precision == 2 ? split_kv_es() : step_kv_es(m);

@@ -152,14 +152,28 @@ VCK_EXPORT void vck_kv_permute_tail(void* kcache, void* vcache, void* tmp, const
 }
 VCK_EXPORT void vck_logits_process(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
                                    const int* out_ids, const int* bad_words, int nrows, int V, void* stream) {
+    LogitsProcessArgs a{logits, ldl, out, ldo, const_cast<int*>(rows), prompt_ids, out_ids, bad_words, V};   // (no tables: read only)
+    launch_logits_process(a, nrows, S(stream));
+}
+VCK_EXPORT void vck_logits_process_constrained(const float* logits, int ldl, float* out, int ldo, int* rows, const int* prompt_ids,
+                                               const int* out_ids, const int* bad_words, const int* state_off, const int* edge_tok,
+                                               const int* edge_next, const int* default_next, int n_states, int nrows, int V,
+                                               void* stream) {
     LogitsProcessArgs a{logits, ldl, out, ldo, rows, prompt_ids, out_ids, bad_words, V};
+    if (state_off && edge_tok && edge_next && default_next && n_states > 0) {
+        a.cn_state_off = state_off;
+        a.cn_edge_tok = edge_tok;
+        a.cn_edge_next = edge_next;
+        a.cn_default_next = default_next;
+        a.cn_states = n_states;
+    }
     launch_logits_process(a, nrows, S(stream));
 }
 VCK_EXPORT void vck_logits_process_verify(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
                                           const int* out_ids, const int* bad_words, const int* tok, const int* nq, int B, int Q, int V,
                                           void* stream) {
     if (B < 1 || Q < 1) return;   // nothing is launched, nothing written
-    LogitsProcessArgs a{logits, ldl, out, ldo, rows, prompt_ids, out_ids, bad_words, V, Q, tok, nq};
+    LogitsProcessArgs a{logits, ldl, out, ldo, const_cast<int*>(rows), prompt_ids, out_ids, bad_words, V, Q, tok, nq};
     launch_logits_process(a, B * Q, S(stream));
 }
 VCK_EXPORT void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w,

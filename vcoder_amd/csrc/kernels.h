@@ -438,11 +438,18 @@ enum RowStateField : int {
     RS_LP_NBAD = 100,     // the first so many sequences of LogitsProcessArgs::bad_words apply to the row (<= VC_MAX_BAD_WORDS)
     RS_LP_NEOS = 101,     // ids in RS_LP_EOS: the EOS ids beside RS_EOS (<= VC_MAX_EOS_EXTRA)
     RS_LP_EOS = 102,
+    // the token automaton of the row (logits_process_kernel phase 4; LogitsProcessArgs::cn_*).  The row's switch and its state travel
+    // here, not in a buffer of the view: a record is armed once per call (zeroes: off / state 0 at token 0), rows of one launch
+    // differ, and a step needs no further address.  RS_CN_STATE / RS_CN_POS are a cache of walk(out_ids[0 .. RS_STEP)) that the
+    // kernel itself advances: any RS_CN_POS <= RS_STEP with the state behind that many ids gives the same row
+    RS_CN_ON = 110,       // != 0: the automaton applies to the row
+    RS_CN_STATE = 111,    // state behind out_ids[0 .. RS_CN_POS) (-1: dead)
+    RS_CN_POS = 112,      // ids of the row the state has consumed
     RS_STRIDE = 128,
 };
 constexpr int VC_MAX_BAD_WORDS = 32, VC_MAX_BAD_WORD_LEN = 8, VC_MAX_EOS_EXTRA = 8;
 static_assert(RS_STOP + VC_MAX_STOP * (1 + VC_MAX_STOP_LEN) <= RS_LP_NGRAM, "row record overflow");
-static_assert(RS_LP_EOS + VC_MAX_EOS_EXTRA <= RS_STRIDE, "row record overflow");
+static_assert(RS_LP_EOS + VC_MAX_EOS_EXTRA <= RS_CN_ON && RS_CN_POS < RS_STRIDE, "row record overflow");
 
 // selection (greedy / sampled) + EOS / stop bookkeeping + embedding of the selected token (fp32 residual row x, RMSNorm
 // partials ssq, first GEMV operand xg = bf16(x * xg_w)) + per-row step / position advance: one workgroup per row
@@ -558,12 +565,16 @@ void launch_topk_logprob(const TopkLogprobArgs& a, int nrows, int lds_floats, hi
 // ids generated so far; ids outside [0, V) are skipped), then -inf for what NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor
 // and MinNewTokensLengthLogitsProcessor ban.  One workgroup per row; parameters in the row's record (RS_LP_*), so rows of one
 // launch may differ; a row with everything off is copied.  The raw row is only read; pad columns of `out` are not written.
+// With the cn_* tables (a token automaton, vcoder_amd/constraints.py: CSR edges per state, ascending unique ids) a fourth phase masks
+// the processed row of every record with RS_CN_ON: the state is advanced over the ids emitted since it was stored and written back
+// (the only write to the records), then every id without an edge becomes -inf — nothing in a state whose default_next >= 0,
+// everything in the dead state (-1, or a state outside [0, cn_states)).  Unfinished rows of the plain form only.
 struct LogitsProcessArgs {
     const float* logits;     // [nrows, ldl] fp32: the raw rows
     int ldl;
     float* out;              // [nrows, ldo] fp32: the processed rows
     int ldo;
-    const int* rows;         // [nrows][RS_STRIDE]
+    int* rows;               // [nrows][RS_STRIDE]; written only with the cn_* tables (RS_CN_STATE / RS_CN_POS)
     const int* prompt_ids;   // the call's prompt ids; row r: prompt_ids[RS_LP_HIST_OFF .. + RS_LP_HIST_LEN)
     const int* out_ids;      // base of the id store; row r: out_ids[RS_OUT_OFF .. + RS_STEP)
     const int* bad_words;    // [VC_MAX_BAD_WORDS][1 + VC_MAX_BAD_WORD_LEN]: (length, ids); nullptr when no row has RS_LP_NBAD > 0
@@ -574,6 +585,12 @@ struct LogitsProcessArgs {
     int Q;
     const int* tok;          // [B * Q] the draft kernel's token rows
     const int* nq;           // [B]
+    // the token automaton (all nullptr / 0: off — the launch then writes what it wrote without these members)
+    const int* cn_state_off;     // [cn_states + 1]
+    const int* cn_edge_tok;      // [E] ascending and unique within a state
+    const int* cn_edge_next;     // [E] in [-1, cn_states)
+    const int* cn_default_next;  // [cn_states] in [-1, cn_states)
+    int cn_states;
 };
 void launch_logits_process(const LogitsProcessArgs& a, int nrows, hipStream_t s);
 // one beam-search step of B sequences of n beams each (rows b * n .. b * n + n - 1; R = B * n <= 16) behind a launch_topk_logprob

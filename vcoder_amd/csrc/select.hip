@@ -703,7 +703,7 @@ void launch_topk_logprob(const TopkLogprobArgs& a0, int nrows, int lds_floats, h
 // min_new_tokens= / min_length=); [HF] generation/logits_process.py of Transformers 4.31) ------------------------------------------
 // One workgroup of 1024 threads per row writes a processed copy of the raw fp32 row; the raw row is only read (the log-prob kernel
 // keeps scoring it).  Every processor touches a sparse set of entries chosen by the row's own history h = the caller's prompt ids
-// (placeholders and all: HF counts the un-spliced input_ids) followed by out_ids[0 .. RS_STEP), of length L.  Three phases, a
+// (placeholders and all: HF counts the un-spliced input_ids) followed by out_ids[0 .. RS_STEP), of length L.  Four phases, a
 // workgroup barrier between them:
 //   1. copy: 16-byte accesses over the part of the row where source and destination are both aligned, scalar elsewhere
 //   2. RepetitionPenaltyLogitsProcessor: out[t] = raw[t] < 0 ? raw[t] * p : raw[t] / p for every history id t in [0, V) — read from
@@ -715,12 +715,35 @@ void launch_topk_logprob(const TopkLogprobArgs& a0, int nrows, int lds_floats, h
 //      NoBadWordsLogitsProcessor: sequence q of the call's table (thread q): one id — always; longer — its last id when the
 //        history ends with the ids in front of it (a tail that may reach into the prompt)
 //      MinNewTokensLengthLogitsProcessor / MinLengthLogitsProcessor (folded on the host): RS_EOS and RS_LP_EOS while RS_STEP < m
+//   4. the token automaton (LogitsProcessArgs::cn_*; records with RS_CN_ON, unfinished, plain form): thread 0 advances the row's
+//      state over out_ids[RS_CN_POS .. RS_STEP) — a binary search in the state's edge slice per id, else default_next — stores
+//      (state, RS_STEP) back and broadcasts it through LDS.  A free-text state (default_next >= 0) masks nothing; the dead state
+//      fills [0, V) with -inf; otherwise the workgroup sets one bit per allowed id in an LDS bitmap (the state's edge slice read once,
+//      a run of consecutive edges per thread; two barriers), and every thread takes 4-float chunks of `out` (16-byte accesses over the aligned part): a chunk
+//      whose ids are all allowed is not touched, one with none is stored as -inf without a load, the rest is read, masked, stored.
+//      No cap on a state's edges; a thread touches its own chunks only, behind the barrier that ends phase 3.  A vocabulary above
+//      32 * CN_BITMAP_WORDS ids takes lower_bound(chunk start) in the sorted slice per chunk instead of the bitmap.
 // Ids outside [0, V) are never written.  Rows are independent; pad columns V .. ldo are not touched.
 // The verify form (p.Q > 0; prompt-lookup speculation): workgroup r = b * Q + j, j < nq[b], processes logits row r under record b as
 // the plain loop would j steps later, if the j drafts in front of the row are accepted — the history is followed by the drafts
 // tok[b * Q + 1 .. b * Q + j] (tok[b * Q] is out_ids[RS_STEP - 1], in the store already) and MinNewTokens compares RS_STEP + j.  Rows
 // j >= nq[b] write nothing.  A row behind a rejected draft holds what nobody reads.
 constexpr int LPROC_THREADS = 1024;
+constexpr int CN_BITMAP_WORDS = 8192;   // 32 KB of LDS: one bit per id of a vocabulary of up to 262144
+// the token automaton of phase 4: first edge of [e0, e1) whose id is >= t; the state behind `tok` in state `st`
+VC_DEV int cn_lower_bound(const int* et, int e0, int e1, int t) {
+    while (e0 < e1) {
+        const int mid = e0 + ((e1 - e0) >> 1);
+        if (et[mid] < t) e0 = mid + 1;
+        else e1 = mid;
+    }
+    return e0;
+}
+VC_DEV int cn_step(const LogitsProcessArgs& p, int st, int tok) {
+    if ((unsigned)st >= (unsigned)p.cn_states) return -1;
+    const int e1 = p.cn_state_off[st + 1], k = cn_lower_bound(p.cn_edge_tok, p.cn_state_off[st], e1, tok);
+    return k < e1 && p.cn_edge_tok[k] == tok ? p.cn_edge_next[k] : p.cn_default_next[st];
+}
 __global__ __launch_bounds__(LPROC_THREADS) void logits_process_kernel(LogitsProcessArgs p) {
     const int r = blockIdx.x, tid = threadIdx.x;
     const int rec = p.Q > 0 ? r / p.Q : r, nd = p.Q > 0 ? r % p.Q : 0;   // the row's record; the drafts behind its history
@@ -783,6 +806,101 @@ __global__ __launch_bounds__(LPROC_THREADS) void logits_process_kernel(LogitsPro
             if ((unsigned)t < (unsigned)V) out[t] = -INFINITY;
         }
     }
+    // ---- 4. the token automaton (PrefixConstrainedLogitsProcessor: behind MinNewTokensLength) --------------------------------------
+    if (p.cn_state_off == nullptr || p.Q > 0 || !rs[RS_CN_ON] || rs[RS_FINISHED]) return;   // (uniform over the workgroup)
+    __shared__ int cn_state_s;
+    if (tid == 0) {
+        // the stored state is a cache of walk(out_ids[0 .. RS_STEP)): advance it over the ids emitted since (one, as a rule)
+        int* rw = p.rows + (size_t)rec * RS_STRIDE;
+        int st = rs[RS_CN_STATE], pos = rs[RS_CN_POS];
+        if (pos < 0 || pos > step) st = 0, pos = 0;
+        for (; pos < step; ++pos) st = cn_step(p, st, hg[pos]);
+        if ((unsigned)st >= (unsigned)p.cn_states) st = -1;   // one dead state
+        rw[RS_CN_STATE] = st;
+        rw[RS_CN_POS] = step;
+        cn_state_s = st;
+    }
+    __syncthreads();   // the state; and phase 3's writes are behind it
+    const int st = cn_state_s;
+    const bool dead = (unsigned)st >= (unsigned)p.cn_states;
+    if (!dead && p.cn_default_next[st] >= 0) return;   // free text: the edges only redirect
+    const int e0 = dead ? 0 : p.cn_state_off[st], e1 = dead ? 0 : p.cn_state_off[st + 1];
+    const int* et = p.cn_edge_tok;
+    // in place on `out`: a thread owns the ids of its chunks, scalar in front of and behind the 16-byte aligned part of the row
+    const int omis = (int)((reinterpret_cast<uintptr_t>(out) >> 2) & 3);
+    const int ohead = min(V, (4 - omis) & 3), obody_end = ohead + ((V - ohead) & ~3);
+    const f32x4 ninf4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    if (((V + 31) >> 5) <= CN_BITMAP_WORDS) {
+        // the state's allowed ids as a bitmap in LDS: the edges are read once, with no search (a binary search per chunk is
+        // a chain of dependent loads: a launch of 20.6 us for 133 edges, against 8.6 us this way)
+        __shared__ unsigned allowed[CN_BITMAP_WORDS];
+        for (int w = tid; w < ((V + 31) >> 5); w += LPROC_THREADS) allowed[w] = 0u;
+        __syncthreads();
+        // a thread takes a run of consecutive edges and gathers the bits of one word before it touches LDS: the ids of a dense state
+        // fall into the same few words, and one atomic per edge would serialise a wave on them (33 us for 32000 edges, 20 us this way)
+        auto flush = [&](int w, unsigned bits) {
+            if (bits == 0u) return;
+#ifdef VC_EMU
+            __atomic_fetch_or(&allowed[w], bits, __ATOMIC_RELAXED);
+#else
+            atomicOr(&allowed[w], bits);
+#endif
+        };
+        const int per = (e1 - e0 + LPROC_THREADS - 1) / LPROC_THREADS;
+        const int eb = e0 + tid * per, ee = min(eb + per, e1);
+        int w = 0;
+        unsigned bits = 0u;
+        for (int e = eb; e < ee; ++e) {
+            const int t = et[e];
+            if ((unsigned)t >= (unsigned)V) continue;
+            if ((t >> 5) != w) {
+                flush(w, bits);
+                w = t >> 5;
+                bits = 0u;
+            }
+            bits |= 1u << (t & 31);
+        }
+        flush(w, bits);
+        __syncthreads();
+        auto ok = [&](int i) { return (allowed[i >> 5] >> (i & 31)) & 1u; };
+        if (tid < ohead && !ok(tid)) out[tid] = -INFINITY;
+        for (int i = ohead + tid * 4; i < obody_end; i += LPROC_THREADS * 4) {
+            const unsigned m = ok(i) | ok(i + 1) << 1 | ok(i + 2) << 2 | ok(i + 3) << 3;
+            if (m == 15u) continue;          // every id of the chunk is allowed: not touched
+            if (m == 0u) {                   // none: written without being read
+                st16f(out + i, ninf4);
+                continue;
+            }
+            f32x4 v = ld16f(out + i);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (!(m >> c & 1u)) v[c] = -INFINITY;
+            st16f(out + i, v);
+        }
+        if (obody_end + tid < V && !ok(obody_end + tid)) out[obody_end + tid] = -INFINITY;
+        return;
+    }
+    // a vocabulary the bitmap does not hold: every thread finds lower_bound(chunk start) in the sorted slice
+    auto one = [&](int i) {
+        const int k = cn_lower_bound(et, e0, e1, i);
+        if (k >= e1 || et[k] != i) out[i] = -INFINITY;
+    };
+    if (tid < ohead) one(tid);
+    for (int i = ohead + tid * 4; i < obody_end; i += LPROC_THREADS * 4) {
+        int k = cn_lower_bound(et, e0, e1, i);
+        if (k >= e1 || et[k] >= i + 4) {
+            st16f(out + i, ninf4);
+            continue;
+        }
+        f32x4 v = ld16f(out + i);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (k < e1 && et[k] == i + c) ++k;
+            else v[c] = -INFINITY;
+        }
+        st16f(out + i, v);
+    }
+    if (obody_end + tid < V) one(obody_end + tid);
 }
 void launch_logits_process(const LogitsProcessArgs& a, int nrows, hipStream_t s) {
     if (nrows <= 0) return;

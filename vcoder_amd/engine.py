@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _lib, synth
 from . import logits_processors as _lp
+from .constraints import TokenAutomaton
 from .config import VCoderConfig
 
 _ERRORS = {_lib.VC_ERR_INVALID: ValueError, _lib.VC_ERR_HIP: RuntimeError, _lib.VC_ERR_STATE: RuntimeError,
@@ -589,7 +590,7 @@ class HipEngine:
                  on_tokens=None, stream_every: int = 1, attention_mask=None, logprobs: bool = False,
                  top_logprobs: int = 0, processors=None, eos_extra: Sequence[int] = (), speculate: Optional[int] = None,
                  lookup_ngram: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False,
-                 speculate_selection: str = "greedy") -> np.ndarray:
+                 speculate_selection: str = "greedy", constraint: Optional[TokenAutomaton] = None) -> np.ndarray:
         """generate() on the device (vc_generate): greedy, or temperature / top-k / top-p sampling with a counter-based
         generator (same seed -> same tokens).  on_tokens(first_step, ids [B, n]) is called with every `stream_every` new
         columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32.
@@ -625,7 +626,15 @@ class HipEngine:
         its n rows (the fan-out attention), when the engine serves that: the bf16 precision mode, 2 <= n <= 8, and a prefill whose
         bits do not depend on the rows sharing its launch (at 7b dims: set_batch_invariant(True); the tiny models always).  Measured at 7b it
         wins for B = 2, n = 8 and loses for B = 1 (profiles/fanout_wall_times.md), hence not the default.  last_fanout = {"n",
-        "shared", "prefill_rows"} of the call (None without n > 1).  B n above MAX_BATCH: ValueError."""
+        "shared", "prefill_rows"} of the call (None without n > 1).  B n above MAX_BATCH: ValueError.
+        constraint (a constraints.TokenAutomaton; vc_request_constraint): every row walks the automaton from state 0 over the ids it
+        generates, and in front of every selection — behind the processors — the ids its state does not allow are -inf in the
+        processed row (a fourth phase of the processor kernel; the state lives in the row's record).  Greedy and sampled calls,
+        every precision mode, with or without processors, log-probs (of the raw rows), EOS ids, stop sequences, on_tokens and
+        num_return_sequences in both forms; the call runs on the session's own loop.  `speculate` is not served beside it
+        (last_speculation is None).  Any other type: ValueError."""
+        if constraint is not None and not isinstance(constraint, TokenAutomaton):
+            raise ValueError(f"constraint has to be a constraints.TokenAutomaton, but is {type(constraint).__name__}")
         ids = self._ids(input_ids)
         B, T = ids.shape
         self.last_speculation = None
@@ -674,7 +683,8 @@ class HipEngine:
                                            max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                            pad_token_id=pad_token_id, stop_sequences=stop_sequences, do_sample=do_sample,
                                            temperature=temperature, top_k=top_k, top_p=top_p, seed=seed + b0,
-                                           logprobs=want_lp, top_logprobs=K, processors=processors, eos_extra=eos_extra))
+                                           logprobs=want_lp, top_logprobs=K, processors=processors, eos_extra=eos_extra,
+                                           constraint=constraint))
                 lps.append(self.last_generate_logprobs)
                 lens.add(int(self.lib.vc_last_spliced_len(self._model)))
             if len(lens) > 1:
@@ -738,6 +748,16 @@ class HipEngine:
                 self.lib.vc_clear_attention_mask(self._model)
                 self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
                 raise
+        if constraint is not None:
+            cn_tabs = [np.ascontiguousarray(a, dtype=np.int32) for a in constraint.tables()]   # (alive until vc_request_constraint returns)
+            req_cn = _lib.TokenAutomatonTables(constraint.num_states, constraint.num_edges, *(a.ctypes.data_as(C.c_void_p) for a in cn_tabs))
+            try:
+                self._check(self.lib.vc_request_constraint(self._model, C.byref(req_cn)))
+            except BaseException:
+                self.lib.vc_clear_attention_mask(self._model)
+                self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
+                self.lib.vc_request_logits_processors(self._model, None)
+                raise
         if speculate is not None and B <= self.MAX_BATCH:
             lk_flat = lk_lens = None
             if look is not None:
@@ -752,6 +772,7 @@ class HipEngine:
                 self.lib.vc_clear_attention_mask(self._model)
                 self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
                 self.lib.vc_request_logits_processors(self._model, None)
+                self.lib.vc_request_constraint(self._model, None)
                 raise
         if nret > 1:
             try:
@@ -760,6 +781,7 @@ class HipEngine:
                 self.lib.vc_clear_attention_mask(self._model)
                 self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
                 self.lib.vc_request_logits_processors(self._model, None)
+                self.lib.vc_request_constraint(self._model, None)
                 self.lib.vc_request_speculation(self._model, 0, 0, None, None, 0)
                 raise
         self._check(self.lib.vc_generate(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev,

@@ -2,7 +2,9 @@
 min_length, min_new_tokens): their validation, the form the engine takes (vc_request_logits_processors) and ONE torch restatement in
 the order of Transformers 4.31's `_get_logits_processor` — repetition penalty, no-repeat n-gram, bad words, min length, min new
 tokens — which the host fallback loop of generate() and the host beam search apply.  The device loop runs the same processors in
-logits_process_kernel (csrc/select.hip).
+logits_process_kernel (csrc/select.hip).  `apply_prefix_constraint` restates PrefixConstrainedLogitsProcessor
+(generate(prefix_allowed_tokens_fn=) and, through TokenAutomaton.as_prefix_allowed_tokens_fn, generate(constraint=) on the host loops),
+which 4.31 puts behind all of them.
 
 A row's history is the caller's input_ids (image placeholders and all: HF counts the un-spliced ids) followed by the generated ids.
 History ids outside [0, vocab) are skipped: HF's RepetitionPenaltyLogitsProcessor would raise an index error on the negative image
@@ -107,4 +109,25 @@ def apply_torch(proc: LogitsProcessors, history, scores, prompt_len: int, eos_id
     eos = [int(e) for e in eos_ids if 0 <= int(e) < V]
     if eos and (L < proc.min_length or L - prompt_len < proc.min_new_tokens):
         out[:, eos] = ninf
+    return out
+
+
+def apply_prefix_constraint(fn, history, scores, num_beams: int = 1, skip=None):
+    """HF 4.31's PrefixConstrainedLogitsProcessor: row r of `scores` [R, V] keeps its value at the ids
+    fn(r // num_beams, history[r]) returns and is -inf elsewhere; an empty list leaves the row all -inf.  Ids outside [0, V) allow
+    nothing (HF would raise an index error).  Rows where `skip` [R] is true — finished rows, whose token is pad whatever their
+    scores are — are returned as they came.  -> a new tensor."""
+    import torch
+
+    R, V = scores.shape
+    out = torch.full_like(scores, float("-inf"))
+    for r in range(R):
+        if skip is not None and bool(skip[r]):
+            out[r] = scores[r]
+            continue
+        ids = [int(t) for t in fn(r // num_beams, history[r])]
+        ids = [t for t in ids if 0 <= t < V]
+        if ids:
+            idx = torch.tensor(ids, dtype=torch.long)
+            out[r, idx] = scores[r, idx]
     return out

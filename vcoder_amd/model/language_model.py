@@ -17,6 +17,7 @@ import numpy as np
 
 from ..config import VCoderConfig
 from .. import logits_processors as _lp
+from ..constraints import TokenAutomaton
 from ..engine import HipEngine
 from .projector import build_depth_projector, build_seg_projector, build_vision_projector
 from .vision_tower import build_vision_tower
@@ -455,7 +456,7 @@ class _HipCausalLMBase:
                  no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
                  bad_words_ids=None, processors_on_device: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
                  max_matching_ngram_size: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False,
-                 speculate_selection: str = "greedy", **kwargs):
+                 speculate_selection: str = "greedy", constraint=None, prefix_allowed_tokens_fn=None, **kwargs):
         """Returns cat(input_ids, new_ids) [B, T+n] int64 — the prompt part keeps its negative placeholder ids,
         callers slice `[:, T:]` (serve/cli.py:135).
 
@@ -483,6 +484,22 @@ class _HipCausalLMBase:
         log_softmax(logits) before the beam scores are added, as 4.31's beam_search.  Log-probs (output_logprobs / top_logprobs)
         stay those of the model's own distribution: the raw logits, before processors as well as before warpers.  Invalid values
         raise ValueError before the engine is touched.
+
+        constraint (a constraints.TokenAutomaton) / prefix_allowed_tokens_fn (HF's callable fn(batch_id, input_ids) -> allowed ids):
+        constrained decoding with HF 4.31's PrefixConstrainedLogitsProcessor semantics — behind the processors above, in front of
+        the warpers, the ids the callable does not return are -inf (an empty list: the whole row).  A callable cannot run inside a
+        captured step, so prefix_allowed_tokens_fn always takes the host loops.  `constraint` states the same restriction as a
+        deterministic automaton over token ids ("one of these strings": TokenAutomaton.from_sequences; "a separated list drawn
+        from these classes": from_list; raw tables: from_edges) whose state the device loop keeps per row: a fourth phase of the
+        processor kernel masks the processed row in front of every selection — greedy and sampled calls, every precision mode,
+        with or without the processors, with log-probs (still those of the raw rows), EOS ids, stop sequences, a streamer and
+        num_return_sequences in both forms; the call runs on the session's own loop.  Its definition is
+        constraint.as_prefix_allowed_tokens_fn(T): whatever takes the host loop — processors_on_device=False, a stopping criterion
+        that needs host code, num_beams > 1 (`_beam_search`, which applies it to log_softmax(logits) before the beam scores are
+        added) — runs under that callable and returns the same tensor.  The automaton starts at the first generated token; rows
+        that are finished are not constrained (they emit pad).  prompt_lookup_num_tokens is not served beside a constraint (the
+        call runs as without it, `speculation` is None).  Both arguments together, or a wrong type, raise ValueError before the
+        engine is touched; without either every call takes the path it took.
 
         num_beams = n > 1: beam search (HF 4.31's beam_search + BeamSearchScorer; `length_penalty`, `early_stopping` as keyword
         arguments).  Without sampling and stopping criteria, outside strict mode and with B * n <= 16 rows it runs inside the device
@@ -564,6 +581,12 @@ class _HipCausalLMBase:
                 raise ValueError(f"max_matching_ngram_size must be in 1 .. 4, got {max_matching_ngram_size!r}")
         if speculate_selection not in ("greedy", "any"):
             raise ValueError(f"speculate_selection must be 'greedy' or 'any', got {speculate_selection!r}")
+        if constraint is not None and prefix_allowed_tokens_fn is not None:
+            raise ValueError("`constraint` and `prefix_allowed_tokens_fn` state the same thing: pass one of them")
+        if constraint is not None and not isinstance(constraint, TokenAutomaton):
+            raise ValueError(f"`constraint` has to be a vcoder_amd.constraints.TokenAutomaton, but is {type(constraint).__name__}")
+        if prefix_allowed_tokens_fn is not None and not callable(prefix_allowed_tokens_fn):
+            raise ValueError(f"`prefix_allowed_tokens_fn` has to be callable, but is {type(prefix_allowed_tokens_fn).__name__}")
         nrs = int(num_return_sequences)
         if nrs < 1:
             raise ValueError(f"`num_return_sequences` has to be at least 1, got {num_return_sequences!r}")
@@ -599,12 +622,16 @@ class _HipCausalLMBase:
             # plain beam search (what the reference's eval loaders ask for) runs inside the device loop; beam-sample, stopping
             # criteria, strict mode and more rows than a replica decodes keep the host loop
             # (logits processors too: the device beam loop does not carry them)
+            allowed_fn = prefix_allowed_tokens_fn
+            if constraint is not None:
+                allowed_fn = constraint.as_prefix_allowed_tokens_fn(input_ids.shape[1], self.config.vocab_size)
             on_device = (kwargs.get("beam_on_device", True) and sample is None and not stopping_criteria and proc is None
-                         and self.engine.precision != "strict" and input_ids.shape[0] * int(num_beams) <= self.engine.MAX_BATCH)
+                         and allowed_fn is None and self.engine.precision != "strict" and input_ids.shape[0] * int(num_beams) <= self.engine.MAX_BATCH)
             if on_device:
                 seqs, scores = self._beam_search_device(*beam_args, *beam_kw)
             else:
-                seqs, scores = self._beam_search(*beam_args, stopping_criteria, *beam_kw, sample, return_scores=True, processors=proc)
+                seqs, scores = self._beam_search(*beam_args, stopping_criteria, *beam_kw, sample, return_scores=True, processors=proc,
+                                                 allowed_fn=allowed_fn)
             return GenerateOutput(sequences=seqs, sequences_scores=scores) if as_dict else seqs
         T = input_ids.shape[1]
         B = input_ids.shape[0]
@@ -642,6 +669,14 @@ class _HipCausalLMBase:
         on_device = stops is not None and len(stops) <= 8
         if proc is not None:   # what the device kernel does not hold, or the caller's wish: the host loop applies them
             on_device = on_device and bool(processors_on_device) and proc.fits_device() and len(eos_more) <= _lp.MAX_EOS_EXTRA
+        # a callable runs on the host; an automaton where the call is device-served anyway, else as its own callable
+        if prefix_allowed_tokens_fn is not None:
+            on_device = False
+        if constraint is not None:
+            on_device = on_device and bool(processors_on_device) and len(eos_more) <= _lp.MAX_EOS_EXTRA
+        allowed_fn = prefix_allowed_tokens_fn
+        if constraint is not None and not on_device:
+            allowed_fn = constraint.as_prefix_allowed_tokens_fn(T, self.config.vocab_size)
         if nrs > 1:
             rep = np.repeat(np.arange(B), nrs)   # rows b n + j, as HF's _expand_inputs_for_generation
 
@@ -679,7 +714,7 @@ class _HipCausalLMBase:
                                        eos_extra=eos_more if proc is not None else (),
                                        speculate=None if prompt_lookup_num_tokens is None else int(prompt_lookup_num_tokens),
                                        lookup_ngram=int(max_matching_ngram_size), lookup_ids=lookup_ids,
-                                       speculate_selection=speculate_selection,
+                                       speculate_selection=speculate_selection, constraint=constraint,
                                        **(dict(num_return_sequences=nrs, fan_out=bool(fan_out)) if nrs > 1 else {}))
             self._generation += 1
             out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
@@ -705,6 +740,8 @@ class _HipCausalLMBase:
                 raw = scores
                 if proc is not None:   # in front of the warpers, as HF; the log-probs below stay those of `raw`
                     scores = _lp.apply_torch(proc, cur, scores, T, ([] if eos is None else [int(eos)]) + eos_more)
+                if allowed_fn is not None:   # behind the processors (4.31's order); finished rows emit pad: not constrained
+                    scores = _lp.apply_prefix_constraint(allowed_fn, cur, scores, skip=(unfinished == 0) if eos is not None else None)
                 if do_sample:
                     scores = scores / float(temperature)
                     if top_k and 0 < top_k < scores.shape[-1]:
@@ -798,7 +835,7 @@ class _HipCausalLMBase:
 
     def _beam_search(self, input_ids, images, segs, depths, num_beams, max_new_tokens, max_length, eos_token_id, pad_token_id,
                      attention_mask, stopping_criteria, length_penalty, early_stopping, len_counts_prompt, sample=None,
-                     return_scores=False, processors=None):
+                     return_scores=False, processors=None, allowed_fn=None):
         """`generate(num_beams=n)` as the reference's eval loaders can ask for it (eval/model_seg_loader.py:129-139 forwards
         args.num_beams): every sequence is expanded to n beams (rows b*n .. b*n+n-1, as `_expand_inputs_for_generation`), the
         prefill and one cached decode step per token run on the engine, scoring is HF's — log-softmax of the fp32 logits plus
@@ -815,7 +852,9 @@ class _HipCausalLMBase:
         order changed after 4.31).
 
         processors (logits_processors.LogitsProcessors): applied to log_softmax(logits) over every beam row's ids before the running
-        beam score is added, as 4.31's beam_search / beam_sample apply their logits_processor."""
+        beam score is added, as 4.31's beam_search / beam_sample apply their logits_processor.  allowed_fn (a
+        prefix_allowed_tokens_fn): PrefixConstrainedLogitsProcessor behind them, fn(row // num_beams, ids of the beam row); the rows
+        of a sequence that is done are skipped (their tokens are pad)."""
         import torch
 
         ids_cpu = input_ids.detach().cpu() if hasattr(input_ids, "detach") else torch.as_tensor(np.asarray(input_ids))
@@ -888,6 +927,8 @@ class _HipCausalLMBase:
             scores = torch.log_softmax(logits, dim=-1)
             if processors is not None:
                 scores = _lp.apply_torch(processors, seqs, scores, T, eos_list)
+            if allowed_fn is not None:
+                scores = _lp.apply_prefix_constraint(allowed_fn, seqs, scores, nb, skip=[done[r // nb] for r in range(B * nb)])
             scores = scores + beam_scores[:, None]
             if sample is not None:
                 w = scores / sample["temperature"]
