@@ -386,6 +386,38 @@ int vc_request_fanout(vc_model* m, int n);
  * prompt rows the prefill ran over (B when served, B n otherwise)}.  VC_ERR_STATE when that call had no request. */
 int vc_last_fanout(vc_model* m, int32_t* out /* [3] */);
 
+/* Classifier-free guidance of the NEXT vc_generate or vc_prefill call (one-shot; HF's generate(guidance_scale=, negative_prompt_ids=),
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor).  neg_ids [B, Tn] int64: the negative prompt of every sequence of that call —
+ * rectangular, unpadded, placeholders allowed when neg_img (and neg_seg / neg_depth as the variant takes them) bring one image per
+ * sample, as the pixels of vc_generate; copied here.  The pixel pointers are borrowed: they must stay valid until that call returns.
+ * Every step scores the next token behind the prompt (raw row c) and behind the negative prompt (raw row u), both followed by the ids
+ * generated so far, and replaces c by
+ *     out = scale * (lc - lu) + lu,   lc = (c - max c) - log(sum(exp(c - max c))),  lu likewise      (fp32, no fused multiply-add)
+ * as the input of everything behind it: the logits processors (the repetition penalty's sign test runs on these log-domain values,
+ * as in HF, where guidance is the first processor), the token automaton, the warpers, the greedy or sampled selection.  Log-probs
+ * (vc_request_generate_logprobs) stay those of the raw row c.  EOS, stop sequences and max_new are decided on the conditional row.
+ * A served vc_generate runs on the session's own loop (whatever VC_POOL says) over 2 B rows in ONE weight pass per step — rows
+ * 0 .. B - 1 the call's sequences, rows B .. 2 B - 1 their followers behind the negative prompts, which take over every chosen token —
+ * after two prefills of B rows each (each prompt gets the bits a call of its own gives it); out_ids, the log-prob buffers and the
+ * callback's columns stay B rows wide.  A vc_generate is served in the bf16 precision mode (VC_ERR_STATE otherwise), every weight format, bf16 and
+ * e4m3 caches, greedy and sampled, with logits processors, a token automaton, log-probs, EOS, stop sequences and a callback; a pending
+ * vc_request_speculation is not served beside it, a pending vc_request_fanout makes the call fail (VC_ERR_STATE), vc_generate_beam
+ * refuses (VC_ERR_STATE).  The cache holds max(spliced prompt, spliced negative prompt) + max_new positions (VC_ERR_INVALID beyond
+ * max_position_embeddings).  Behind a served vc_generate the rows stand at different positions: vc_decode_step and vc_extend refuse
+ * (VC_ERR_STATE) until the next prefill.
+ * vc_prefill with a pending request builds the same state for a host loop, in EVERY precision mode (bf16, strict, split — the strict
+ * step then reads every row's own position); has_attention_mask applies to both prompts (the unequal-length quirk); logits_last
+ * receives [2 B, V] (the prompts' rows, then the negative prompts'), *S_out the prompts' spliced length, and vc_decode_step then takes 2 B tokens and returns 2 B rows, every row
+ * advancing its own position (tok == NULL, vc_extend, vc_rewind and vc_reorder_cache refuse; no labels / all-row logits / hidden
+ * states / attentions beside it).  The combination itself is then the host's (logits_processors.apply_guidance).
+ * A non-finite scale, B < 1, 2 B > 16 or Tn < 1: VC_ERR_INVALID, nothing changed; B other than that call's batch makes the call fail.
+ * neg_ids == NULL cancels.  Cleared when that call returns, also when it fails. */
+int vc_request_guidance(vc_model* m, float scale, const int64_t* neg_ids, int B, int Tn, const float* neg_img, const float* neg_seg,
+                        const float* neg_depth, int pixels_on_device);
+/* What the last vc_generate / vc_prefill of this session made of a guidance request: out = {1 (served), B, spliced length of the
+ * prompts, spliced length of the negative prompts}.  VC_ERR_STATE when that call had no request. */
+int vc_last_guidance(vc_model* m, int32_t* out /* [4] */);
+
 /* Logits processors of the NEXT vc_generate / vc_generate_greedy* call (one-shot), applied on the device in front of every selection
  * of the loop, in HF 4.31's order (generation/logits_process.py):
  *   repetition_penalty p   RepetitionPenaltyLogitsProcessor: every id t of the row's history gets raw[t] < 0 ? raw[t] * p : raw[t] / p

@@ -236,6 +236,23 @@ void vck_logits_process_constrained(const float* logits, int ldl, float* out, in
  * (min_new_tokens) — what vck_logits_process would write j steps later, had the drafts been emitted. */
 void vck_logits_process_verify(const float* logits, int ldl, float* out, int ldo, const int* rows, const int* prompt_ids,
                                const int* out_ids, const int* bad_words, const int* tok, const int* nq, int B, int Q, int V, void* stream);
+/* classifier-free guidance in front of the processors (generate(guidance_scale=, negative_prompt_ids=); HF's
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor): for every pair r of a raw conditional row c = cond[r] and a raw unconditional row
+ * u = uncond[r] (fp32, stride ldl, finite)
+ *   lc[t] = (c[t] - max c) - log(sum exp(c - max c)),   lu[t] likewise,   out[r, t] = g * (lc[t] - lu[t]) + lu[t]
+ * in fp32 with the product and the sum rounded separately (no fused multiply-add); g = the float whose bits are word 113 of the
+ * pair's RowState record (rows [nrows][vck_row_state_stride()]; word 0 == 0: the pair is skipped, nothing is written).
+ * scalars[r] = {max c, log sum c, max u, log sum u}: `out` is an element-wise function of the two rows and these four values, which
+ * numpy float32 reproduces bit for bit.  The raw rows are only read, nothing beyond column V - 1; columns V..ldo of `out` are not
+ * written; the rows need no alignment (16-byte accesses where all three allow them).  One workgroup per pair. */
+void vck_guidance_combine(const float* cond, const float* uncond, int ldl, float* out, int ldo, const int* rows, float* scalars,
+                          int nrows, int V, void* stream);
+/* the unconditional rows of a guided decode step follow their partners, behind vck_select_embed over rows 0 .. B - 1: row B + i takes
+ * row i's next_tok, x row [D], ssq row [npart] and xg row [D]; word 1 of its record (finished) becomes row i's, and its OWN words
+ * 2 / 3 (step / position) advance by advance & 1 / advance & 2.  A row B + i whose word 0 (active) is 0 and every row outside
+ * [B, 2 B) are not touched.  D a multiple of 8 (else nothing is launched).  One workgroup per follower. */
+void vck_guidance_follow(int* rows, int32_t* next_tok, float* x, float* ssq, uint16_t* xg, int B, int D, int npart, int advance,
+                         void* stream);
 void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w, uint16_t* xg, int B,
                           int D, int npart, void* stream);
 void vck_advance(int* step_dev, int* pos_dev, int* ctx_dev, void* stream);

@@ -733,6 +733,44 @@ def bench_logits_process():
             print(f"logits_process rows {rows:3d} V {V} {'all on, step %3d' % step if on else 'all off (copy) '}: {us:7.1f} us", flush=True)
 
 
+def bench_guidance_combine():
+    """guidance_combine_kernel over B pairs of [32000] fp32 rows laid out as a guided step's lm_head leaves them (2 B rows, the
+    unconditional ones behind the conditional ones), B = 1 / 8"""
+    V = 32000
+    stride = int(lib.vck_row_state_stride())
+    f32 = lambda x: int(torch.tensor(x, dtype=torch.float32).view(torch.int32))
+    for B in (1, 8):
+        lg = [torch.randn(2 * B, V, device=dev) * 3 for _ in range(4)]
+        out = torch.empty(B, V, device=dev)
+        sc = torch.empty(B, 4, device=dev)
+        rs = torch.zeros((B, stride), dtype=torch.int32, device=dev)
+        rs[:, 0] = 1                  # RS_ACTIVE
+        rs[:, 113] = f32(1.5)         # RS_GD_SCALE
+        it = [0]
+        def f():
+            it[0] += 1
+            x = lg[it[0] % 4]
+            lib.vck_guidance_combine(P(x), P(x[B:]), V, P(out), V, P(rs), P(sc), B, V, None)
+        print(f"guidance_combine pairs {B} V {V}: {timeit(f, iters=40):7.1f} us", flush=True)
+
+
+def bench_guidance_follow():
+    """guidance_follow_kernel at 7b dims (D 4096, 256 sum-of-squares partials): B = 1 / 8 followers"""
+    D, npart = 4096, 256
+    stride = int(lib.vck_row_state_stride())
+    for B in (1, 8):
+        rs = torch.zeros((2 * B, stride), dtype=torch.int32, device=dev)
+        rs[:, 0] = 1
+        tok = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+        x = torch.randn(2 * B, D, device=dev)
+        ssq = torch.rand(2 * B, npart, device=dev)
+        xg = torch.zeros(2 * B, D, dtype=torch.int16, device=dev)
+
+        def f():
+            lib.vck_guidance_follow(P(rs), P(tok), P(x), P(ssq), P(xg), B, D, npart, 0, None)
+        print(f"guidance_follow followers {B} D {D}: {timeit(f, iters=40):7.1f} us", flush=True)
+
+
 def bench_logits_process_constrained():
     """logits_process_kernel with a token automaton (phase 4) over [rows, 32000] fp32 logits, the other processors off: the launch
     without tables (the copy), a free-text state, and states of 1 / 133 / 4096 / 32000 edges (ids spread evenly over the vocabulary);
@@ -914,6 +952,7 @@ if __name__ == "__main__":
              "extend_linears": bench_extend_linears, "extend_attn": bench_extend_attn, "token_logprob": bench_token_logprob,
              "topk_logprob": bench_topk_logprob, "logits_process": bench_logits_process,
              "logits_process_constrained": bench_logits_process_constrained,
+             "guidance_combine": bench_guidance_combine, "guidance_follow": bench_guidance_follow,
              "score_head": bench_score_head, "attention_verify": bench_attention_verify, "attention_fanout": bench_attention_fanout, "gemv_formats": bench_gemv_formats, "gemv_w4": lambda: bench_gemv_formats(("w4",))}
     for w in what:
         table[w]()

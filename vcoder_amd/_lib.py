@@ -135,6 +135,14 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_request_fanout.restype = C.c_int
     lib.vc_last_fanout.argtypes = [vp, vp]
     lib.vc_last_fanout.restype = C.c_int
+    lib.vc_request_guidance.argtypes = [vp, C.c_float, vp, i32, i32, vp, vp, vp, i32]
+    lib.vc_request_guidance.restype = C.c_int
+    lib.vc_last_guidance.argtypes = [vp, vp]
+    lib.vc_last_guidance.restype = C.c_int
+    lib.vck_guidance_combine.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp]
+    lib.vck_guidance_combine.restype = None
+    lib.vck_guidance_follow.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.vck_guidance_follow.restype = None
     lib.vck_attention_fanout.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, C.c_float, i32, vp]
     lib.vck_attention_fanout.restype = C.c_int
     lib.vck_topk_logprob.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]

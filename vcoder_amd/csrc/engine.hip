@@ -164,9 +164,14 @@ struct LoopView {
     // processor launch, if the step holds one, has no fourth phase
     const int *cn_state_off, *cn_edge_tok, *cn_edge_next, *cn_default_next;
     int cn_states;         // (padding follows)
+    // classifier-free guidance of a generate() call (vc_request_guidance): the step runs over 2 B rows — B conditional rows and their
+    // B followers behind them — and its selection tail combines each pair of raw rows into gd_logits [B, V] (gd_scalars [B, 4]: the
+    // combine kernel's reduction scalars), selects for the B conditional rows and lets the followers take over the chosen tokens.
+    // nullptr (every view but the one such a call makes for itself): a plain tail over all rows of the step
+    float *gd_logits, *gd_scalars;
 };
 inline bool operator==(const LoopView& a, const LoopView& b) {
-    static_assert(sizeof(LoopView) == 288, "LoopView changed: compare the new member here");
+    static_assert(sizeof(LoopView) == 304, "LoopView changed: compare the new member here");
     return a.st == b.st && a.kc == b.kc && a.vc == b.vc && a.es == b.es && a.split_G == b.split_G && a.capR == b.capR &&
            a.capS == b.capS && a.rows == b.rows && a.kmask == b.kmask && a.kmask_stride == b.kmask_stride && a.x_dec == b.x_dec &&
            a.xg_dec == b.xg_dec && a.qkv_dec == b.qkv_dec && a.attn_dec == b.attn_dec && a.h_dec == b.h_dec && a.logits == b.logits &&
@@ -175,7 +180,8 @@ inline bool operator==(const LoopView& a, const LoopView& b) {
            a.stamp_scratch == b.stamp_scratch && a.lp_tok == b.lp_tok && a.lp_top == b.lp_top && a.lp_ids == b.lp_ids &&
            a.lp_k == b.lp_k && a.proc_prompt == b.proc_prompt && a.proc_bad == b.proc_bad && a.proc_logits == b.proc_logits && a.fan_n == b.fan_n && a.fan_P == b.fan_P &&
            a.cn_state_off == b.cn_state_off && a.cn_edge_tok == b.cn_edge_tok && a.cn_edge_next == b.cn_edge_next &&
-           a.cn_default_next == b.cn_default_next && a.cn_states == b.cn_states;
+           a.cn_default_next == b.cn_default_next && a.cn_states == b.cn_states && a.gd_logits == b.gd_logits &&
+           a.gd_scalars == b.gd_scalars;
 }
 
 // The buffers of the device beam loop (vc_generate_beam): the fixed-size part carved from m->bm_state, the tables from m->bm_tab /
@@ -237,6 +243,9 @@ inline bool operator==(const BeamLoop& a, const BeamLoop& b) {
 // instantiation) and the address of the groups' prompt lengths (fan_P; the lengths themselves are read on the device) — both are
 // LoopView members, so (b) covers them: another n, or another B at the same n (nrows), re-captures; the same (B, n) replays.  The
 // cache capacity in rows (capR) bounds the rows the kernel touches and is a member already.
+// A guided step (STEP_GUIDE; vc_request_guidance) is a plain step over nrows = 2 B rows whose selection tail holds the combine and the
+// follow launch: beside the view's members it bakes in the guided rows and the scalars' address (gd_logits / gd_scalars, LoopView
+// members: non-null says the tail is the guided one) and B = nrows / 2.  The scale is read from the records on the device.
 struct SpecLoop {
     int *tok, *nq, *counters;
     const int *lookup, *lookup_len, *prompt, *prompt_len;
@@ -272,7 +281,8 @@ enum StepKind {
     STEP_BEAM = 2,
     STEP_SPEC = 3,   // the verify step of prompt-lookup speculation
     STEP_FAN = 4,    // the step of a fan-out call (num_return_sequences): the fan-out attention, with or without log-probs / processors
-    STEP_KINDS = 5
+    STEP_GUIDE = 5,  // the step of a guided call (guidance_scale): 2 B rows, the guided selection tail, with or without log-probs / processors
+    STEP_KINDS = 6
 };
 struct StepGraph {
     StepKey key{};
@@ -407,6 +417,20 @@ struct vc_model {
     bool fan_closed = false;      // a served fan-out call ran: cache row r no longer holds one sequence — the session's loop is closed
     bool fan_last = false, fan_last_shared = false;
     int fan_last_n = 0, fan_last_B = 0;
+    // classifier-free guidance of the NEXT vc_generate / vc_prefill (vc_request_guidance; one-shot): the scale, a copy of the negative
+    // prompt's ids [gd_B, gd_T] and the caller's pixel pointers of its images (borrowed until that call returns).  A served call runs
+    // on the session's loop over 2 gd_B rows — the conditional rows 0 .. B - 1, their followers behind them — with the guided
+    // selection tail (LoopView::gd_logits); gd_last*: what the last vc_generate / vc_prefill made of a request
+    bool gd_on = false;
+    float gd_scale = 1.f;
+    std::vector<int64_t> gd_ids;
+    int gd_B = 0, gd_T = 0, gd_px_on_dev = 0;
+    const float* gd_px[3] = {nullptr, nullptr, nullptr};
+    Buf gd_logits, gd_scalars;
+    bool gd_closed = false;       // a guided generate ran: the rows stand at different positions — the session's loop is closed
+    int gd_pair = 0;              // > 0: a guided vc_prefill left a loop of 2 gd_pair rows (pairs at different positions) for vc_decode_step
+    bool gd_last = false;
+    int gd_last_B = 0, gd_last_Sc = 0, gd_last_Sn = 0;
     bool tok_stale = false;       // vc_rewind ran: the token the last step selected on the device no longer continues the sequence
     bool plan_only = false;       // do_prefill stops behind the splice plan (vc_plan_spliced_len): no tower pass, no state change
     int reserve_new = 64;         // KV slots a vc_prefill keeps free behind the prompt (vc_model_reserve_decode)
@@ -487,6 +511,13 @@ static void clear_speculation_request(vc_model* m) {
     m->spec_lookup.clear();
     m->spec_lookup_len.clear();
 }
+static void clear_guidance_request(vc_model* m) {
+    m->gd_on = false;
+    m->gd_scale = 1.f;
+    m->gd_ids.clear();
+    m->gd_B = m->gd_T = m->gd_px_on_dev = 0;
+    for (auto& p : m->gd_px) p = nullptr;
+}
 static void clear_generate_logprobs_request(vc_model* m) {
     m->glp_k = 0;
     m->glp_tok = m->glp_top = nullptr;
@@ -511,6 +542,7 @@ struct OneShotReset {
         clear_logits_processors_request(m);
         clear_constraint_request(m);
         clear_speculation_request(m);
+        clear_guidance_request(m);
         m->fan_n = 0;
         m->fan_rows = 0;
     }

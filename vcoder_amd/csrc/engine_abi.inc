@@ -849,6 +849,55 @@ VC_API int vc_model_reserve_decode(vc_model* m, int max_new_tokens) {
     return VC_OK;
 }
 
+/* Classifier-free guidance of the NEXT vc_generate / vc_prefill call (one-shot).  neg_ids == NULL cancels.  See
+ * include/vcoder_hip.h. */
+VC_API int vc_request_guidance(vc_model* m, float scale, const int64_t* neg_ids, int B, int Tn, const float* neg_img,
+                               const float* neg_seg, const float* neg_depth, int pixels_on_device) {
+    if (!m) return VC_ERR_INVALID;
+    if (!neg_ids) {
+        clear_guidance_request(m);
+        return VC_OK;
+    }
+    // (a refusal leaves a pending request as it was: nothing touched)
+    if (!std::isfinite(scale)) {
+        m->ctx->err = "vc_request_guidance: the scale must be finite";
+        return VC_ERR_INVALID;
+    }
+    if (B < 1 || 2 * B > VC_MAX_ROWS || Tn < 1) {
+        m->ctx->err = "vc_request_guidance needs 1 <= B <= 8 negative prompts (2 B rows: at most 16 per GPU replica) of at least one id";
+        return VC_ERR_INVALID;
+    }
+    m->gd_on = true;
+    m->gd_scale = scale;
+    m->gd_ids.assign(neg_ids, neg_ids + (size_t)B * Tn);
+    m->gd_B = B;
+    m->gd_T = Tn;
+    m->gd_px[0] = neg_img;
+    m->gd_px[1] = neg_img ? neg_seg : nullptr;
+    m->gd_px[2] = neg_img ? neg_depth : nullptr;
+    m->gd_px_on_dev = pixels_on_device;
+    return VC_OK;
+}
+/* what the last vc_generate / vc_prefill of this session made of a guidance request: out = {served (1), conditional rows B, spliced
+ * length of the prompts, spliced length of the negative prompts}; VC_OK, or VC_ERR_STATE (no request) */
+VC_API int vc_last_guidance(vc_model* m, int32_t* out) {
+    if (!m || !out) return VC_ERR_INVALID;
+    if (!m->gd_last) {
+        m->ctx->err = "the last generate / prefill call of this session had no guidance request";
+        return VC_ERR_STATE;
+    }
+    out[0] = 1;
+    out[1] = m->gd_last_B;
+    out[2] = m->gd_last_Sc;
+    out[3] = m->gd_last_Sn;
+    return VC_OK;
+}
+
+namespace {
+void guided_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth, int on_dev,
+                    int has_mask, float* logits_last, int* S_out);   // engine_pool.inc
+}
+
 VC_API int vc_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg,
                       const float* depth, int pixels_on_device, int has_attention_mask, float* logits_last,
                       float* logits_all, int* S_out) {
@@ -856,6 +905,16 @@ VC_API int vc_prefill(vc_model* m, const int64_t* ids, int B, int T, const float
     OneShotReset one_shot{m};
     GUARD_BEGIN
     USE_DEVICE(m->ctx);
+    m->gd_last = false;
+    if (m->gd_on) {
+        // vc_request_guidance: the loop of 2 B rows a host loop steps with vc_decode_step over 2 B tokens; every refusal comes before
+        // anything of the session is touched
+        REQUIRE(m->score_labels.empty() && !logits_all && !m->hidden_out && !m->attn_out, VC_ERR_STATE,
+                "a guided vc_prefill returns its 2 B last-row logits only (no labels, all-row logits, hidden states or attentions)");
+        REQUIRE(m->gd_B == B, VC_ERR_INVALID, "negative prompts given for %d sequences, batch is %d", m->gd_B, B);
+        guided_prefill(m, ids, B, T, img, seg, depth, pixels_on_device, has_attention_mask, logits_last, S_out);
+        return VC_OK;
+    }
     if (!m->score_labels.empty()) {
         // vc_request_token_scores: a scored prefill is refused while the session's cache and position are still what they were — the
         // shape here, the label range and the capacity behind the splice plan in do_prefill, which drops the position only then
@@ -966,6 +1025,7 @@ VC_API int vc_reorder_cache(vc_model* m, const int32_t* src_rows, int B) {
     GUARD_BEGIN
     USE_DEVICE(m->ctx);
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_reorder_cache before vc_prefill");
+    REQUIRE(!m->gd_pair, VC_ERR_STATE, "vc_reorder_cache behind a guided vc_prefill: its rows are pairs at different positions");
     REQUIRE(src_rows && B == m->curB, VC_ERR_INVALID, "beam_idx must have one entry per row of the current batch (%d)", m->curB);
     bool identity = true;
     for (int b = 0; b < B; ++b) {
@@ -1000,6 +1060,7 @@ VC_API int vc_rewind(vc_model* m, int P) {
     GUARD_BEGIN
     USE_DEVICE(m->ctx);
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_rewind before vc_prefill");
+    REQUIRE(!m->gd_pair, VC_ERR_STATE, "vc_rewind behind a guided vc_prefill: its rows stand at different positions");
     REQUIRE(P >= m->curS && P <= m->cur_pos, VC_ERR_INVALID, "vc_rewind to %d: the prompt ends at %d, the loop stands at %d", P,
             m->curS, m->cur_pos);
     if (P != m->cur_pos) {
@@ -1019,7 +1080,11 @@ void decode_step_impl(vc_model* m, const int32_t* tok, float* logits, int32_t* n
             "vc_decode_step behind a speculated generate: its rows stand at different positions (prefill again)");
     REQUIRE(!(m->cur_pos < 0 && m->fan_closed), VC_ERR_STATE,
             "vc_decode_step behind a fan-out generate: a cache row no longer holds one sequence (prefill again)");
+    REQUIRE(!(m->cur_pos < 0 && m->gd_closed), VC_ERR_STATE,
+            "vc_decode_step behind a guided generate: its rows stand at different positions (prefill again)");
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_decode_step before vc_prefill");
+    REQUIRE(!m->gd_pair || !(m->hidden_out || m->attn_out), VC_ERR_STATE,
+            "hidden states / attentions of a step behind a guided vc_prefill: its rows stand at different positions");
     REQUIRE(tok || !m->tok_stale, VC_ERR_STATE,
             "vc_decode_step(tok = NULL) after vc_rewind: the token selected on the device belongs to the rows that were dropped");
     if (m->cur_pos + 1 > m->capS) grow_kv(m, m->cur_pos + 1);
@@ -1091,7 +1156,10 @@ VC_API int vc_extend(vc_model* m, const int32_t* tok, int B, int n, float* logit
             "vc_extend behind a speculated generate: its rows stand at different positions (prefill again)");
     REQUIRE(!(m->cur_pos < 0 && m->fan_closed), VC_ERR_STATE,
             "vc_extend behind a fan-out generate: a cache row no longer holds one sequence (prefill again)");
+    REQUIRE(!(m->cur_pos < 0 && m->gd_closed), VC_ERR_STATE,
+            "vc_extend behind a guided generate: its rows stand at different positions (prefill again)");
     REQUIRE(m->cur_pos >= 0, VC_ERR_STATE, "vc_extend before vc_prefill");
+    REQUIRE(!m->gd_pair, VC_ERR_STATE, "vc_extend behind a guided vc_prefill: its rows stand at different positions");
     REQUIRE(tok && n >= 1, VC_ERR_INVALID, "vc_extend needs n >= 1 tokens per row");
     REQUIRE(B == m->curB, VC_ERR_INVALID, "vc_extend: %d rows given, the session's loop has %d", B, m->curB);
     for (size_t i = 0; i < (size_t)B * n; ++i)

@@ -508,7 +508,20 @@ const float* enqueue_step_processors(vc_model* m, const LoopView& v, const float
 
 // the selection tail of a step on `logits`: the processors (a view with their buffers), the selection + embedding of the chosen
 // tokens (K19/K20+K10), the log-probs (a view with slabs).  advance 3: a cached step; 1: step 0 on the prefill logits.
+// A guided view (gd_logits; vc_request_guidance): nrows = 2 B — the raw rows of the B conditional sequences, then those of their
+// followers.  combine (B pairs -> the guided rows) | the processors on the guided rows | selection + embedding for the B conditional
+// rows | follow (the followers take the chosen tokens and advance their own positions) | the log-probs of the RAW conditional rows.
 void enqueue_selection(vc_model* m, const LoopView& v, const float* logits, int nrows, int advance) {
+    if (v.gd_logits) {
+        const int B = nrows / 2, V = m->c.vocab;
+        GuidanceCombineArgs ca{logits, logits + (size_t)B * V, V, v.gd_logits, V, v.rows, v.gd_scalars, V};
+        launch_guidance_combine(ca, B, v.st);
+        launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, v.gd_logits, B), B, advance), v.st);
+        GuidanceFollowArgs fa{v.rows, v.next_tok, v.x_dec, v.ssq, v.xg_dec, B, m->c.hidden, m->npart, advance};
+        launch_guidance_follow(fa, v.st);
+        enqueue_step_logprobs(m, v, logits, B);
+        return;
+    }
     launch_select_embed(select_args(m, v, enqueue_step_processors(m, v, logits, nrows), nrows, advance), v.st);
     enqueue_step_logprobs(m, v, logits, nrows);
 }
@@ -633,10 +646,11 @@ void enqueue_decode_step(vc_model* m, const LoopView& view, int nrows, int hook_
         launch_stamp_accumulate(v.stamps, *v.stamp_next, m->c.layers, v.prof_acc, v.stamp_scratch, v.st);
 }
 
-// strict mode: the rows of a session advance in lockstep, so row 0's position serves every row of the fp32 kernels
+// strict mode: the rows of a session advance in lockstep, so row 0's position serves every row of the fp32 kernels — except behind a
+// guided vc_prefill (gd_pair), whose pairs stand at different positions: every row then reads its own record
 void enqueue_decode_step_strict(vc_model* m, const LoopView& v, int B) {
     emit_hidden(m, 0, B, 1, m->x_dec.as<float>());
-    run_llm_layers_strict(m, m->x_dec.as<float>(), B, 1, v.rows + RS_POS, false);
+    run_llm_layers_strict(m, m->x_dec.as<float>(), B, 1, v.rows + RS_POS, false, 0, m->gd_pair ? RS_STRIDE : 0);
     logits_strict(m, m->x_dec.as<float>(), nullptr, B);
     enqueue_selection(m, v, v.logits, B, 3);
 }
@@ -1138,7 +1152,8 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
         // reserve_new >= 0: required (generate) — exceeding max_position_embeddings is an error
         int want = (int)S + std::max(reserve_new < 0 ? -reserve_new : reserve_new, 1);
         if (reserve_new < 0) want = std::max((int)S + 1, std::min(want, c.max_positions / 64 * 64));
-        if (own_kv) ensure_llm(m, std::max(B, m->fan_rows), want);   // a served fan-out call: the cache and the loop of B n rows
+        if (own_kv) m->gd_pair = 0;   // (a guided vc_prefill sets it again behind its two prefills)
+        if (own_kv) ensure_llm(m, std::max(B, m->fan_rows), want);   // a served fan-out / guided call: the cache and the loop of B n / 2 B rows
         else ensure_prefill_ws(m, B, (int)rup(S, 64));
     }
     std::vector<int> flat((size_t)B * S * 2);
@@ -1157,7 +1172,7 @@ void do_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img,
     if (m->precision) {  // strict and split: the projected features are fp32
         if (m->precision == 1) {
             REQUIRE(own_kv, VC_ERR_STATE, "strict mode runs on the session's own decode loop");
-            ensure_strict(m, B, m->capS);
+            ensure_strict(m, std::max(B, m->fan_rows), m->capS);   // (a guided prefill: the fp32 caches of 2 B rows as well)
         }
         launch_splice_f32(m->row_src.as<int>(), (int)(B * S), m->embed, m->s_feats.as<float>(), m->x.as<float>(), c.hidden,
                           m->st, lo_plane(m, m->embed));
@@ -1329,7 +1344,7 @@ void finish_prefill(vc_model* m, const KvTarget& kv, float* logits_all_host) {
     if (m->precision) HIPCHK(hipMemcpyAsync(m->last_idx.p, idx.data(), B * 4, hipMemcpyHostToDevice, m->st));
     emit_hidden(m, 0, B, S);   // inputs_embeds
     if (m->precision == 1) {
-        run_llm_layers_strict(m, m->x.as<float>(), B, S, nullptr, true);
+        run_llm_layers_strict(m, m->x.as<float>(), B, S, nullptr, true, kv.row0);
         logits_strict(m, m->x.as<float>(), m->last_idx.as<int>(), B);
     } else if (m->precision == 2) {
         run_prefill_layers_split(m, kv, B, S);
@@ -1384,6 +1399,27 @@ void arm_session_rows(vc_model* m, const GenParams& g, const int* tail, int fan 
     m->cur_pos = S;
     m->spec_closed = false;
     m->fan_closed = false;
+    m->gd_closed = false;
+    m->tok_stale = false;
+}
+
+// arm the session's loop for a guided call (vc_request_guidance): rows 0 .. B - 1 continue the B prompts at position S_c with the
+// call's parameters and the scale; rows B .. 2 B - 1 are their followers at position S_n — active, nothing recorded (RS_MAXNEW 0),
+// no EOS or stop sequence of their own (guidance_follow_kernel mirrors RS_FINISHED)
+void arm_guided_rows(vc_model* m, const GenParams& g, const int* tail, int B, int S_c, int S_n, float scale) {
+    std::vector<int> rec((size_t)2 * B * RS_STRIDE);
+    fill_rows(rec.data(), B, g, S_c, tail, 0, m->out_stride);
+    GenParams f;
+    f.pad = g.pad;
+    fill_rows(rec.data() + (size_t)B * RS_STRIDE, B, f, S_n, nullptr, 0, 0);
+    for (int b = 0; b < B; ++b) memcpy(&rec[(size_t)b * RS_STRIDE + RS_GD_SCALE], &scale, 4);
+    HIPCHK(hipMemsetAsync(m->rows.p, 0, m->rows.cap, m->st));
+    HIPCHK(hipMemcpyAsync(m->rows.p, rec.data(), rec.size() * 4, hipMemcpyHostToDevice, m->st));
+    HIPCHK(hipStreamSynchronize(m->st));
+    m->cur_pos = std::max(S_c, S_n);
+    m->spec_closed = false;
+    m->fan_closed = false;
+    m->gd_closed = false;
     m->tok_stale = false;
 }
 

@@ -598,6 +598,108 @@ std::unique_lock<std::mutex> prefill_on_session(vc_model* m, const int64_t* ids,
     return gate;
 }
 
+// the guidance request a call serves (vc_request_guidance), taken out of the model before anything can fail
+struct GuidanceCall {
+    float scale = 1.f;
+    std::vector<int64_t> ids;   // the negative prompt [B, T]
+    int B = 0, T = 0, on_dev = 0;
+    const float* px[3] = {nullptr, nullptr, nullptr};
+};
+GuidanceCall take_guidance(vc_model* m) {
+    GuidanceCall gd;
+    gd.scale = m->gd_scale;
+    gd.ids.swap(m->gd_ids);
+    gd.B = m->gd_B;
+    gd.T = m->gd_T;
+    gd.on_dev = m->gd_px_on_dev;
+    for (int k = 0; k < 3; ++k) gd.px[k] = m->gd_px[k];
+    clear_guidance_request(m);
+    return gd;
+}
+
+// The two prompts of a guided call on the session's own loop of R = 2 B rows: the negative prompt is prefilled straight into cache
+// rows B .. 2 B - 1 (KvTarget::row0, as a request joins the pool's cache) and its last-row logits moved up by B rows, then the caller's
+// prompt into rows 0 .. B - 1 — two prefills of B rows each, so each has the bits a call of its own gives it (one prefill of 2 B rows
+// would not: README, batch invariance).  Both spliced lengths are planned first (do_prefill's plan_only form: no tower pass, no state),
+// so the first prefill already sizes the cache for max(S_c, S_n) + `room` positions and the second cannot re-allocate it.  The
+// caller's attention mask and image counts belong to ITS prompt; the negative prompt is rectangular with one image per placeholder.
+// hint: `room` is a wish (vc_prefill's reserve), cut at max_position_embeddings; else required (generate's max_new).
+std::unique_lock<std::mutex> prefill_guided_on_session(vc_model* m, const GuidanceCall& gd, const int64_t* ids, int B, int T,
+                                                       const float* img, const float* seg, const float* depth, int on_dev, int has_mask,
+                                                       int room, bool hint, int* S_c_out, int* S_n_out) {
+    const int R = 2 * B;
+    std::vector<int> counts[3];
+    for (int k = 0; k < 3; ++k) counts[k] = m->img_counts[k];
+    int S_c = 0, S_n = 0;
+    {
+        struct Plan {
+            vc_model* m;
+            ~Plan() { m->plan_only = false; }
+        } plan{m};
+        m->plan_only = true;
+        do_prefill(m, ids, B, T, img, seg, depth, on_dev, has_mask, -1, false, &S_c);   // (consumes the image counts, not the mask)
+        do_prefill(m, gd.ids.data(), B, gd.T, gd.px[0], gd.px[1], gd.px[2], gd.on_dev, has_mask, -1, false, &S_n);
+    }
+    m->cur_pos = -1;   // from here on the cache is being overwritten: a call that fails half-way leaves no loop to step
+    int total = std::max(S_c, S_n) + std::max(room, 1);
+    if (hint) total = std::max(std::max(S_c, S_n) + 1, std::min(total, m->c.max_positions / 64 * 64));
+    std::vector<uint8_t> mask;
+    mask.swap(m->mask_next);
+    std::unique_lock<std::mutex> gate(g_prefill_gate);
+    struct Rows {
+        vc_model* m;
+        ~Rows() { m->fan_rows = 0; }
+    } rows{m};
+    m->fan_rows = R;   // both prefills size the cache and the loop's buffers for R rows
+    int S = 0;
+    do_prefill(m, gd.ids.data(), B, gd.T, gd.px[0], gd.px[1], gd.px[2], gd.on_dev, has_mask, total - S_n, true, &S);
+    REQUIRE(S == S_n && m->capB == R && total <= m->capS, VC_ERR_STATE, "guided prefill: planned %d rows, spliced %d (cache %d x %d)", S_n, S,
+            m->capB, m->capS);
+    finish_prefill(m, KvTarget{m->kc.as<bf16_t>(), m->vc.as<bf16_t>(), m->capB, m->capS, B, m->kv_es}, nullptr);
+    const size_t lg = (size_t)B * m->c.vocab * 4;
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(m->logits.p) + lg, m->logits.p, lg, hipMemcpyDeviceToDevice, m->st));
+    const void* kc0 = m->kc.p;
+    const int capS0 = m->capS;
+    for (int k = 0; k < 3; ++k) m->img_counts[k] = counts[k];
+    m->mask_next.swap(mask);
+    do_prefill(m, ids, B, T, img, seg, depth, on_dev, has_mask, total - S_c, true, &S);
+    REQUIRE(S == S_c && m->kc.p == kc0 && m->capS == capS0 && m->capB == R, VC_ERR_STATE,
+            "guided prefill: the second prompt moved the cache (planned %d rows, spliced %d)", S_c, S);
+    finish_prefill(m, session_kv(m), nullptr);
+    m->last_S = S_c;
+    m->kmask_in_decode = false;   // the cached steps of both streams run under an all-ones mask, as generate()'s
+    if (m->ev[2]) HIPCHK(hipEventRecord(m->ev[2], m->st));
+    if (S_c_out) *S_c_out = S_c;
+    if (S_n_out) *S_n_out = S_n;
+    return gate;
+}
+
+// vc_prefill with a pending vc_request_guidance (every precision mode: the strict prefill takes the row offset, the strict step the
+// rows' own positions — run_llm_layers_strict): the same state of 2 B rows for a host loop — logits_last [2 B, V] (the conditional
+// rows, then the negative prompts'), and a loop vc_decode_step steps over 2 B host-supplied tokens (the pairs advance their own
+// positions; nothing is selected on the device: vc_decode_step(tok = NULL) is refused as behind a rewind)
+void guided_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth, int on_dev,
+                    int has_mask, float* logits_last, int* S_out) {
+    const GuidanceCall gd = take_guidance(m);
+    int S_c = 0, S_n = 0;
+    std::unique_lock<std::mutex> gate = prefill_guided_on_session(m, gd, ids, B, T, img, seg, depth, on_dev, has_mask, m->reserve_new, true, &S_c, &S_n);
+    ensure_out_ids(m, 2 * B, 1);
+    GenParams g;   // nothing is recorded (max_new 0), no EOS bookkeeping
+    arm_guided_rows(m, g, nullptr, B, S_c, S_n, gd.scale);
+    m->curB = 2 * B;
+    m->gd_pair = B;
+    m->tok_stale = true;
+    m->gd_last = true;
+    m->gd_last_B = B;
+    m->gd_last_Sc = S_c;
+    m->gd_last_Sn = S_n;
+    if (S_out) *S_out = S_c;
+    if (logits_last) {
+        HIPCHK(hipMemcpyAsync(logits_last, m->logits.p, (size_t)2 * B * m->c.vocab * 4, hipMemcpyDeviceToHost, m->st));
+        HIPCHK(hipStreamSynchronize(m->st));
+    }
+}
+
 // whether the pending vc_request_speculation is served by a call of this form (the LDS bound of the verify attention is known
 // behind the prefill only): greedy and no processors — or any selection, with vc_request_speculation_selection — the bf16 step,
 // B * (k + 1) rows in one weight pass
@@ -611,20 +713,31 @@ bool spec_request_served(const vc_model* m, const GenParams& g, int B) {
 // runs over the R rows b fan + j, whose step 0 reads prompt b's logits row and whose steps attend with the fan-out kernel — prompt
 // keys from cache row b, own keys from cache row b fan + j (positions >= S: the two regions of a cache row never overlap).  ids,
 // log-probs and the callback's columns are R rows wide; the session's loop is closed behind the call.
+// gd != nullptr (a served vc_request_guidance; fan == 1): the loop runs over Rs = 2 B rows — the B rows of the call, whose ids,
+// log-probs and callback columns come back as ever, and their B followers behind the negative prompt (prefill_guided_on_session) —
+// with the guided selection tail (LoopView::gd_logits); the session's loop is closed behind the call.
 void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth,
                          int on_dev, const GenParams& g, const std::vector<int>& tail, vc_token_cb cb, void* cb_user,
-                         int cb_every, int32_t* out_ids, int* n_generated, int fan = 1) {
+                         int cb_every, int32_t* out_ids, int* n_generated, int fan = 1, const GuidanceCall* gd = nullptr) {
     const int max_new = g.max_new;
-    const int R = B * fan;   // rows of the loop
+    const int R = B * fan;   // rows of the loop that return ids
+    const int Rs = gd ? 2 * B : R;   // rows of a step
     m->spec_closed = false;
     m->fan_closed = false;
-    m->fan_rows = fan > 1 ? R : 0;   // the prefill sizes the cache and the loop's buffers for R rows
-    std::unique_lock<std::mutex> gate = prefill_on_session(m, ids, B, T, img, seg, depth, on_dev, max_new);
-    m->fan_rows = 0;
+    m->gd_closed = false;
+    int S_neg = 0;
+    std::unique_lock<std::mutex> gate;
+    if (gd) {
+        gate = prefill_guided_on_session(m, *gd, ids, B, T, img, seg, depth, on_dev, 1, max_new, false, nullptr, &S_neg);   // generate() always builds a mask
+    } else {
+        m->fan_rows = fan > 1 ? R : 0;   // the prefill sizes the cache and the loop's buffers for R rows
+        gate = prefill_on_session(m, ids, B, T, img, seg, depth, on_dev, max_new);
+        m->fan_rows = 0;
+    }
     ensure_out_ids(m, R, max_new);
     // vc_request_speculation: served when the call's form allows (spec_request_served) and the score rows of Q queries over this
     // cache fit a CU's LDS.  (A row drafts no further than its last slot, so the prefill's reserve of max_new positions holds.)
-    const int Q = fan == 1 && spec_request_served(m, g, B) ? m->spec_k + 1 : 0;
+    const int Q = fan == 1 && !gd && spec_request_served(m, g, B) ? m->spec_k + 1 : 0;
     const bool spec = Q > 0 && (m->hd == 128 || m->hd == 64) && (m->kv_es == 2 || m->kv_es == 1) &&
                       attention_verify_lds_bytes(Q, m->hd, m->kv_es == 1, m->capS) <= ATTN_VERIFY_LDS_MAX;
     // the steps of this call: the session's plain view, plus what the call asked for — the view goes to the step-0 selection, to the
@@ -686,7 +799,15 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
         v.fan_n = fan;
         v.fan_P = m->fan_P.as<int>();
     }
-    arm_session_rows(m, g, tail.data(), fan);
+    if (gd) {
+        m->gd_logits.ensure((size_t)rup(B, 16) * m->c.vocab * 4);
+        m->gd_scalars.ensure((size_t)VC_MAX_ROWS * 4 * 4);
+        v.gd_logits = m->gd_logits.as<float>();
+        v.gd_scalars = m->gd_scalars.as<float>();
+        arm_guided_rows(m, g, tail.data(), B, m->last_S, S_neg, gd->scale);
+    } else {
+        arm_session_rows(m, g, tail.data(), fan);
+    }
     // token 0 comes from the prefill logits
     std::vector<int> fill((size_t)R * m->out_stride, g.pad);
     HIPCHK(hipMemcpyAsync(m->out_ids.p, fill.data(), fill.size() * 4, hipMemcpyHostToDevice, m->st));
@@ -699,7 +820,7 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
                 HIPCHK(hipMemcpyAsync(reinterpret_cast<char*>(v.logits) + r * rowb, reinterpret_cast<char*>(v.logits) + (r / fan) * rowb, rowb,
                                       hipMemcpyDeviceToDevice, m->st));
     }
-    enqueue_selection(m, v, v.logits, R, 1);   // step 0 -> 1; the position stays at S
+    enqueue_selection(m, v, v.logits, Rs, 1);   // step 0 -> 1; the position stays at S
     HIPCHK(hipStreamSynchronize(m->st));
     gate.unlock();
     int produced = 1, reported = 0;
@@ -781,7 +902,8 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
         m->cur_pos = -1;       // the rows stand at different positions: the session's loop is closed
         m->spec_closed = true;
     } else if (max_new > 1 && !all_finished()) {
-        const hipGraphExec_t exec = m->precision != 1 ? step_graph(m, fan > 1 ? STEP_FAN : (want_lp || g.proc ? STEP_CALL : STEP_PLAIN), v, R) : nullptr;
+        const StepKind kind = gd ? STEP_GUIDE : (fan > 1 ? STEP_FAN : (want_lp || g.proc ? STEP_CALL : STEP_PLAIN));
+        const hipGraphExec_t exec = m->precision != 1 ? step_graph(m, kind, v, Rs) : nullptr;
         for (int step = 1; step < max_new; ++step) {
             if (m->precision == 1) enqueue_decode_step_strict(m, v, B);
             else HIPCHK(hipGraphLaunch(exec, m->st));
@@ -832,6 +954,14 @@ void generate_on_session(vc_model* m, const int64_t* ids, int B, int T, const fl
     if (fan > 1) {
         m->cur_pos = -1;       // cache row r holds prompt r's keys and sequence r's own: the session's loop is closed
         m->fan_closed = true;
+    }
+    if (gd) {
+        m->cur_pos = -1;       // the conditional rows and their followers stand at different positions: the session's loop is closed
+        m->gd_closed = true;
+        m->gd_last = true;     // (set behind the loop: a call that failed reports no served request)
+        m->gd_last_B = B;
+        m->gd_last_Sc = m->last_S;
+        m->gd_last_Sn = S_neg;
     }
     if (n_generated) *n_generated = produced;
     read_phase_times(m, m->ev[2], m->ev[3]);
@@ -1226,7 +1356,19 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
     REQUIRE(m->spec_k == 0 || m->spec_lookup.empty() || m->spec_B == B, VC_ERR_INVALID, "lookup ids given for %d sequences, batch is %d",
             m->spec_B, B);
     m->spec_last = false;
-    if (fan > 1) {
+    // vc_request_guidance: the call runs on the session's own loop over 2 B rows (the pool's steps carry no guided tail); a pending
+    // vc_request_speculation is not served beside it
+    m->gd_last = false;
+    if (m->gd_on) {
+        REQUIRE(fan == 1, VC_ERR_STATE, "a vc_request_guidance and a vc_request_fanout are pending: repeat the prompts instead");
+        REQUIRE(m->precision == 0, VC_ERR_STATE, "guidance is served in the bf16 precision mode");
+        // guidance_follow_kernel copies the x / xg rows in 16-byte chunks: D a multiple of 8 puts every row start on 16 bytes
+        REQUIRE(m->c.hidden % 8 == 0, VC_ERR_STATE, "the guided step copies rows in 16-byte chunks: hidden_size %d is no multiple of 8", m->c.hidden);
+        REQUIRE(m->gd_B == B, VC_ERR_INVALID, "negative prompts given for %d sequences, batch is %d", m->gd_B, B);
+        REQUIRE(2 * B <= VC_MAX_ROWS, VC_ERR_INVALID, "a guided batch of %d needs %d rows: at most %d per GPU replica", B, 2 * B, VC_MAX_ROWS);
+        const GuidanceCall gd = take_guidance(m);
+        generate_on_session(m, ids, B, T, img, seg, depth, pixels_on_device, g, tail, cb, cb_user, cb_every, out_ids, n_generated, 1, &gd);
+    } else if (fan > 1) {
         // served: the bf16 step over a bf16 or e4m3 cache, head dim 128 or 64, up to 8 rows per prompt, n score rows over the
         // longest cache this model can ask for within a CU's LDS (the capacity itself is known behind the prefill only), and a
         // prefill whose bits do not depend on the rows that share its launch (else no shared prefix equals the repeated call)
@@ -1284,6 +1426,7 @@ VC_API int vc_generate_beam(vc_model* m, const int64_t* ids, int B, int T, const
     REQUIRE(!m->glp_tok, VC_ERR_STATE, "per-token log-probs are not implemented for beam search: a vc_request_generate_logprobs is pending");
     REQUIRE(!m->gproc, VC_ERR_STATE, "logits processors are not implemented in the device beam loop: a vc_request_logits_processors is pending");
     REQUIRE(m->gcn_tab.empty(), VC_ERR_STATE, "constrained decoding is not implemented in the device beam loop: a vc_request_constraint is pending");
+    REQUIRE(!m->gd_on, VC_ERR_STATE, "guidance is not implemented in the device beam loop: a vc_request_guidance is pending");
     m->spec_last = false;   // (a pending vc_request_speculation is not served by beam search)
     {   // the tail permute moves 16-byte chunks of a cache row: the element size the prefill below will give the session's cache
         const int es = m->precision == 2 ? split_kv_es() : step_kv_es(m);

@@ -323,7 +323,9 @@ float* s_vcache(vc_model* m, int l) { return m->s_vc.as<float>() + (size_t)l * m
 
 // one decoder stack pass over `T` new tokens per sample starting at the device-scalar position (prefill: pos 0).
 // is_prefill says which of the two the pass is — a text-only prefill of ONE token has T == 1 too
-void run_llm_layers_strict(vc_model* m, float* x, int B, int T, const int* pos_dev, bool is_prefill) {
+// row0: the B sequences are cache rows row0 .. row0 + B - 1 (a guided prefill's negative prompts); pos_stride != 0: sequence b
+// stands at pos_dev[b * pos_stride] (the rows' RS_POS: the pairs of a guided loop stand at different positions)
+void run_llm_layers_strict(vc_model* m, float* x, int B, int T, const int* pos_dev, bool is_prefill, int row0 = 0, int pos_stride = 0) {
     const vc_model_cfg& c = m->c;
     const int D = c.hidden, F = c.ffn, H = c.heads, M = B * T;
     float *xn = m->s_xn.as<float>(), *qkv = m->s_qkv.as<float>(), *q = m->s_q.as<float>(), *at = m->s_attn.as<float>(),
@@ -333,10 +335,12 @@ void run_llm_layers_strict(vc_model* m, float* x, int B, int T, const int* pos_d
         const LlmLayer& L = m->llm[l];
         launch_rmsnorm_f32(x, nullptr, L.in_norm, xn, M, D, c.rms_eps, m->st);
         gemm32(m, xn, L.qkv_w, nullptr, qkv, M, 3 * D, D, D, D, 3 * D, EPI_F32);
-        QkvF32Args qa{qkv, q, s_kcache(m, l), s_vcache(m, l), B, T, H, m->hd, T, m->s_capS, pos_dev, m->rope_cos, m->rope_sin};
+        const size_t roff = (size_t)row0 * H * m->s_capS * m->hd;
+        float *kl = s_kcache(m, l) + roff, *vl = s_vcache(m, l) + roff;
+        QkvF32Args qa{qkv, q, kl, vl, B, T, H, m->hd, T, m->s_capS, pos_dev, m->rope_cos, m->rope_sin, pos_stride};
         launch_qkv_rope_f32(qa, m->st);
-        AttnF32Args aa{q, s_kcache(m, l), s_vcache(m, l), at, B, H, T, m->hd, T, m->s_capS, 1, 0, pos_dev,
-                       1.0f / sqrtf((float)m->hd)};
+        AttnF32Args aa{q, kl, vl, at, B, H, T, m->hd, T, m->s_capS, 1, 0, pos_dev, 1.0f / sqrtf((float)m->hd)};
+        aa.pos_stride = pos_stride;
         attach_kmask(m, aa, is_prefill ? m->has_kmask : m->kmask_in_decode);
         launch_attention_f32(aa, m->st);
         const bool step = !is_prefill && x == m->x_dec.as<float>();   // a session's cached decode step (m->cur_pos = its position)

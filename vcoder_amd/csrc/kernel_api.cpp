@@ -176,6 +176,17 @@ VCK_EXPORT void vck_logits_process_verify(const float* logits, int ldl, float* o
     LogitsProcessArgs a{logits, ldl, out, ldo, const_cast<int*>(rows), prompt_ids, out_ids, bad_words, V, Q, tok, nq};
     launch_logits_process(a, B * Q, S(stream));
 }
+VCK_EXPORT void vck_guidance_combine(const float* cond, const float* uncond, int ldl, float* out, int ldo, const int* rows,
+                                     float* scalars, int nrows, int V, void* stream) {
+    GuidanceCombineArgs a{cond, uncond, ldl, out, ldo, rows, scalars, V};
+    launch_guidance_combine(a, nrows, S(stream));
+}
+VCK_EXPORT void vck_guidance_follow(int* rows, int* next_tok, float* x, float* ssq, uint16_t* xg, int B, int D, int npart, int advance,
+                                    void* stream) {
+    if (B < 1 || D < 8 || D % 8 != 0) return;   // nothing is launched, nothing written
+    GuidanceFollowArgs a{rows, next_tok, x, ssq, reinterpret_cast<bf16_t*>(xg), B, D, npart, advance};
+    launch_guidance_follow(a, S(stream));
+}
 VCK_EXPORT void vck_embed_tokens_ssq(const int* tok, const uint16_t* embed, float* x, float* ssq, const float* xg_w,
                                      uint16_t* xg, int B, int D, int npart, void* stream) {
     launch_embed_tokens_ssq(tok, embed, x, ssq, xg_w, xg, B, D, npart, S(stream));

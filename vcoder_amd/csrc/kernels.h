@@ -445,6 +445,7 @@ enum RowStateField : int {
     RS_CN_ON = 110,       // != 0: the automaton applies to the row
     RS_CN_STATE = 111,    // state behind out_ids[0 .. RS_CN_POS) (-1: dead)
     RS_CN_POS = 112,      // ids of the row the state has consumed
+    RS_GD_SCALE = 113,    // float bits: the guidance scale of a conditional row (guidance_combine_kernel)
     RS_STRIDE = 128,
 };
 constexpr int VC_MAX_BAD_WORDS = 32, VC_MAX_BAD_WORD_LEN = 8, VC_MAX_EOS_EXTRA = 8;
@@ -593,6 +594,37 @@ struct LogitsProcessArgs {
     int cn_states;
 };
 void launch_logits_process(const LogitsProcessArgs& a, int nrows, hipStream_t s);
+// classifier-free guidance in front of the processors (select.hip guidance_combine_kernel; [HF] generation/logits_process.py
+// UnbatchedClassifierFreeGuidanceLogitsProcessor): for the raw conditional row c = cond[r] and the raw unconditional row u = uncond[r]
+//   lc = (c - max c) - log(sum exp(c - max c)),  lu likewise,  out[r] = g * (lc - lu) + lu     (fp32; product and sum rounded separately)
+// with g = the float in rows[r][RS_GD_SCALE], so one captured step serves every scale.  One workgroup per pair; both raw rows are only
+// read, pad columns V .. ldo of `out` are not written, inactive rows write nothing.  scalars[r] = {max c, log sum c, max u, log sum u}:
+// out is a pure element-wise function of the two rows and these four values.
+struct GuidanceCombineArgs {
+    const float* cond;      // [nrows, ldl] fp32: the raw conditional rows
+    const float* uncond;    // [nrows, ldl] fp32: the raw unconditional rows (a loop of 2 B rows: cond + B * ldl)
+    int ldl;
+    float* out;             // [nrows, ldo] fp32: the guided rows
+    int ldo;
+    const int* rows;        // [nrows][RS_STRIDE]: RS_ACTIVE, RS_GD_SCALE of the conditional rows
+    float* scalars;         // [nrows, 4]
+    int V;
+};
+void launch_guidance_combine(const GuidanceCombineArgs& a, int nrows, hipStream_t s);
+// the unconditional rows of a guided step follow their partners (select.hip guidance_follow_kernel), behind launch_select_embed over
+// the B conditional rows: follower B + i takes row i's next_tok, x row, sum-of-squares partials and xg row (so the next step feeds both
+// streams the same token), mirrors its RS_FINISHED and advances its OWN RS_STEP / RS_POS as SelectArgs::advance says.  Followers
+// that are not RS_ACTIVE, and every row outside [B, 2 B), are not touched.  One workgroup per follower.
+struct GuidanceFollowArgs {
+    int* rows;              // [2 B][RS_STRIDE]
+    int* next_tok;          // [2 B]
+    float* x;               // [2 B, D]
+    float* ssq;             // [2 B, npart]
+    bf16_t* xg;             // [2 B, D]
+    int B, D, npart;        // D a multiple of 8
+    int advance;            // bit 0: step += 1; bit 1: pos += 1
+};
+void launch_guidance_follow(const GuidanceFollowArgs& a, hipStream_t s);
 // one beam-search step of B sequences of n beams each (rows b * n .. b * n + n - 1; R = B * n <= 16) behind a launch_topk_logprob
 // with K = 2 n into cand_lp / cand_id [R, 2 n] (select.hip beam_step_kernel): what one iteration of HF's beam_search does between
 // `topk` and `_reorder_cache` — the 2 n best of a sequence's n * 2 n candidates (score = lp + beam_score[row], one fp32 add; ordered
@@ -660,6 +692,7 @@ struct AttnF32Args {
     float scale;
     const uint8_t* key_mask;  // [B, mask_stride]: 0 hides the key from every query of the sequence (nullptr = none)
     int mask_stride;
+    int pos_stride;   // 0: pos0_dev is one scalar for every sequence; else sequence b reads pos0_dev[b * pos_stride] (RowState records)
 };
 void launch_attention_f32(const AttnF32Args& a, hipStream_t s);
 // output_attentions (diagnostic): probabilities [B, H, T, T] fp32 of a causal prefill layer from its q / k — fp32 (q32 / k32),
@@ -695,6 +728,7 @@ struct QkvF32Args {
     const int* pos0_dev;
     const float* rope_cos;  // nullptr: no RoPE (ViT)
     const float* rope_sin;
+    int pos_stride;    // as AttnF32Args::pos_stride
 };
 void launch_qkv_rope_f32(const QkvF32Args& a, hipStream_t s);
 void launch_layernorm_f32(const float* x, const float* w, const float* b, float* y, int rows, int D, float eps, hipStream_t s);

@@ -907,6 +907,132 @@ void launch_logits_process(const LogitsProcessArgs& a, int nrows, hipStream_t s)
     VC_LAUNCH(logits_process_kernel, dim3((unsigned)nrows), dim3(LPROC_THREADS), 0, s, a);
 }
 
+// ---- classifier-free guidance in front of the processors (generate(guidance_scale=, negative_prompt_ids=); [HF]
+// generation/logits_process.py UnbatchedClassifierFreeGuidanceLogitsProcessor) --------------------------------------------------------
+// One workgroup of 1024 threads per pair (conditional row c, unconditional row u), two passes:
+//   1. the (max, sum) pairs of BOTH rows with lse_add / lse_merge in the fixed merge order of token_logprob_kernel (lanes, then the
+//      waves in ascending order, the same in every thread), one partition of the columns for both rows — identical rows reduce to
+//      identical scalars;
+//   2. out[t] = g * (lc[t] - lu[t]) + lu[t] with lc[t] = (c[t] - max c) - log sum c, lu likewise — lp_value()'s expression — the
+//      product and the sum rounded separately (guided_value: contraction off), so numpy float32 reproduces every bit from the four
+//      scalars, which tid 0 leaves in scalars[r].
+// Two rows of V = 32000 (250 KiB) do not fit a CU's LDS together, and NEITHER is staged: both were just written by the lm_head launch
+// and sit in L2, so pass 2 re-reads them from there — staging the conditional row in 16-byte LDS accesses measured 25.6 us per launch
+// against 25.6 us without at V = 32000, B = 1 (profiles/guidance_wall_times.md), and without it the kernel needs no dynamic LDS.
+// 16-byte accesses over [head, body_end) where the rows are congruent modulo 16 bytes (pass 1: c and u; pass 2: `out` too), one float
+// at a time in front of and behind it, and everywhere when they are not; nothing beyond column V - 1 is read, pad columns of `out`
+// are not written.
+constexpr int GUIDE_THREADS = 1024, GUIDE_WAVES = GUIDE_THREADS / 64;
+VC_DEV float guided_value(float c, float u, float mc, float lsc, float mu, float lsu, float g) {
+#pragma clang fp contract(off)
+    const float lc = (c - mc) - lsc;
+    const float lu = (u - mu) - lsu;
+    const float d = lc - lu;
+    const float p = g * d;
+    return p + lu;
+}
+__global__ __launch_bounds__(GUIDE_THREADS) void guidance_combine_kernel(GuidanceCombineArgs p) {
+    __shared__ float red_mc[GUIDE_WAVES], red_sc[GUIDE_WAVES], red_mu[GUIDE_WAVES], red_su[GUIDE_WAVES];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* rs = p.rows + (size_t)r * RS_STRIDE;
+    if (!rs[RS_ACTIVE]) return;
+    const int V = p.V;
+    const float g = __builtin_bit_cast(float, rs[RS_GD_SCALE]);
+    const float* c = p.cond + (size_t)r * p.ldl;
+    const float* u = p.uncond + (size_t)r * p.ldl;
+    float* out = p.out + (size_t)r * p.ldo;
+    // ---- pass 1 -------------------------------------------------------------------------------------------------------------------
+    const int mis = (int)((reinterpret_cast<uintptr_t>(c) >> 2) & 3);
+    const bool vec1 = ((reinterpret_cast<uintptr_t>(c) ^ reinterpret_cast<uintptr_t>(u)) & 15) == 0;
+    const bool vec2 = vec1 && ((reinterpret_cast<uintptr_t>(c) ^ reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int head = vec1 ? min(V, (4 - mis) & 3) : V;   // columns [0, head) and [body_end, V) one float at a time
+    const int body_end = head + ((V - head) & ~3);
+    float mc = -INFINITY, sc = 0.f, mu = -INFINITY, su = 0.f;
+    for (int i = tid; i < head; i += GUIDE_THREADS) {
+        lse_add(mc, sc, c[i]);
+        lse_add(mu, su, u[i]);
+    }
+    for (int i = head + tid * 4; i < body_end; i += GUIDE_THREADS * 4) {
+        const f32x4 cv = ld16f(c + i), uv = ld16f(u + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            lse_add(mc, sc, cv[e]);
+            lse_add(mu, su, uv[e]);
+        }
+    }
+    if (body_end + tid < V) {
+        lse_add(mc, sc, c[body_end + tid]);
+        lse_add(mu, su, u[body_end + tid]);
+    }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        const float omc = shfl_xor(mc, k), osc = shfl_xor(sc, k), omu = shfl_xor(mu, k), osu = shfl_xor(su, k);
+        lse_merge(mc, sc, omc, osc);
+        lse_merge(mu, su, omu, osu);
+    }
+    if (lane == 0) { red_mc[wave] = mc; red_sc[wave] = sc; red_mu[wave] = mu; red_su[wave] = su; }
+    __syncthreads();
+    mc = red_mc[0];
+    sc = red_sc[0];
+    mu = red_mu[0];
+    su = red_su[0];
+#pragma unroll
+    for (int w = 1; w < GUIDE_WAVES; ++w) {   // fixed order, the same in every thread
+        lse_merge(mc, sc, red_mc[w], red_sc[w]);
+        lse_merge(mu, su, red_mu[w], red_su[w]);
+    }
+    const float lsc = logf(sc), lsu = logf(su);
+    if (tid == 0) {
+        float* q = p.scalars + (size_t)r * 4;
+        q[0] = mc;
+        q[1] = lsc;
+        q[2] = mu;
+        q[3] = lsu;
+    }
+    // ---- pass 2 -------------------------------------------------------------------------------------------------------------------
+    const int head2 = vec2 ? head : V, body_end2 = vec2 ? body_end : V;
+    for (int i = tid; i < head2; i += GUIDE_THREADS) out[i] = guided_value(c[i], u[i], mc, lsc, mu, lsu, g);
+    for (int i = head2 + tid * 4; i < body_end2; i += GUIDE_THREADS * 4) {
+        const f32x4 cv = ld16f(c + i), uv = ld16f(u + i);
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = guided_value(cv[e], uv[e], mc, lsc, mu, lsu, g);
+        st16f(out + i, o);
+    }
+    if (body_end2 + tid < V) out[body_end2 + tid] = guided_value(c[body_end2 + tid], u[body_end2 + tid], mc, lsc, mu, lsu, g);
+}
+void launch_guidance_combine(const GuidanceCombineArgs& a, int nrows, hipStream_t s) {
+    if (nrows <= 0) return;
+    VC_LAUNCH(guidance_combine_kernel, dim3((unsigned)nrows), dim3(GUIDE_THREADS), 0, s, a);
+}
+
+// The unconditional rows of a guided step follow their partners: behind select_embed_kernel over rows 0 .. B - 1, workgroup i copies
+// what that launch left for row i — next_tok, the fp32 residual row, its sum-of-squares partials, the first GEMV's operand row — to
+// row B + i, mirrors RS_FINISHED and advances row B + i's OWN RS_STEP / RS_POS (the two prompts differ in length).  A follower
+// records no ids (its RS_MAXNEW is 0) and is never selected for.  16-byte copies: D is a multiple of 8, the rows start on 16 bytes.
+__global__ __launch_bounds__(256) void guidance_follow_kernel(GuidanceFollowArgs p) {
+    const int src = blockIdx.x, dst = p.B + (int)blockIdx.x, tid = threadIdx.x;
+    int* rs = p.rows + (size_t)dst * RS_STRIDE;
+    if (!rs[RS_ACTIVE]) return;
+    const float* xs = p.x + (size_t)src * p.D;
+    float* xd = p.x + (size_t)dst * p.D;
+    for (int i = tid * 4; i < p.D; i += 256 * 4) st16f(xd + i, ld16f(xs + i));
+    const bf16_t* gs = p.xg + (size_t)src * p.D;
+    bf16_t* gd = p.xg + (size_t)dst * p.D;
+    for (int i = tid * 8; i < p.D; i += 256 * 8) st16(gd + i, ld16(gs + i));
+    for (int q = tid; q < p.npart; q += 256) p.ssq[(size_t)dst * p.npart + q] = p.ssq[(size_t)src * p.npart + q];
+    if (tid == 0) {
+        p.next_tok[dst] = p.next_tok[src];
+        rs[RS_FINISHED] = p.rows[(size_t)src * RS_STRIDE + RS_FINISHED];
+        if (p.advance & 1) rs[RS_STEP] += 1;
+        if (p.advance & 2) rs[RS_POS] += 1;
+    }
+}
+void launch_guidance_follow(const GuidanceFollowArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    VC_LAUNCH(guidance_follow_kernel, dim3((unsigned)a.B), dim3(256), 0, s, a);
+}
+
 // ---- one beam-search step on the device (kernels.h BeamStepArgs; [HF] generation/utils.py beam_search + beam_search.py
 // BeamSearchScorer.process of Transformers 4.31) -----------------------------------------------------------------------------------
 // ONE workgroup, one wave per sequence (B * n <= 16 rows, so the launch holds at most 16 * 32 = 512 candidates): the lanes add

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(64) void attention_f32_kernel(AttnF32Args p) {
     const int lane = threadIdx.x;
     const int t = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const size_t bh = (size_t)b * p.H + h;
-    const int pos = (p.pos0_dev ? *p.pos0_dev : 0) + t;  // absolute position of this query
+    const int pos = (p.pos0_dev ? p.pos0_dev[(size_t)b * p.pos_stride] : 0) + t;  // absolute position of this query
     const int nkeys = p.causal ? pos + 1 : p.Tk;
     const float* q = p.q + (bh * p.q_stride + t) * p.hd;
     for (int d = lane; d < p.hd; d += 64) qs[d] = q[d];
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(64) void qkv_rope_f32_kernel(QkvF32Args p) {
     const int t = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
     const int half = p.hd / 2;
     if (d >= half) return;
-    const int pos = (p.pos0_dev ? *p.pos0_dev : 0) + t;
+    const int pos = (p.pos0_dev ? p.pos0_dev[(size_t)b * p.pos_stride] : 0) + t;
     const int D = p.H * p.hd;
     const float* row = p.qkv + ((size_t)b * p.T + t) * (3 * D) + h * p.hd;
     float c = 1.f, s = 0.f;

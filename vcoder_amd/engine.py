@@ -590,7 +590,7 @@ class HipEngine:
                  on_tokens=None, stream_every: int = 1, attention_mask=None, logprobs: bool = False,
                  top_logprobs: int = 0, processors=None, eos_extra: Sequence[int] = (), speculate: Optional[int] = None,
                  lookup_ngram: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False,
-                 speculate_selection: str = "greedy", constraint: Optional[TokenAutomaton] = None) -> np.ndarray:
+                 speculate_selection: str = "greedy", constraint: Optional[TokenAutomaton] = None, guidance=None) -> np.ndarray:
         """generate() on the device (vc_generate): greedy, or temperature / top-k / top-p sampling with a counter-based
         generator (same seed -> same tokens).  on_tokens(first_step, ids [B, n]) is called with every `stream_every` new
         columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32.
@@ -632,16 +632,31 @@ class HipEngine:
         processed row (a fourth phase of the processor kernel; the state lives in the row's record).  Greedy and sampled calls,
         every precision mode, with or without processors, log-probs (of the raw rows), EOS ids, stop sequences, on_tokens and
         num_return_sequences in both forms; the call runs on the session's own loop.  `speculate` is not served beside it
-        (last_speculation is None).  Any other type: ValueError."""
+        (last_speculation is None).  Any other type: ValueError.
+        guidance (a logits_processors.Guidance; vc_request_guidance): classifier-free guidance — every step runs 2 B rows in one
+        weight pass, the B sequences behind input_ids and B followers behind guidance.negative_ids [B, Tn] (with their own pixels
+        when they hold placeholders), and the selection reads scale * (log_softmax(c) - log_softmax(u)) + log_softmax(u) of the two
+        raw rows, in front of the processors, the automaton and the warpers; every chosen token continues both streams.  Greedy
+        and sampled, processors, constraint, log-probs (of the raw conditional rows), EOS ids, stop sequences, on_tokens; the
+        bf16 precision mode; the call runs on the session's own loop and closes it.  `speculate` is not served beside it
+        (last_speculation is None).  num_return_sequences > 1: repeat the inputs instead (ValueError); 2 B above MAX_BATCH:
+        ValueError.  last_guidance = {"rows", "prompt_len", "negative_len"} of a served call, else None."""
         if constraint is not None and not isinstance(constraint, TokenAutomaton):
             raise ValueError(f"constraint has to be a constraints.TokenAutomaton, but is {type(constraint).__name__}")
         ids = self._ids(input_ids)
         B, T = ids.shape
         self.last_speculation = None
         self.last_fanout = None
+        self.last_guidance = None
         nret = int(num_return_sequences)
         if nret < 1:
             raise ValueError(f"num_return_sequences must be at least 1, got {num_return_sequences!r}")
+        gd_neg = None
+        if guidance is not None:
+            if nret > 1:
+                raise ValueError("guidance with num_return_sequences > 1: repeat the prompts, the negative prompts and the pixels instead")
+            gd_neg = self._guidance_ids(guidance, B)
+            speculate = None   # not served beside guidance
         if nret > 1 and B * nret > self.MAX_BATCH:
             raise ValueError(f"batch {B} x num_return_sequences {nret} exceeds the {self.MAX_BATCH} rows a replica decodes at a time")
         look = None
@@ -784,6 +799,15 @@ class HipEngine:
                 self.lib.vc_request_constraint(self._model, None)
                 self.lib.vc_request_speculation(self._model, 0, 0, None, None, 0)
                 raise
+        if guidance is not None:
+            try:
+                gd_keep = self._request_guidance(guidance, gd_neg, B)
+            except BaseException:
+                self.lib.vc_clear_attention_mask(self._model)
+                self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
+                self.lib.vc_request_logits_processors(self._model, None)
+                self.lib.vc_request_constraint(self._model, None)
+                raise
         self._check(self.lib.vc_generate(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev,
                                          int(max_new_tokens), eos, pad,
                                          flat.ctypes.data_as(C.c_void_p) if stops else None,
@@ -793,6 +817,8 @@ class HipEngine:
         if errs:
             raise errs[0]
         self._cur_batch = R
+        if guidance is not None:
+            self.last_guidance = self._last_guidance()
         if nret > 1:
             lf = np.zeros((3,), dtype=np.int32)
             if self.lib.vc_last_fanout(self._model, lf.ctypes.data_as(C.c_void_p)) == 0:
@@ -836,6 +862,72 @@ class HipEngine:
         self._cur_batch = B * int(num_beams)
         self.last_beam_steps = n.value
         return out[:, : min(int(lens.max()) + 1, mn)].copy(), lens, score
+
+    # ---- classifier-free guidance (vc_request_guidance) -----------------------------------------------------------------------
+    last_guidance = None     # {"rows", "prompt_len", "negative_len"} of the last guided generate / prefill_guided, else None
+
+    def _guidance_ids(self, guidance, B: int) -> np.ndarray:
+        """every refusal of a guidance request that needs no engine: -> the negative ids [B, Tn] int64"""
+        if not isinstance(guidance, _lp.Guidance):
+            raise ValueError(f"guidance has to be a logits_processors.Guidance, but is {type(guidance).__name__}")
+        if not np.isfinite(float(guidance.scale)):
+            raise ValueError(f"the guidance scale has to be finite, but is {guidance.scale!r}")
+        if 2 * B > self.MAX_BATCH:
+            raise ValueError(f"a guided batch of {B} needs {2 * B} rows: a replica decodes at most {self.MAX_BATCH} at a time")
+        neg = self._ids(guidance.negative_ids)
+        if neg.shape[0] != B or neg.shape[1] < 1:
+            raise ValueError(f"negative ids must be [{B}, Tn], got {tuple(neg.shape)}")
+        for a in (guidance.images, guidance.segs, guidance.depths):
+            self._check_pixels(a, B)
+        if guidance.images is None and bool((neg < 0).any()):
+            raise ValueError("the negative prompt holds image placeholders, but no negative pixels were given")
+        return neg
+
+    def _request_guidance(self, guidance, neg: np.ndarray, B: int):
+        """announces the request for the next generate / prefill call (one-shot); -> what must stay alive until that call returns"""
+        img = guidance.images
+        (pi, ps, pd), on_dev, keep = self._pixels(img, guidance.segs if img is not None else None,
+                                                  guidance.depths if img is not None else None)
+        self._check(self.lib.vc_request_guidance(self._model, C.c_float(float(guidance.scale)), neg.ctypes.data_as(C.c_void_p), B,
+                                                 int(neg.shape[1]), pi, ps, pd, on_dev))
+        return neg, keep
+
+    def _last_guidance(self):
+        lg = np.zeros((4,), dtype=np.int32)
+        if self.lib.vc_last_guidance(self._model, lg.ctypes.data_as(C.c_void_p)) != 0:
+            return None
+        return {"rows": 2 * int(lg[1]), "prompt_len": int(lg[2]), "negative_len": int(lg[3])}
+
+    def prefill_guided(self, input_ids, images, segs=None, depths=None, guidance=None, reserve: Optional[int] = None,
+                       attention_mask=None):
+        """The state of a guided generate for a host loop (vc_prefill with a pending vc_request_guidance): both prompts prefilled
+        into one loop of 2 B rows.  -> (logits [2 B, V]: the rows behind input_ids, then those behind guidance.negative_ids; S of the
+        prompts).  decode_step then takes 2 B tokens (a pair continues with the same token) and returns 2 B rows; every row
+        advances its own position.  rewind / extend / reorder_cache refuse until the next prefill."""
+        ids = self._ids(input_ids)
+        B, T = ids.shape
+        self.last_guidance = None
+        neg = self._guidance_ids(guidance, B)
+        if reserve is not None:
+            self._check(self.lib.vc_model_reserve_decode(self._model, int(reserve)))
+        (pi, ps, pd), on_dev, keep = self._pixels(*self._image_blocks(B, images, segs, depths))
+        self._announce_mask(attention_mask, B, T)
+        last = np.empty((2 * B, self.cfg.vocab_size), dtype=np.float32)
+        S = C.c_int(0)
+        self.last_hidden_states = self.last_attentions = None
+        self.last_token_logprobs = self.last_spliced_labels = None
+        try:
+            gd_keep = self._request_guidance(guidance, neg, B)
+            self._check(self.lib.vc_prefill(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev, 1,
+                                            last.ctypes.data_as(C.c_void_p), None, C.byref(S)))
+        except BaseException:
+            self.lib.vc_clear_attention_mask(self._model)
+            self.lib.vc_request_guidance(self._model, C.c_float(1.0), None, 0, 0, None, None, None, 0)
+            raise
+        self.last_S = self._step_pos = S.value
+        self._cur_batch = 2 * B
+        self.last_guidance = self._last_guidance()
+        return last, S.value
 
     last_beam_steps = 0
     last_speculation = None

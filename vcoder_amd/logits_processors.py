@@ -73,6 +73,46 @@ def make(repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None
     return LogitsProcessors(float(p), n, m, ml, bad)
 
 
+@dataclass
+class Guidance:
+    """A classifier-free guidance request as HipEngine.generate(guidance=) / prefill_guided take it: the scale, the negative prompt's
+    ids [B, Tn] (int64, rectangular, unpadded) and, when they hold placeholders, its pixels [B, 3, S, S] per modality."""
+    scale: float
+    negative_ids: object
+    images: object = None
+    segs: object = None
+    depths: object = None
+
+
+def check_guidance_scale(guidance_scale) -> Optional[float]:
+    """generate(guidance_scale=): None or 1.0 is no request (HF's `_get_logits_processor`) -> None; else the finite scale as a float
+    (ValueError otherwise)"""
+    import math
+
+    if guidance_scale is None:
+        return None
+    if not isinstance(guidance_scale, (int, float)) or isinstance(guidance_scale, bool) or not math.isfinite(guidance_scale):
+        raise ValueError(f"`guidance_scale` has to be a finite float, but is {guidance_scale!r}")
+    return None if float(guidance_scale) == 1.0 else float(guidance_scale)
+
+
+def apply_guidance(cond, uncond, scale: float):
+    """Classifier-free guidance, HF's UnbatchedClassifierFreeGuidanceLogitsProcessor — the FIRST processor of the list: `cond` /
+    `uncond` [R, V] are the raw logits of the step behind the prompt / behind the negative prompt (both followed by the ids
+    generated so far) -> scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond) in fp32, product and sum rounded
+    separately: what guidance_combine_kernel (csrc/select.hip) writes in front of the other processors of the device loop.  The log
+    softmax is taken in the kernel's form, (x - max) - log(sum(exp(x - max)))."""
+    import torch
+
+    def lsm(x):
+        x = x.float()
+        z = x - x.max(dim=-1, keepdim=True)[0]
+        return z - z.exp().sum(dim=-1, keepdim=True).log()
+
+    lc, lu = lsm(cond), lsm(uncond)
+    return torch.tensor(float(scale), dtype=torch.float32) * (lc - lu) + lu
+
+
 def apply_torch(proc: LogitsProcessors, history, scores, prompt_len: int, eos_ids: Sequence[int]):
     """`scores` [R, V] float32 of the next token behind `history` [R, L] int64 (prompt_len prompt ids, then the generated ones)
     -> the processed scores (a new tensor).  HF 4.31's order; fp32 arithmetic (the penalty's division is torch's IEEE division)."""

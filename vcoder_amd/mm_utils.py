@@ -71,6 +71,29 @@ def _ret(ids, return_tensors):
     raise ValueError(f"Unsupported tensor type: {return_tensors}")
 
 
+def strip_placeholders(input_ids):
+    """The same prompt without its image, seg and depth placeholders (every negative id): `input_ids` [B, T] (a tensor, an array or
+    nested lists) -> [B, T'] of the same kind.  This is the visual-contrastive recipe for classifier-free guidance:
+    generate(guidance_scale=g, negative_prompt_ids=strip_placeholders(input_ids)) scores every token a second time behind the
+    question WITHOUT the pictures and pushes the distribution away from what the language prior alone would have said.  The rows
+    must hold the same number of placeholders (the result is rectangular); ValueError otherwise."""
+    import numpy as np
+
+    is_torch = hasattr(input_ids, "detach")
+    a = input_ids.detach().cpu().numpy() if is_torch else np.asarray(input_ids)
+    if a.ndim != 2:
+        raise ValueError("input_ids must be [B, T]")
+    rows = [r[r >= 0] for r in a]
+    if any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("the rows hold different numbers of placeholders: the stripped prompt would not be rectangular")
+    out = np.stack(rows, axis=0) if rows else a
+    if is_torch:
+        import torch
+
+        return torch.from_numpy(np.ascontiguousarray(out)).to(input_ids.device)
+    return out if isinstance(input_ids, np.ndarray) else out.tolist()
+
+
 def expand2square(pil_img, background_color):
     from PIL import Image
 

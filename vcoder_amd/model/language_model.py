@@ -456,7 +456,9 @@ class _HipCausalLMBase:
                  no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
                  bad_words_ids=None, processors_on_device: bool = True, prompt_lookup_num_tokens: Optional[int] = None,
                  max_matching_ngram_size: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False,
-                 speculate_selection: str = "greedy", constraint=None, prefix_allowed_tokens_fn=None, **kwargs):
+                 speculate_selection: str = "greedy", constraint=None, prefix_allowed_tokens_fn=None,
+                 guidance_scale: Optional[float] = None, negative_prompt_ids=None, negative_prompt_attention_mask=None,
+                 negative_images=None, negative_segs=None, negative_depths=None, **kwargs):
         """Returns cat(input_ids, new_ids) [B, T+n] int64 — the prompt part keeps its negative placeholder ids,
         callers slice `[:, T:]` (serve/cli.py:135).
 
@@ -549,6 +551,31 @@ class _HipCausalLMBase:
         num_beams == 1 raises HF's ValueError; with num_beams > 1 NotImplementedError (returning the n best beams is the beam
         scorer's business); B n above 16 ValueError.  n == 1 (the default) is the call it always was.
 
+        guidance_scale = g, negative_prompt_ids [B, Tn] or [1, Tn] (rectangular, unpadded), negative_prompt_attention_mask,
+        negative_images / negative_segs / negative_depths: classifier-free guidance with the semantics of Transformers'
+        UnbatchedClassifierFreeGuidanceLogitsProcessor, the FIRST processor of the list.  Every step scores the next token behind the
+        prompt (raw row c) and behind the negative prompt (raw row u), both followed by the ids generated so far, and everything
+        behind it — the five processors (the repetition penalty's sign test then runs on log-domain values, as in HF), the
+        constraint, the warpers, the greedy or sampled selection — reads g * (log_softmax(c) - log_softmax(u)) + log_softmax(u) in
+        place of c.  Log-probs stay those of the raw conditional row; EOS, stop sequences and max_new_tokens are decided on the
+        conditional stream; the processors' history is input_ids + generated ids.  Without negative_prompt_ids the negative prompt
+        is HF's default, the last prompt token alone.  Placeholders in it are spliced from the negative_* pixels ([B, 3, S, S]);
+        mm_utils.strip_placeholders(input_ids) — the question without its pictures — is the visual-contrastive recipe against
+        object hallucination.  HF runs a second forward per token; here the unconditional row rides in the same weight pass: the
+        device loop steps 2 B rows (guidance_combine_kernel in front of the processor launch, guidance_follow_kernel behind the
+        selection), on the session's own loop, which it closes (decode_step / extend refuse until the next prefill);
+        engine.last_guidance reports it.  Served on the device with greedy and sampled selection, the processors, `constraint`,
+        log-probs, EOS ids, stop sequences, a streamer and num_return_sequences (the inputs are repeated; fan_out=True falls back to
+        that); processors_on_device=False, a stopping criterion that needs host code, prefix_allowed_tokens_fn and the precision
+        modes "split" / "strict" take the host
+        loop, which applies logits_processors.apply_guidance in front of the other processors to the 2 B rows of
+        engine.prefill_guided / decode_step and returns the same ids.  prompt_lookup_num_tokens is not served beside it (the call
+        runs as without it, `speculation` is None).  guidance_scale None or 1.0 is no request (HF's rule): the call takes exactly
+        the path it takes without the arguments, decode pool included.  Refused before the engine is touched: a non-finite scale,
+        placeholders without their pixels, a negative batch other than B or 1, zeros in the mask of a negative prompt
+        (NotImplementedError for a text-only one, as a padded text-only batch), 2 B n above 16 rows (ValueError); num_beams > 1
+        (NotImplementedError).
+
         Everything the reference's callers ask for runs on the device inside the hipGraph-replayed decode loop
         (vc_generate): greedy argmax; sampling with HF's warper order temperature -> top-k -> top-p -> multinomial
         (`top_k` defaults to 50 when sampling, HF's GenerationConfig default, which is what serve/cli.py:122-132 gets);
@@ -590,6 +617,17 @@ class _HipCausalLMBase:
         nrs = int(num_return_sequences)
         if nrs < 1:
             raise ValueError(f"`num_return_sequences` has to be at least 1, got {num_return_sequences!r}")
+        # guidance: every refusal before the engine is touched; None / 1.0 is no request and nothing below changes
+        gscale = _lp.check_guidance_scale(guidance_scale)
+        neg_ids = None
+        if gscale is not None:
+            if num_beams != 1:
+                raise NotImplementedError("guidance_scale is not implemented for num_beams > 1")
+            neg_ids = self._negative_prompt(input_ids, negative_prompt_ids, negative_prompt_attention_mask, negative_images,
+                                            negative_segs, negative_depths)
+            if 2 * input_ids.shape[0] * nrs > self.engine.MAX_BATCH:
+                raise ValueError(f"a guided batch of {input_ids.shape[0]} x num_return_sequences {nrs} needs "
+                                 f"{2 * input_ids.shape[0] * nrs} rows: a replica decodes at most {self.engine.MAX_BATCH} at a time")
         if nrs > 1:
             if num_beams != 1:
                 raise NotImplementedError("num_return_sequences > 1 is not implemented for num_beams > 1: returning the n best beams "
@@ -601,6 +639,7 @@ class _HipCausalLMBase:
                                  "replica decodes at a time")
         self.engine.last_speculation = None
         self.engine.last_fanout = None
+        self.engine.last_guidance = None
         eos_all = self.config.eos_token_id if eos_token_id is None else eos_token_id
         eos_all = [int(e) for e in (eos_all if isinstance(eos_all, (list, tuple)) else ([] if eos_all is None else [eos_all]))]
         proc = _lp.make(repetition_penalty, no_repeat_ngram_size, min_new_tokens, min_length, bad_words_ids, eos_all)
@@ -669,6 +708,9 @@ class _HipCausalLMBase:
         on_device = stops is not None and len(stops) <= 8
         if proc is not None:   # what the device kernel does not hold, or the caller's wish: the host loop applies them
             on_device = on_device and bool(processors_on_device) and proc.fits_device() and len(eos_more) <= _lp.MAX_EOS_EXTRA
+        if gscale is not None:   # the caller's wish holds for a guided call as well: the host loop over engine.prefill_guided;
+            # the device form is the bf16 step's: "split" / "strict" take the host loop too
+            on_device = on_device and bool(processors_on_device) and self.engine.precision == "bf16"
         # a callable runs on the host; an automaton where the call is device-served anyway, else as its own callable
         if prefix_allowed_tokens_fn is not None:
             on_device = False
@@ -689,7 +731,10 @@ class _HipCausalLMBase:
 
             prompts = ids_cpu
             ids_cpu = ids_cpu[torch.as_tensor(rep)]   # what the returned rows carry in front
-            if not on_device:   # the host loop runs over the expanded batch
+            if gscale is not None:   # a guided call repeats its inputs here, both prompts: the engine sees B n sequences
+                neg_ids = neg_ids[rep]
+                negative_images, negative_segs, negative_depths = expand(negative_images), expand(negative_segs), expand(negative_depths)
+            if not on_device or gscale is not None:   # the host loop runs over the expanded batch
                 images, segs, depths, attention_mask = expand(images), expand(segs), expand(depths), expand(attention_mask)
                 if lookup_ids is not None and not (B == 1 and all(np.ndim(q) == 0 for q in lookup_ids)):
                     lookup_ids = expand(list(lookup_ids))
@@ -697,6 +742,12 @@ class _HipCausalLMBase:
                 prompts = ids_cpu
         else:
             prompts = ids_cpu
+        gd = None
+        if gscale is not None:
+            neg_px = negative_images is not None
+            gd = _lp.Guidance(gscale, neg_ids, negative_images, (negative_segs if self.variant != "llava" else None) if neg_px else None,
+                              (negative_depths if self.variant == "vcoder_ds" else None) if neg_px else None)
+            prompt_lookup_num_tokens = None   # not served beside guidance
         if streamer is not None:
             streamer.put(ids_cpu)
         if on_device:
@@ -715,7 +766,8 @@ class _HipCausalLMBase:
                                        speculate=None if prompt_lookup_num_tokens is None else int(prompt_lookup_num_tokens),
                                        lookup_ngram=int(max_matching_ngram_size), lookup_ids=lookup_ids,
                                        speculate_selection=speculate_selection, constraint=constraint,
-                                       **(dict(num_return_sequences=nrs, fan_out=bool(fan_out)) if nrs > 1 else {}))
+                                       **(dict(guidance=gd) if gd is not None else {}),
+                                       **(dict(num_return_sequences=nrs, fan_out=bool(fan_out)) if nrs > 1 and gd is None else {}))
             self._generation += 1
             out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
             if want_lp:
@@ -724,8 +776,12 @@ class _HipCausalLMBase:
             if streamer is not None:
                 streamer.end()
         else:
-            last, _, S = self.engine.prefill(ids_cpu.numpy(), images, segs, depths, has_attention_mask=True,
-                                             reserve=max_new_tokens, attention_mask=attention_mask)
+            if gd is not None:   # 2 B rows: the prompts', then the negative prompts'; a pair continues with the same token
+                last, S = self.engine.prefill_guided(ids_cpu.numpy(), images, segs, depths, guidance=gd, reserve=max_new_tokens,
+                                                     attention_mask=attention_mask)
+            else:
+                last, _, S = self.engine.prefill(ids_cpu.numpy(), images, segs, depths, has_attention_mask=True,
+                                                 reserve=max_new_tokens, attention_mask=attention_mask)
             self.engine.clear_attention_mask()   # generate(): the cached steps run under an all-ones mask (:130-133)
             self._generation += 1
             logits = torch.from_numpy(last)
@@ -738,6 +794,9 @@ class _HipCausalLMBase:
             for step in range(max_new_tokens):
                 scores = logits.float()
                 raw = scores
+                if gd is not None:   # the first processor of the list; the log-probs below stay those of the raw conditional rows
+                    raw = scores[:B]
+                    scores = _lp.apply_guidance(scores[:B], scores[B:], gscale)
                 if proc is not None:   # in front of the warpers, as HF; the log-probs below stay those of `raw`
                     scores = _lp.apply_torch(proc, cur, scores, T, ([] if eos is None else [int(eos)]) + eos_more)
                 if allowed_fn is not None:   # behind the processors (4.31's order); finished rows emit pad: not constrained
@@ -784,7 +843,8 @@ class _HipCausalLMBase:
                         stop = stop or bool(r.all() if hasattr(r, "all") else r)
                 if stop or step + 1 == max_new_tokens:
                     break
-                lg, _ = self.engine.decode_step(nxt.numpy().astype(np.int32))
+                step_tok = nxt.numpy().astype(np.int32)
+                lg, _ = self.engine.decode_step(np.concatenate([step_tok, step_tok]) if gd is not None else step_tok)
                 logits = torch.from_numpy(lg)
             out = cur
             if want_lp:
@@ -804,6 +864,46 @@ class _HipCausalLMBase:
                               top_token_ids=top_id if K else None, sequence_logprob=tok_lp.sum(dim=1), speculation=spec)
 
     _sample_calls = 0
+
+    def _negative_prompt(self, input_ids, negative_prompt_ids, negative_prompt_attention_mask, negative_images, negative_segs,
+                         negative_depths):
+        """the negative prompt of a guided generate as [B, Tn] int64 numpy — HF's default (the last prompt token alone) without
+        negative_prompt_ids; every refusal that needs no engine"""
+        B = input_ids.shape[0]
+        to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if negative_prompt_ids is None:
+            neg = to_np(input_ids)[:, -1:]
+        else:
+            neg = to_np(negative_prompt_ids)
+            if neg.ndim != 2 or neg.shape[0] not in (1, B) or neg.shape[1] < 1:
+                raise ValueError(f"`negative_prompt_ids` has to be [{B}, Tn] or [1, Tn], but is {tuple(neg.shape)}")
+            if neg.shape[0] != B:
+                neg = np.repeat(neg, B, axis=0)
+        neg = np.ascontiguousarray(neg, dtype=np.int64)
+        if negative_prompt_attention_mask is not None:
+            mk = to_np(negative_prompt_attention_mask)
+            if mk.ndim != 2 or mk.shape[1] != neg.shape[1] or mk.shape[0] not in (1, B):
+                raise ValueError(f"`negative_prompt_attention_mask` has to match negative_prompt_ids, but is {tuple(mk.shape)}")
+            if not bool(np.all(mk != 0)):
+                if negative_images is None:
+                    raise NotImplementedError("a padded TEXT-ONLY batch (attention_mask with zeros, images=None) is outside the "
+                                              "VCoder hot path")
+                raise ValueError("`negative_prompt_ids` has to be rectangular and unpadded: its attention mask holds zeros")
+        s = self.engine.cfg.vit_image_size
+        for name, a in (("negative_images", negative_images), ("negative_segs", negative_segs), ("negative_depths", negative_depths)):
+            if a is not None and tuple(a.shape) != (B, 3, s, s):
+                raise ValueError(f"`{name}` has to be [{B}, 3, {s}, {s}], but is {tuple(a.shape)}")
+        if negative_images is None and (negative_segs is not None or negative_depths is not None):
+            raise ValueError("`negative_segs` / `negative_depths` need `negative_images`")
+        if bool((neg < 0).any()):
+            if negative_images is None:
+                raise ValueError("`negative_prompt_ids` holds image placeholders, but no `negative_images` were given")
+            from ..constants import DEPTH_TOKEN_INDEX, SEG_TOKEN_INDEX
+            if bool((neg == SEG_TOKEN_INDEX).any()) and self.variant != "llava" and negative_segs is None:
+                raise ValueError("`negative_prompt_ids` holds seg placeholders, but no `negative_segs` were given")
+            if bool((neg == DEPTH_TOKEN_INDEX).any()) and self.variant == "vcoder_ds" and negative_depths is None:
+                raise ValueError("`negative_prompt_ids` holds depth placeholders, but no `negative_depths` were given")
+        return neg
 
     # ---- beam search (HF GenerationMixin.beam_search + BeamSearchScorer of the reference's pinned Transformers 4.31) -----------
     def _beam_search_device(self, input_ids, images, segs, depths, num_beams, max_new_tokens, max_length, eos_token_id, pad_token_id,
