@@ -418,6 +418,23 @@ int vc_request_guidance(vc_model* m, float scale, const int64_t* neg_ids, int B,
  * prompts, spliced length of the negative prompts}.  VC_ERR_STATE when that call had no request. */
 int vc_last_guidance(vc_model* m, int32_t* out /* [4] */);
 
+/* The further warpers of the NEXT vc_generate call (one-shot): HF's MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper and
+ * EtaLogitsWarper with min_tokens_to_keep = 1, applied on the device behind those of vc_sampling, in HF's order:
+ *     temperature -> top-k -> top-p -> min-p -> typical -> epsilon -> eta -> draw
+ * Every warper sees the row with what those in front of it removed at -inf: its softmax and its entropy H are taken over the survivors.
+ *   min_p           p < min_p * max p is removed (the maximum always stays).  [0, 1]; 0: off
+ *   typical_p       s_i = |-log p_i - H|; in ascending order of s the first tokens whose cumulative probability reaches typical_p stay,
+ *                   equal s together.  > 0; >= 1: off
+ *   epsilon_cutoff  p < epsilon_cutoff is removed unless the score equals the maximum.  [0, 1); 0: off
+ *   eta_cutoff      p < min(eta_cutoff, sqrt(eta_cutoff) * exp(-H)) is removed unless the score equals the maximum.  [0, 1); 0: off
+ * The values travel in the rows' records, so the request neither moves a call to another loop (a sampled call of the decode pool runs
+ * there, beside rows with other settings) nor changes a captured step; logits processors, a token automaton, guidance, log-probs, a
+ * fan-out and speculation with the "any" selection select through the same code and combine freely.  A greedy call (samp NULL or
+ * do_sample 0) applies none of them, as HF does.  With all four off the call takes the path and returns the bits it would without
+ * the request.  A value outside its range: VC_ERR_INVALID, nothing changed.  Cleared when the next vc_generate returns, also when it
+ * fails; vc_prefill, vc_generate_beam and the scoring calls ignore and clear it. */
+int vc_request_sampling_warpers(vc_model* m, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff);
+
 /* Logits processors of the NEXT vc_generate / vc_generate_greedy* call (one-shot), applied on the device in front of every selection
  * of the loop, in HF 4.31's order (generation/logits_process.py):
  *   repetition_penalty p   RepetitionPenaltyLogitsProcessor: every id t of the row's history gets raw[t] < 0 ? raw[t] * p : raw[t] / p

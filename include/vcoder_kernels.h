@@ -164,6 +164,12 @@ void vck_spec_accept_sel(const float* logits, int ldl, int V, int* rows, int* ne
  * lds_floats: -1 = the scaled row is staged in LDS when the device allows, 0 = never (every pass re-reads global memory). */
 void vck_spec_select(const float* logits, int ldl, int V, const int* rows, const int* nq, int* sel, int B, int Q, int lds_floats,
                      void* stream);
+/* test hook of the sampler's warpers: keep[r * V + i] (int32 0 / 1) = whether the sampled selection of logits row r under record r can
+ * draw token i — the set left by temperature -> top-k -> top-p -> min-p -> typical -> epsilon -> eta (record words 9 .. 11 and
+ * 114 .. 117: 1 / temperature, top_k, top_p, min_p, typical_p, epsilon_cutoff, eta_cutoff as float bits, zero = off for the last
+ * four), computed by the threshold code vck_select_embed / vck_spec_select run.  Words 0 (active) and 8 (sample) are not looked at.
+ * One workgroup per row; lds_floats as vck_spec_select takes it. */
+void vck_warp_support(const float* logits, int ldl, int V, const int* rows, int nrows, int* keep, int lds_floats, void* stream);
 /* test hook of the sampler: u[i] = the uniform in (0,1) the Gumbel-max draw derives from 32-bit hash h[i] (strictly
  * inside the interval for EVERY h, so the Gumbel term -log(-log(u)) written to gumbel[i] is finite) */
 void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, void* stream);

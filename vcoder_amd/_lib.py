@@ -139,6 +139,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.vc_request_guidance.restype = C.c_int
     lib.vc_last_guidance.argtypes = [vp, vp]
     lib.vc_last_guidance.restype = C.c_int
+    lib.vc_request_sampling_warpers.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
+    lib.vc_request_sampling_warpers.restype = C.c_int
+    lib.vck_warp_support.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp]
+    lib.vck_warp_support.restype = None
     lib.vck_guidance_combine.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32, vp]
     lib.vck_guidance_combine.restype = None
     lib.vck_guidance_follow.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]

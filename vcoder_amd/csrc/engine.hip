@@ -431,6 +431,10 @@ struct vc_model {
     int gd_pair = 0;              // > 0: a guided vc_prefill left a loop of 2 gd_pair rows (pairs at different positions) for vc_decode_step
     bool gd_last = false;
     int gd_last_B = 0, gd_last_Sc = 0, gd_last_Sn = 0;
+    // the further warpers of the NEXT vc_generate (vc_request_sampling_warpers; one-shot): min_p, typical_p, epsilon_cutoff,
+    // eta_cutoff of a sampled call — 0 (typical_p: also >= 1) is off.  They travel in the rows' records (RS_MINP .. RS_ETA) and
+    // change neither the loop a call runs on nor a captured step
+    float warp_min_p = 0.f, warp_typical = 0.f, warp_eps = 0.f, warp_eta = 0.f;
     bool tok_stale = false;       // vc_rewind ran: the token the last step selected on the device no longer continues the sequence
     bool plan_only = false;       // do_prefill stops behind the splice plan (vc_plan_spliced_len): no tower pass, no state change
     int reserve_new = 64;         // KV slots a vc_prefill keeps free behind the prompt (vc_model_reserve_decode)
@@ -518,6 +522,7 @@ static void clear_guidance_request(vc_model* m) {
     m->gd_B = m->gd_T = m->gd_px_on_dev = 0;
     for (auto& p : m->gd_px) p = nullptr;
 }
+static void clear_sampling_warpers_request(vc_model* m) { m->warp_min_p = m->warp_typical = m->warp_eps = m->warp_eta = 0.f; }
 static void clear_generate_logprobs_request(vc_model* m) {
     m->glp_k = 0;
     m->glp_tok = m->glp_top = nullptr;
@@ -543,6 +548,7 @@ struct OneShotReset {
         clear_constraint_request(m);
         clear_speculation_request(m);
         clear_guidance_request(m);
+        clear_sampling_warpers_request(m);
         m->fan_n = 0;
         m->fan_rows = 0;
     }

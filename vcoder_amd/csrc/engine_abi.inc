@@ -893,6 +893,26 @@ VC_API int vc_last_guidance(vc_model* m, int32_t* out) {
     return VC_OK;
 }
 
+/* The further warpers of the NEXT vc_generate call (one-shot): min_p, typical_p, epsilon_cutoff, eta_cutoff behind temperature /
+ * top-k / top-p of a sampled call.  See include/vcoder_hip.h. */
+VC_API int vc_request_sampling_warpers(vc_model* m, float min_p, float typical_p, float epsilon_cutoff, float eta_cutoff) {
+    if (!m) return VC_ERR_INVALID;
+    // (a refusal leaves a pending request as it was: nothing touched)
+    auto refuse = [&](const char* why) {
+        m->ctx->err = std::string("vc_request_sampling_warpers: ") + why;
+        return VC_ERR_INVALID;
+    };
+    if (!(min_p >= 0.f && min_p <= 1.f)) return refuse("min_p must be in [0, 1]");
+    if (!(typical_p > 0.f) || !std::isfinite(typical_p)) return refuse("typical_p must be positive (>= 1: off)");
+    if (!(epsilon_cutoff >= 0.f && epsilon_cutoff < 1.f)) return refuse("epsilon_cutoff must be in [0, 1)");
+    if (!(eta_cutoff >= 0.f && eta_cutoff < 1.f)) return refuse("eta_cutoff must be in [0, 1)");
+    m->warp_min_p = min_p;
+    m->warp_typical = typical_p < 1.f ? typical_p : 0.f;
+    m->warp_eps = epsilon_cutoff;
+    m->warp_eta = eta_cutoff;
+    return VC_OK;
+}
+
 namespace {
 void guided_prefill(vc_model* m, const int64_t* ids, int B, int T, const float* img, const float* seg, const float* depth, int on_dev,
                     int has_mask, float* logits_last, int* S_out);   // engine_pool.inc

@@ -954,6 +954,7 @@ struct GenParams {  // what a generate() call asks for (HF GenerationMixin subse
     int max_new = 0, eos = -1, pad = 0;
     int do_sample = 0, top_k = 0;
     float temperature = 1.f, top_p = 1.f;
+    float min_p = 0.f, typical_p = 0.f, epsilon_cutoff = 0.f, eta_cutoff = 0.f;   // vc_request_sampling_warpers; 0: off
     uint64_t seed = 0;
     int n_stop = 0;
     int stop[VC_MAX_STOP][1 + VC_MAX_STOP_LEN] = {};
@@ -990,6 +991,10 @@ void fill_rows(int* rec, int B, const GenParams& g, int pos, const int* tail /*[
         memcpy(&r[RS_INVTEMP], &inv_t, 4);
         r[RS_TOPK] = g.top_k;
         memcpy(&r[RS_TOPP], &g.top_p, 4);
+        memcpy(&r[RS_MINP], &g.min_p, 4);
+        memcpy(&r[RS_TYPICAL], &g.typical_p, 4);
+        memcpy(&r[RS_EPS], &g.epsilon_cutoff, 4);
+        memcpy(&r[RS_ETA], &g.eta_cutoff, 4);
         r[RS_SEED_LO] = (int)mix_seed(g.seed, (uint32_t)b, 0x51u);  // per-row streams: independent of the row's slot
         r[RS_SEED_HI] = (int)mix_seed(g.seed, (uint32_t)b, 0xA7u);
         r[RS_OUT_OFF] = out_off0 + b * out_stride;

@@ -1321,6 +1321,11 @@ VC_API int vc_generate(vc_model* m, const int64_t* ids, int B, int T, const floa
         g.top_k = samp->top_k;
         g.top_p = samp->top_p;
         g.seed = samp->seed;
+        // vc_request_sampling_warpers: into the records (a greedy call applies no warper, as in HF)
+        g.min_p = m->warp_min_p;
+        g.typical_p = m->warp_typical;
+        g.epsilon_cutoff = m->warp_eps;
+        g.eta_cutoff = m->warp_eta;
     }
     constexpr int TL = VC_MAX_STOP_LEN - 1;
     std::vector<int> tail((size_t)B * TL, INT32_MIN);  // ids never equal INT32_MIN

@@ -125,6 +125,9 @@ VCK_EXPORT void vck_spec_select(const float* logits, int ldl, int V, const int* 
     SpecSelectArgs a{logits, ldl, V, rows, nq, sel, B, Q, 0};
     launch_spec_select(a, lds_floats, S(stream));
 }
+VCK_EXPORT void vck_warp_support(const float* logits, int ldl, int V, const int* rows, int nrows, int* keep, int lds_floats, void* stream) {
+    launch_warp_support(logits, ldl, V, rows, nrows, keep, lds_floats, S(stream));
+}
 VCK_EXPORT int vck_row_state_stride() { return RS_STRIDE; }
 VCK_EXPORT void vck_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, void* stream) {
     launch_uniform_probe(h, u, gumbel, n, S(stream));

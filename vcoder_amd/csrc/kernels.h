@@ -446,11 +446,17 @@ enum RowStateField : int {
     RS_CN_STATE = 111,    // state behind out_ids[0 .. RS_CN_POS) (-1: dead)
     RS_CN_POS = 112,      // ids of the row the state has consumed
     RS_GD_SCALE = 113,    // float bits: the guidance scale of a conditional row (guidance_combine_kernel)
+    // the four further warpers of a sampled row, behind top-p in HF's order (select.hip warp_thresholds); float bits, and the zero of
+    // a cleared record is off for each
+    RS_MINP = 114,        // MinPLogitsWarper: p < min_p * max p is removed
+    RS_TYPICAL = 115,     // TypicalLogitsWarper: the mass; 0 or >= 1: off
+    RS_EPS = 116,         // EpsilonLogitsWarper: p < epsilon is removed
+    RS_ETA = 117,         // EtaLogitsWarper: p < min(eta, sqrt(eta) exp(-H)) is removed
     RS_STRIDE = 128,
 };
 constexpr int VC_MAX_BAD_WORDS = 32, VC_MAX_BAD_WORD_LEN = 8, VC_MAX_EOS_EXTRA = 8;
 static_assert(RS_STOP + VC_MAX_STOP * (1 + VC_MAX_STOP_LEN) <= RS_LP_NGRAM, "row record overflow");
-static_assert(RS_LP_EOS + VC_MAX_EOS_EXTRA <= RS_CN_ON && RS_CN_POS < RS_STRIDE, "row record overflow");
+static_assert(RS_LP_EOS + VC_MAX_EOS_EXTRA <= RS_CN_ON && RS_ETA < RS_STRIDE, "row record overflow");
 
 // selection (greedy / sampled) + EOS / stop bookkeeping + embedding of the selected token (fp32 residual row x, RMSNorm
 // partials ssq, first GEMV operand xg = bf16(x * xg_w)) + per-row step / position advance: one workgroup per row
@@ -538,6 +544,10 @@ struct SpecSelectArgs {
 };
 // lds_floats < 0: stage the scaled row in LDS when the device allows; 0 (or < V): every pass re-reads the row from global memory
 void launch_spec_select(const SpecSelectArgs& a, int lds_floats, hipStream_t s);
+// test hook: keep[r * V + i] = 1 when the sampled selection of logits row r under record r may draw token i, else 0 — the kept set of
+// temperature -> top-k -> top-p -> min-p -> typical -> epsilon -> eta, from the threshold code the selection itself runs (select.hip
+// warp_thresholds).  RS_SAMPLE and RS_ACTIVE are not looked at.  One workgroup per row; lds_floats as launch_spec_select takes it.
+void launch_warp_support(const float* logits, int ldl, int V, const int* rows, int nrows, int* keep, int lds_floats, hipStream_t s);
 void launch_advance(int* step_dev, int* pos_dev, int* ctx_dev, hipStream_t s);
 // scoring: logprob[r] = logits[r, target[r]] - logsumexp(logits[r, 0:V]) for `rows` rows of stride ldl floats (ldl >= V; any V, any
 // alignment), one workgroup per row, fp32 throughout (select.hip)

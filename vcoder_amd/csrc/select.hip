@@ -4,7 +4,9 @@
 //   greedy   : fp32 argmax, lowest index on ties            [HF] generation/utils.py:2894,2925
 //   sampling : temperature -> top-k -> top-p -> multinomial  [HF] generation/logits_process.py (TemperatureLogitsWarper,
 //              TopKLogitsWarper, TopPLogitsWarper) + utils.py:2921-2923; what vcoder_llava/serve/cli.py:122-132 asks for
-//              (do_sample=True, temperature=0.2) and serve/chat.py:141-151 (temperature, top_p)
+//              (do_sample=True, temperature=0.2) and serve/chat.py:141-151 (temperature, top_p); behind top-p, when the row's
+//              record asks for them: min-p -> typical -> epsilon -> eta (MinPLogitsWarper, TypicalLogitsWarper,
+//              EpsilonLogitsWarper, EtaLogitsWarper; warp_thresholds below)
 //   finished rows emit pad, EOS finishes a row                [HF] generation/utils.py:2928-2929
 //   keyword stop: suffix match of the row's ids               vcoder_llava/mm_utils.py:128-151 (KeywordsStoppingCriteria)
 //   embedding of the chosen token                             [HF] llama/modeling_llama.py:377
@@ -159,11 +161,203 @@ VC_DEV int emit_token(int* rs, int* out, int step, int sel) {
     return tok;
 }
 
+// The scaled row z = logits / temperature of a sampled selection: from its LDS staging when the row fits (lds_floats >= V), else
+// recomputed from global memory in every pass — the same ROUNDED product (no contraction into the subtraction or the addition that
+// consumes it: a pass that fused it would see another z than the pass that found the threshold, and the token that sits exactly on
+// a typical band's tau would fall out of its own band), so both forms and all passes see the same bits.  The form is a template
+// argument: every pass over the row is compiled for its form alone.
+template <bool STAGED>
+struct ScaledRow {
+    const float* lg;
+    float* zs;
+    float inv_t;
+    VC_DEV float operator()(int i) const {
+#pragma clang fp contract(off)
+        return STAGED ? zs[i] : lg[i] * inv_t;
+    }
+    VC_DEV void stage(int V, int tid) const {   // all threads of the workgroup
+#pragma clang fp contract(off)
+        if (!STAGED) return;
+        for (int i = tid; i < V; i += 1024) zs[i] = lg[i] * inv_t;
+        __syncthreads();
+    }
+};
+
+// The kept set of a sampled row — what is left behind temperature -> top-k -> top-p -> min-p -> typical -> epsilon -> eta — as a
+// predicate on the scaled VALUE: two bounds on its order-preserving key (top-k, top-p), a floor (min-p, epsilon, eta: each removes
+// what lies under a probability, and the probability rises with z) and a band around the expected value (typical, below).  Equal
+// values are kept or removed together, as HF's warpers do.  -inf entries (processors, an automaton) are never kept.
+struct WarpSet {
+    uint32_t kmin = 0;          // keep keys >= kmin (top-k)
+    uint32_t kgt = 0;           // keep keys > kgt (top-p; 0 = none removed: no finite value has key 0)
+    bool only_max = false;      // top_p <= 0: the draw is the argmax of what top-k left
+    bool typ = false;           // the typical band applies: bits(|z - typ_c|) <= typ_tau
+    float typ_c = 0.f;
+    uint32_t typ_tau = 0;
+    float zfloor = -INFINITY;   // keep z >= zfloor (never above the maximum of the set it was taken over)
+};
+VC_DEV bool warp_kept(const WarpSet& w, float v) {
+    const uint32_t k = fkey(v);
+    if (k < w.kmin || k <= w.kgt || !(v > -INFINITY)) return false;
+    if (v < w.zfloor) return false;
+    return !w.typ || __builtin_bit_cast(uint32_t, fabsf(v - w.typ_c)) <= w.typ_tau;
+}
+
+// (max, sum e, [sum e (z - max)]) over the kept set w of the row, e = exp(z - max): log Z = max + log S, H = log S - A / S
+template <bool STAGED>
+VC_DEV float warp_max(const ScaledRow<STAGED>& z, int V, const WarpSet& w, BlockRed& red, int tid, int lane, int wave) {
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += 1024) {
+        const float v = z(i);
+        if (warp_kept(w, v)) mx = fmaxf(mx, v);
+    }
+    int dummy = 0;
+    block_argmax(mx, dummy, red, lane, wave);
+    return mx;
+}
+template <bool STAGED>
+VC_DEV void warp_mass(const ScaledRow<STAGED>& z, int V, const WarpSet& w, float mx, bool want_a, float& S, float& A, BlockRed& red, int tid,
+                      int lane, int wave) {
+    float s = 0.f, a = 0.f;
+    for (int i = tid; i < V; i += 1024) {
+        const float v = z(i);
+        if (!warp_kept(w, v)) continue;
+        const float e = __expf(v - mx);
+        s += e;
+        a += e * (v - mx);
+    }
+    S = block_sum_f(s, red, lane, wave);
+    A = want_a ? block_sum_f(a, red, lane, wave) : 0.f;
+}
+// the floor that removes p < thr of a set with maximum mx and mass S (e < thr S), the maximum itself exempt
+VC_DEV float warp_floor(float zfloor, float mx, float thr, float S) { return fmaxf(zfloor, fminf(mx, mx + logf(thr * S))); }
+
+// The thresholds of the kept set of ONE sampled row under the record `rs`, in HF's warper order; every warper sees the survivors of
+// those in front of it.  All 1024 threads of the workgroup call it and all get the same WarpSet; the block shape is part of the
+// arithmetic (the loop strides, block_sum_f's fixed order for every mass).  A warper that is off costs its compare on the record.
+//   top-k    : keep z >= the k-th largest value (bisection over the key, counting)
+//   top-p    : ascending cumulative probability <= 1 - top_p is removed (bisection over the key, masses)
+//   min-p    : p < min_p max p  <=>  z < max + log(min_p): no pass over the row at all
+//   typical  : s_i = |-log p_i - H| = |z_i - c| with c = max + A / S, the expected value of z under p — log Z cancels.  s >= 0, so its
+//              fp32 bits are an order-preserving key; tau = the largest key u with sum_{s_j < u} e_j < mass S is HF's s[last] (the
+//              first entry of the ascending order whose cumulative probability reaches the mass), ties included
+//   epsilon  : p < eps, eta: p < min(eta, sqrt(eta) exp(-H)) — one mass pass each (eta: with A), then a floor; the maximum of the
+//              set they see is exempt, which behind a typical band need not be the row's maximum: it is taken again there
+template <bool STAGED>
+VC_DEV WarpSet warp_thresholds(const ScaledRow<STAGED>& z, int V, const int* rs, BlockRed& red, int tid, int lane, int wave) {
+    WarpSet w;
+    const int top_k = rs[RS_TOPK];
+    const float top_p = __builtin_bit_cast(float, rs[RS_TOPP]);
+    const float min_p = __builtin_bit_cast(float, rs[RS_MINP]), typical = __builtin_bit_cast(float, rs[RS_TYPICAL]);
+    const float eps = __builtin_bit_cast(float, rs[RS_EPS]), eta = __builtin_bit_cast(float, rs[RS_ETA]);
+    const bool typ_on = typical > 0.f && typical < 1.f;
+    const bool more = min_p > 0.f || typ_on || eps > 0.f || eta > 0.f;
+    // ---- top-k: keep z >= (k-th largest value); ties at the threshold are all kept, as TopKLogitsWarper does
+    if (top_k > 0 && top_k < V) {
+        uint32_t t = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = t | (1u << bit);
+            int c = 0;
+            for (int i = tid; i < V; i += 1024) c += fkey(z(i)) >= cand;
+            if (block_sum_i(c, red, lane, wave) >= top_k) t = cand;
+        }
+        w.kmin = t;
+    }
+    // ---- top-p over the survivors: ascending cumulative probability <= 1 - top_p is removed (TopPLogitsWarper)
+    float mx = -INFINITY;   // the row's maximum: it survives top-k, top-p and min-p
+    if (top_p < 1.0f || more) {
+        for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, z(i));
+        int dummy = 0;
+        block_argmax(mx, dummy, red, lane, wave);
+    }
+    if (top_p < 1.0f) {
+        const uint32_t kmin = w.kmin;
+        float zsum = 0.f;
+        for (int i = tid; i < V; i += 1024) {
+            const float v = z(i);
+            if (fkey(v) >= kmin) zsum += __expf(v - mx);
+        }
+        zsum = block_sum_f(zsum, red, lane, wave);
+        const float target = (1.0f - top_p) * zsum;
+        if (!(top_p > 0.f)) {
+            w.only_max = true;
+        } else {
+            uint32_t t = 0;
+            for (int bit = 31; bit >= 0; --bit) {
+                const uint32_t cand = t | (1u << bit);
+                float mass = 0.f;
+                for (int i = tid; i < V; i += 1024) {
+                    const float v = z(i);
+                    const uint32_t k = fkey(v);
+                    if (k >= kmin && k <= cand) mass += __expf(v - mx);
+                }
+                if (block_sum_f(mass, red, lane, wave) <= target) t = cand;
+            }
+            w.kgt = t;
+        }
+    }
+    if (!more || w.only_max) return w;
+    // ---- min-p (MinPLogitsWarper): e < min_p, the maximum (e = 1) always kept
+    if (min_p > 0.f) w.zfloor = fmaxf(w.zfloor, fminf(mx, mx + logf(min_p)));
+    // ---- typical (TypicalLogitsWarper)
+    if (typ_on) {
+        float S, A;
+        warp_mass(z, V, w, mx, true, S, A, red, tid, lane, wave);
+        const float c = mx + A / S, target = typical * S;
+        uint32_t t = 0;
+        for (int bit = 30; bit >= 0; --bit) {   // (bit 31 is the sign: no s has it)
+            const uint32_t cand = t | (1u << bit);
+            float mass = 0.f;
+            for (int i = tid; i < V; i += 1024) {
+                const float v = z(i);
+                if (warp_kept(w, v) && __builtin_bit_cast(uint32_t, fabsf(v - c)) < cand) mass += __expf(v - mx);
+            }
+            if (block_sum_f(mass, red, lane, wave) < target) t = cand;
+        }
+        w.typ = true;
+        w.typ_c = c;
+        w.typ_tau = t;
+        if (eps > 0.f || eta > 0.f) mx = warp_max(z, V, w, red, tid, lane, wave);   // the band may have removed the maximum
+    }
+    // ---- epsilon (EpsilonLogitsWarper)
+    if (eps > 0.f) {
+        float S, A;
+        warp_mass(z, V, w, mx, false, S, A, red, tid, lane, wave);
+        w.zfloor = warp_floor(w.zfloor, mx, eps, S);
+    }
+    // ---- eta (EtaLogitsWarper): the cutoff shrinks with the entropy of what is left
+    if (eta > 0.f) {
+        float S, A;
+        warp_mass(z, V, w, mx, true, S, A, red, tid, lane, wave);
+        const float H = logf(S) - A / S;
+        w.zfloor = warp_floor(w.zfloor, mx, fminf(eta, sqrtf(eta) * expf(-H)), S);
+    }
+    return w;
+}
+
+// the sampled selection of select_row in one staging form: the warpers, then the multinomial over the kept set as a Gumbel-max —
+// argmax_i (z_i - log(-log u_i)) ~ softmax(z) restricted to it
+template <bool STAGED>
+VC_DEV int sample_row(const ScaledRow<STAGED>& z, int V, const int* rs, int step, BlockRed& red, int tid, int lane, int wave) {
+    const uint32_t seed_lo = (uint32_t)rs[RS_SEED_LO], seed_hi = (uint32_t)rs[RS_SEED_HI];
+    z.stage(V, tid);
+    const WarpSet w = warp_thresholds(z, V, rs, red, tid, lane, wave);
+    float best = -INFINITY;
+    int bi = 0x7FFFFFFF;
+    for (int i = tid; i < V; i += 1024) {
+        const float v = z(i);
+        if (!warp_kept(w, v)) continue;
+        const float g = w.only_max ? 0.f : -__logf(-__logf(sample_uniform(seed_lo, seed_hi, (uint32_t)step, (uint32_t)i)));
+        argmax_combine2(best, bi, v + g, i);
+    }
+    block_argmax(best, bi, red, lane, wave);
+    return bi;
+}
+
 // The raw selection of ONE logits row `lg` under the record `rs` with the sampler key `step` (the generated index the token will
-// have): greedy — the argmax, lowest id on ties; sampled — temperature -> top-k -> top-p -> Gumbel-max.  -> the id, in every thread.
-// Called by all 1024 threads of a workgroup; the block shape is part of the arithmetic (the loop strides, block_sum_f's order for the
-// top-p mass), so select_embed_kernel and spec_select_kernel share this one body.  zs: the [V] LDS staging of the scaled row, used
-// when lds_floats >= V (sampling only).
+// have): greedy — the argmax, lowest id on ties; sampled — temperature -> the warpers of warp_thresholds -> Gumbel-max.  -> the id, in
+// every thread.  Called by all 1024 threads of a workgroup; the block shape is part of the arithmetic, so select_embed_kernel and
+// spec_select_kernel share this one body.  zs: the [V] LDS staging of the scaled row, used when lds_floats >= V (sampling only).
 VC_DEV int select_row(const float* lg, int V, const int* rs, int step, float* zs, int lds_floats, BlockRed& red, int tid, int lane,
                       int wave) {
     float best = -INFINITY;
@@ -177,71 +371,12 @@ VC_DEV int select_row(const float* lg, int V, const int* rs, int step, float* zs
         block_argmax(best, bi, red, lane, wave);
     } else {
         const float inv_t = __builtin_bit_cast(float, rs[RS_INVTEMP]);
-        const int top_k = rs[RS_TOPK];
-        const float top_p = __builtin_bit_cast(float, rs[RS_TOPP]);
-        const uint32_t seed_lo = (uint32_t)rs[RS_SEED_LO], seed_hi = (uint32_t)rs[RS_SEED_HI];
-        const bool staged = lds_floats >= V;
-        auto z = [&](int i) { return staged ? zs[i] : lg[i] * inv_t; };
-        if (staged) {
-            for (int i = tid; i < V; i += 1024) zs[i] = lg[i] * inv_t;
-            __syncthreads();
-        }
-        // ---- top-k: keep z >= (k-th largest value); ties at the threshold are all kept, as TopKLogitsWarper does
-        uint32_t kmin = 0;  // keep keys >= kmin
-        if (top_k > 0 && top_k < V) {
-            uint32_t t = 0;
-            for (int bit = 31; bit >= 0; --bit) {
-                const uint32_t cand = t | (1u << bit);
-                int c = 0;
-                for (int i = tid; i < V; i += 1024) c += fkey(z(i)) >= cand;
-                if (block_sum_i(c, red, lane, wave) >= top_k) t = cand;
-            }
-            kmin = t;
-        }
-        // ---- top-p over the survivors: ascending cumulative probability <= 1 - top_p is removed (TopPLogitsWarper)
-        uint32_t kgt = 0;  // keep keys > kgt (0 = none removed: no finite value has key 0)
-        bool only_max = false;
-        if (top_p < 1.0f) {
-            float mx = -INFINITY;
-            for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, z(i));
-            int dummy = 0;
-            block_argmax(mx, dummy, red, lane, wave);
-            float zsum = 0.f;
-            for (int i = tid; i < V; i += 1024) {
-                const float v = z(i);
-                if (fkey(v) >= kmin) zsum += __expf(v - mx);
-            }
-            zsum = block_sum_f(zsum, red, lane, wave);
-            const float target = (1.0f - top_p) * zsum;
-            if (!(top_p > 0.f)) {
-                only_max = true;
-            } else {
-                uint32_t t = 0;
-                for (int bit = 31; bit >= 0; --bit) {
-                    const uint32_t cand = t | (1u << bit);
-                    float mass = 0.f;
-                    for (int i = tid; i < V; i += 1024) {
-                        const float v = z(i);
-                        const uint32_t k = fkey(v);
-                        if (k >= kmin && k <= cand) mass += __expf(v - mx);
-                    }
-                    if (block_sum_f(mass, red, lane, wave) <= target) t = cand;
-                }
-                kgt = t;
-            }
-        }
-        // ---- multinomial over the kept set as a Gumbel-max: argmax_i (z_i - log(-log u_i)) ~ softmax(z) restricted to it
-        for (int i = tid; i < V; i += 1024) {
-            const float v = z(i);
-            const uint32_t k = fkey(v);
-            if (k < kmin || k <= kgt || !(v > -INFINITY)) continue;
-            const float g = only_max ? 0.f : -__logf(-__logf(sample_uniform(seed_lo, seed_hi, (uint32_t)step, (uint32_t)i)));
-            argmax_combine2(best, bi, v + g, i);
-        }
-        block_argmax(best, bi, red, lane, wave);
+        bi = lds_floats >= V ? sample_row(ScaledRow<true>{lg, zs, inv_t}, V, rs, step, red, tid, lane, wave)
+                             : sample_row(ScaledRow<false>{lg, zs, inv_t}, V, rs, step, red, tid, lane, wave);
     }
     return bi;
 }
+
 
 __global__ __launch_bounds__(1024) void select_embed_kernel(SelectArgs p) {
     VC_DYNAMIC_SMEM(float, zs);  // [V] scaled logits of the row (sampling only)
@@ -447,6 +582,39 @@ __global__ __launch_bounds__(64) void uniform_probe_kernel(const uint32_t* h, fl
 }
 void launch_uniform_probe(const uint32_t* h, float* u, float* gumbel, int n, hipStream_t s) {
     VC_LAUNCH(uniform_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, s, h, u, gumbel, n);
+}
+
+// test hook: the kept set of the sampled selection, from the threshold code select_row runs (same block shape, same staging)
+template <bool STAGED>
+VC_DEV void warp_support_row(const ScaledRow<STAGED>& z, int V, const int* rs, int* keep, BlockRed& red, int tid, int lane, int wave) {
+    z.stage(V, tid);
+    const WarpSet w = warp_thresholds(z, V, rs, red, tid, lane, wave);
+    for (int i = tid; i < V; i += 1024) keep[i] = warp_kept(w, z(i)) ? 1 : 0;
+}
+__global__ __launch_bounds__(1024) void warp_support_kernel(const float* logits, int ldl, int V, const int* rows, int* keep,
+                                                            int lds_floats) {
+    VC_DYNAMIC_SMEM(float, zs);  // [V] scaled logits of the row
+    __shared__ BlockRed red;
+    const int r = (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int* rs = rows + (size_t)r * RS_STRIDE;
+    const float* lg = logits + (size_t)r * ldl;
+    const float inv_t = __builtin_bit_cast(float, rs[RS_INVTEMP]);
+    if (lds_floats >= V) warp_support_row(ScaledRow<true>{lg, zs, inv_t}, V, rs, keep + (size_t)r * V, red, tid, lane, wave);
+    else warp_support_row(ScaledRow<false>{lg, zs, inv_t}, V, rs, keep + (size_t)r * V, red, tid, lane, wave);
+}
+void launch_warp_support(const float* logits, int ldl, int V, const int* rows, int nrows, int* keep, int lds_floats, hipStream_t s) {
+    if (nrows <= 0 || V <= 0) return;
+    size_t lds = (size_t)V * 4;
+    if (lds > 150 * 1024 || (lds_floats >= 0 && lds_floats < V)) lds = 0;
+#ifndef VC_EMU
+    static size_t allowed = 0;
+    if (lds > 48 * 1024 && lds > allowed) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(warp_support_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds);
+        allowed = lds;
+    }
+#endif
+    VC_LAUNCH(warp_support_kernel, dim3((unsigned)nrows), dim3(1024), lds, s, logits, ldl, V, rows, keep, (int)(lds / 4));
 }
 
 // ---- log-probability of one target token per logits row (scoring: forward(labels=), score()) -----------------------------------

@@ -590,7 +590,9 @@ class HipEngine:
                  on_tokens=None, stream_every: int = 1, attention_mask=None, logprobs: bool = False,
                  top_logprobs: int = 0, processors=None, eos_extra: Sequence[int] = (), speculate: Optional[int] = None,
                  lookup_ngram: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False,
-                 speculate_selection: str = "greedy", constraint: Optional[TokenAutomaton] = None, guidance=None) -> np.ndarray:
+                 speculate_selection: str = "greedy", constraint: Optional[TokenAutomaton] = None, guidance=None,
+                 min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                 eta_cutoff: Optional[float] = None) -> np.ndarray:
         """generate() on the device (vc_generate): greedy, or temperature / top-k / top-p sampling with a counter-based
         generator (same seed -> same tokens).  on_tokens(first_step, ids [B, n]) is called with every `stream_every` new
         columns while the hipGraph-replayed decode loop keeps running in between.  -> new ids [B, n_generated] int32.
@@ -640,7 +642,13 @@ class HipEngine:
         and sampled, processors, constraint, log-probs (of the raw conditional rows), EOS ids, stop sequences, on_tokens; the
         bf16 precision mode; the call runs on the session's own loop and closes it.  `speculate` is not served beside it
         (last_speculation is None).  num_return_sequences > 1: repeat the inputs instead (ValueError); 2 B above MAX_BATCH:
-        ValueError.  last_guidance = {"rows", "prompt_len", "negative_len"} of a served call, else None."""
+        ValueError.  last_guidance = {"rows", "prompt_len", "negative_len"} of a served call, else None.
+        min_p, typical_p, epsilon_cutoff, eta_cutoff (vc_request_sampling_warpers): HF's MinPLogitsWarper, TypicalLogitsWarper,
+        EpsilonLogitsWarper and EtaLogitsWarper of a sampled call, on the device behind top-p and in that order, each over the
+        survivors of those in front of it.  They travel in the rows' records: the call stays on the loop it would run on without
+        them (the decode pool included) and combines with everything above.  Off: None, 0 (typical_p: >= 1).  Not applied to a
+        greedy call.  ValueError for min_p outside [0, 1], typical_p <= 0, a cutoff outside [0, 1)."""
+        warp = _lp.check_warpers(min_p, typical_p, epsilon_cutoff, eta_cutoff)
         if constraint is not None and not isinstance(constraint, TokenAutomaton):
             raise ValueError(f"constraint has to be a constraints.TokenAutomaton, but is {type(constraint).__name__}")
         ids = self._ids(input_ids)
@@ -699,7 +707,8 @@ class HipEngine:
                                            pad_token_id=pad_token_id, stop_sequences=stop_sequences, do_sample=do_sample,
                                            temperature=temperature, top_k=top_k, top_p=top_p, seed=seed + b0,
                                            logprobs=want_lp, top_logprobs=K, processors=processors, eos_extra=eos_extra,
-                                           constraint=constraint))
+                                           constraint=constraint, min_p=min_p, typical_p=typical_p,
+                                           epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff))
                 lps.append(self.last_generate_logprobs)
                 lens.add(int(self.lib.vc_last_spliced_len(self._model)))
             if len(lens) > 1:
@@ -807,6 +816,19 @@ class HipEngine:
                 self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
                 self.lib.vc_request_logits_processors(self._model, None)
                 self.lib.vc_request_constraint(self._model, None)
+                raise
+        if do_sample and any(warp):
+            try:
+                self._check(self.lib.vc_request_sampling_warpers(self._model, C.c_float(warp[0]), C.c_float(warp[1] or 1.0),
+                                                                 C.c_float(warp[2]), C.c_float(warp[3])))
+            except BaseException:
+                self.lib.vc_clear_attention_mask(self._model)
+                self.lib.vc_request_generate_logprobs(self._model, 0, None, None, None, C.c_size_t(0))
+                self.lib.vc_request_logits_processors(self._model, None)
+                self.lib.vc_request_constraint(self._model, None)
+                self.lib.vc_request_speculation(self._model, 0, 0, None, None, 0)
+                self.lib.vc_request_fanout(self._model, 0)
+                self.lib.vc_request_guidance(self._model, C.c_float(1.0), None, 0, 0, None, None, None, 0)
                 raise
         self._check(self.lib.vc_generate(self._model, ids.ctypes.data_as(C.c_void_p), B, T, pi, ps, pd, on_dev,
                                          int(max_new_tokens), eos, pad,

@@ -113,6 +113,74 @@ def apply_guidance(cond, uncond, scale: float):
     return torch.tensor(float(scale), dtype=torch.float32) * (lc - lu) + lu
 
 
+def check_warpers(min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+    """generate(min_p=, typical_p=, epsilon_cutoff=, eta_cutoff=): validates them (ValueError, as HF's warpers raise it) ->
+    (min_p, typical_p, epsilon_cutoff, eta_cutoff) as floats with 0.0 for a warper that is off — HF's GenerationConfig rules: min_p
+    None or 0, typical_p None or >= 1, a cutoff None or 0."""
+    def number(name, v):
+        if v is None:
+            return None
+        if not isinstance(v, (int, float)) or isinstance(v, bool) or v != v:
+            raise ValueError(f"`{name}` has to be a float, but is {v!r}")
+        return float(v)
+
+    mp, ty = number("min_p", min_p), number("typical_p", typical_p)
+    ep, et = number("epsilon_cutoff", epsilon_cutoff), number("eta_cutoff", eta_cutoff)
+    if mp is not None and not 0.0 <= mp <= 1.0:
+        raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+    if ty is not None and not ty > 0.0:
+        raise ValueError(f"`typical_p` has to be a float > 0, but is {typical_p}")
+    if ep is not None and not 0.0 <= ep < 1.0:
+        raise ValueError(f"`epsilon_cutoff` has to be a float >= 0 and < 1, but is {epsilon_cutoff}")
+    if et is not None and not 0.0 <= et < 1.0:
+        raise ValueError(f"`eta_cutoff` has to be a float >= 0 and < 1, but is {eta_cutoff}")
+    return (mp or 0.0, ty if ty is not None and ty < 1.0 else 0.0, ep or 0.0, et or 0.0)
+
+
+def apply_warpers(scores, min_p: float = 0.0, typical_p: float = 0.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
+                  min_tokens_to_keep: int = 1):
+    """HF's MinPLogitsWarper -> TypicalLogitsWarper -> EpsilonLogitsWarper -> EtaLogitsWarper on `scores` [R, V] float32 (what
+    temperature, top-k and top-p left; removed entries -inf), each over the survivors of the one in front of it; arguments as
+    check_warpers returns them (0.0: off).  -> a new tensor with the removed entries at -inf.  What the host sampling loops apply
+    behind their top-p (min_tokens_to_keep 1) and beam-sample applies with min_tokens_to_keep = 2; the device sampler restates it
+    in warp_thresholds (csrc/select.hip)."""
+    import torch
+
+    ninf = float("-inf")
+    out = scores.float().clone()
+    keep_n = max(1, min(int(min_tokens_to_keep), out.shape[-1]))
+
+    def entropy(x):
+        lp = torch.log_softmax(x, dim=-1)
+        return -(lp * lp.exp()).nansum(dim=-1, keepdim=True), lp
+
+    def under_kth(x):   # the cutoffs spare every score that reaches the keep_n-th largest
+        return x < torch.topk(x, keep_n, dim=-1)[0][..., -1:]
+
+    if min_p > 0.0:
+        p = torch.softmax(out, dim=-1)
+        remove = p < min_p * p.amax(dim=-1, keepdim=True)
+        first = torch.argsort(out, dim=-1, descending=True)[..., :keep_n]
+        remove.scatter_(-1, first, False)
+        out = out.masked_fill(remove, ninf)
+    if 0.0 < typical_p < 1.0:
+        H, lp = entropy(out)
+        s, order = torch.sort((-lp - H).abs(), dim=-1, descending=False)
+        cum = out.gather(-1, order).softmax(dim=-1).cumsum(dim=-1)
+        last = (cum < typical_p).sum(dim=-1, keepdim=True).clamp_(max=out.shape[-1] - 1)
+        remove_sorted = s > s.gather(-1, last)
+        remove_sorted[..., :keep_n] = False
+        out = out.masked_fill(torch.zeros_like(remove_sorted).scatter_(-1, order, remove_sorted), ninf)
+    if epsilon_cutoff > 0.0:
+        out = out.masked_fill((torch.softmax(out, dim=-1) < epsilon_cutoff) & under_kth(out), ninf)
+    if eta_cutoff > 0.0:
+        H, _ = entropy(out)
+        e = torch.tensor(float(eta_cutoff), dtype=torch.float32)
+        eta = torch.minimum(e, torch.sqrt(e) * torch.exp(-H))
+        out = out.masked_fill((torch.softmax(out, dim=-1) < eta) & under_kth(out), ninf)
+    return out
+
+
 def apply_torch(proc: LogitsProcessors, history, scores, prompt_len: int, eos_ids: Sequence[int]):
     """`scores` [R, V] float32 of the next token behind `history` [R, L] int64 (prompt_len prompt ids, then the generated ones)
     -> the processed scores (a new tensor).  HF 4.31's order; fp32 arithmetic (the penalty's division is torch's IEEE division)."""

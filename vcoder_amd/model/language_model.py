@@ -458,7 +458,9 @@ class _HipCausalLMBase:
                  max_matching_ngram_size: int = 2, lookup_ids=None, num_return_sequences: int = 1, fan_out: bool = False,
                  speculate_selection: str = "greedy", constraint=None, prefix_allowed_tokens_fn=None,
                  guidance_scale: Optional[float] = None, negative_prompt_ids=None, negative_prompt_attention_mask=None,
-                 negative_images=None, negative_segs=None, negative_depths=None, **kwargs):
+                 negative_images=None, negative_segs=None, negative_depths=None, min_p: Optional[float] = None,
+                 typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None, eta_cutoff: Optional[float] = None,
+                 **kwargs):
         """Returns cat(input_ids, new_ids) [B, T+n] int64 — the prompt part keeps its negative placeholder ids,
         callers slice `[:, T:]` (serve/cli.py:135).
 
@@ -576,6 +578,21 @@ class _HipCausalLMBase:
         (NotImplementedError for a text-only one, as a padded text-only batch), 2 B n above 16 rows (ValueError); num_beams > 1
         (NotImplementedError).
 
+        min_p / typical_p / epsilon_cutoff / eta_cutoff: Transformers' MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper and
+        EtaLogitsWarper with min_tokens_to_keep = 1, behind top-p and in that order — temperature -> top-k -> top-p -> min-p ->
+        typical -> epsilon -> eta -> draw — each over the survivors of those in front of it (its softmax and entropy see -inf where
+        something was removed).  min_p removes p < min_p * max p; typical_p keeps, in ascending order of |-log p - H|, the tokens
+        up to the one whose cumulative probability reaches it; epsilon_cutoff removes p < epsilon; eta_cutoff removes
+        p < min(eta, sqrt(eta) exp(-H)); the two cutoffs spare every score that equals the maximum.  Off (HF's GenerationConfig
+        rules): min_p None or 0, typical_p None or >= 1, a cutoff None or 0 — the call then takes exactly the path and returns
+        exactly the ids it does without the arguments.  On the device they are four more thresholds of the sampler (warp_thresholds
+        in csrc/select.hip), carried in the row's record: a call keeps the loop it would run on, the decode pool included, and
+        they combine with the processors, `constraint`, guidance, log-probs (of the raw rows), num_return_sequences and
+        prompt_lookup_num_tokens under speculate_selection="any".  The host sampling loop applies
+        logits_processors.apply_warpers behind its top-p, beam-sample with min_tokens_to_keep = 2 (4.31's rule for beams).  Not
+        applied to a greedy call, as in HF; validated all the same, before the engine is touched: ValueError for min_p outside
+        [0, 1], typical_p <= 0, a cutoff outside [0, 1).
+
         Everything the reference's callers ask for runs on the device inside the hipGraph-replayed decode loop
         (vc_generate): greedy argmax; sampling with HF's warper order temperature -> top-k -> top-p -> multinomial
         (`top_k` defaults to 50 when sampling, HF's GenerationConfig default, which is what serve/cli.py:122-132 gets);
@@ -614,6 +631,7 @@ class _HipCausalLMBase:
             raise ValueError(f"`constraint` has to be a vcoder_amd.constraints.TokenAutomaton, but is {type(constraint).__name__}")
         if prefix_allowed_tokens_fn is not None and not callable(prefix_allowed_tokens_fn):
             raise ValueError(f"`prefix_allowed_tokens_fn` has to be callable, but is {type(prefix_allowed_tokens_fn).__name__}")
+        warp = _lp.check_warpers(min_p, typical_p, epsilon_cutoff, eta_cutoff)   # (0.0: off)
         nrs = int(num_return_sequences)
         if nrs < 1:
             raise ValueError(f"`num_return_sequences` has to be at least 1, got {num_return_sequences!r}")
@@ -653,7 +671,7 @@ class _HipCausalLMBase:
                 if generator is None:
                     generator = torch.Generator().manual_seed(int(seed if seed is not None else torch.initial_seed()) & 0x7FFFFFFFFFFFFFFF)
                 sample = dict(temperature=float(temperature or 1.0), top_k=50 if top_k is None else int(top_k),
-                              top_p=1.0 if top_p is None else float(top_p), generator=generator)
+                              top_p=1.0 if top_p is None else float(top_p), generator=generator, warp=warp)
             beam_args = (input_ids, images, segs, depths, int(num_beams), max_new_tokens, max_length, eos_token_id, pad_token_id,
                          attention_mask)
             beam_kw = (float(kwargs.get("length_penalty", 1.0)), kwargs.get("early_stopping", False),
@@ -767,6 +785,8 @@ class _HipCausalLMBase:
                                        lookup_ngram=int(max_matching_ngram_size), lookup_ids=lookup_ids,
                                        speculate_selection=speculate_selection, constraint=constraint,
                                        **(dict(guidance=gd) if gd is not None else {}),
+                                       **(dict(min_p=warp[0], typical_p=warp[1] or None, epsilon_cutoff=warp[2], eta_cutoff=warp[3])
+                                          if do_sample and any(warp) else {}),
                                        **(dict(num_return_sequences=nrs, fan_out=bool(fan_out)) if nrs > 1 and gd is None else {}))
             self._generation += 1
             out = torch.cat([ids_cpu, torch.from_numpy(new.astype(np.int64))], dim=1)
@@ -808,6 +828,8 @@ class _HipCausalLMBase:
                         scores = scores.masked_fill(scores < kth, float("-inf"))
                     if top_p is not None and top_p < 1.0:
                         scores = _top_p_filter(scores, float(top_p))
+                    if any(warp):
+                        scores = _lp.apply_warpers(scores, *warp)
                     probs = torch.softmax(scores, dim=-1)
                     nxt = torch.multinomial(probs, 1, generator=generator).squeeze(1)
                 else:
@@ -1037,6 +1059,8 @@ class _HipCausalLMBase:
                     w = w.masked_fill(w < kth, float("-inf"))
                 if sample["top_p"] < 1.0:
                     w = _top_p_filter(w, sample["top_p"], min_tokens_to_keep=2)   # 4.31: min_tokens_to_keep = 2 when num_beams > 1
+                if any(sample.get("warp", ())):
+                    w = _lp.apply_warpers(w, *sample["warp"], min_tokens_to_keep=2)
                 flat = w.view(B, nb * V)
                 probs = torch.softmax(flat, dim=-1)
                 # torch.multinomial without replacement needs >= 2n non-zero entries (step 0: only beam 0 is alive, and a tight
